@@ -9,22 +9,31 @@
   5                          large-batch stress: flanger render + multi-resolution STFT loss forward / backward,
                              bs = 256 x 4 s per GPU (2048 x 4 s over 8 GPUs)
 
-    python bench.py --gpus N --steps K --warmup W [--config 3]
+    python bench.py --gpus N --steps K --warmup W [--config 3] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
 Outside torchrun the first form is a LAUNCHER: it never touches the GPU itself, starts the N rank processes (fresh
-children; through torch.distributed.run when N > 1) and relays rank 0's result.  At N = 1 on the headline config it
-then measures configs 2 / 4 / 5 the same way (one fresh process each) and appends them as `other_configs`, so a single
-driver run carries every BASELINE configuration.  `--worker` runs one measurement in the calling process (use that
-form under rocprofv3).
+children; through torch.distributed.run when N > 1) and relays rank 0's result.  `--worker` runs one measurement in the
+calling process (use that form under rocprofv3).
+
+A plain run does only what the headline needs: set up, warm up, time exactly K steps, write the outputs (`--dump-outputs`),
+print the line.  The figures that take work of their own -- the isolated effect / LSTM launches with their serial and
+independent floors, the exact-fp32 leg, `cpu_baseline`, and at N = 1 on the headline config the configs 2 / 4 / 5 (one
+fresh process each, appended as `other_configs`) -- are measured with `--full` only.  Per-kernel times and the config 2 /
+3 / 5 roofline come from the timed steps themselves and are in both.
+
+`--dump-outputs DIR` writes what the last timed step computed, as DIR/<name>.npy in float32 / float64 (< 64 MB): the
+loss, the parameters after the step and their gradients, and the step's synthesized batch; an output larger than
+DUMP_SAMPLE elements is cut to the same seeded sample of positions every run.  Seeds are fixed, so the same arguments
+give the same inputs from run to run and two builds can be compared output for output.
 
 OUTPUT (round 6).  The LAST stdout line is ONE short JSON object (< 6 KB: `compact()` below) -- metric, value, unit,
-n_gpus, steps, warmup, ms_per_step, dtype, config, `roofline` (numbers + one short note), `cpu_baseline`, step statistics,
-floor fractions of the sample-recurrent kernels, and a five-number summary per other config.  Everything else (per-kernel
-tables, notes, floors, the other configs in full) goes to `bench_detail.json` next to this file (`--detail-out PATH`) and,
-as one `BENCH_DETAIL {...}` line, to stderr.  N > 1: the line also carries `allreduce_ms`, `step_ms_per_rank`,
-`rank_median_spread_ms`.
+n_gpus, steps, warmup, ms_per_step, dtype, config, `roofline` (numbers + one short note), step statistics and, with
+`--full`, `cpu_baseline`, floor fractions of the sample-recurrent kernels and a five-number summary per other config.
+Everything else (per-kernel tables, notes, floors, the other configs in full) goes to `bench_detail.json` next to this
+file (`--detail-out PATH`) and, as one `BENCH_DETAIL {...}` line, to stderr.  N > 1: the line also carries
+`allreduce_ms`, `step_ms_per_rank`, `rank_median_spread_ms`.
 
 One step of config 2 / 3 = on-device batch synthesis (LFO synth, flanger/chorus, phaser; inputs are generated in
 HBM) -> log-mel -> 6-block 2D-CNN forward -> L1 + 5*FDL1 + 10*SDL1 loss -> backward -> gradient all-reduce (RCCL)
@@ -45,11 +54,12 @@ Extra objects in the JSON line:
                 (the flanger / chorus launch): for a kernel whose HBM time is 1 % of its dependency chain the chain,
                 not HBM, is the roofline that governs, and both fractions are printed.
   step_ms       min / median / max over the timed steps (HIP events on the main stream)
-  exact_fp32_path  (config 2 / 3, N = 1) the same step with the exact-fp32 MFMA convolutions, 3 steps
-  cpu_baseline  the CPU oracle (oracle/: torch fp32 + C effects, "port") timed on this host's cores on a bounded
+  exact_fp32_path  (--full; config 2 / 3, N = 1) the same step with the exact-fp32 MFMA convolutions, 3 steps
+  cpu_baseline  (--full) the CPU oracle (oracle/: torch fp32 + C effects, "port") timed on this host's cores on a bounded
                 sample (rank 0, N = 1 only); `reference_shaped` inside it = SURVEY 8d's form (B = 16, the flanger as the
                 reference's python loop per sample, timed on a short stretch and extrapolated).
-  other_configs (N = 1, config 3) value / ms / roofline / floors of configs 2, 4, 5, each measured in its own process.
+  other_configs (--full; N = 1, config 3) value / ms / roofline / floors of configs 2, 4, 5, each measured in its own
+                process.
 """
 import argparse
 import json
@@ -159,6 +169,33 @@ def hbm_block(kernel: str, bytes_alg: float, ms: float, floor_ms=None, note=None
 
 def mean(v):
     return sum(v) / len(v)
+
+
+DUMP_SAMPLE = 1 << 20               # elements kept of a larger output: the same seeded positions every run
+DUMP_CAP_BYTES = 64 * 10 ** 6
+
+
+def dump_array(t, sample=False):
+    """One output of the timed path as a host float32 / float64 array; `sample`: a larger tensor is cut to DUMP_SAMPLE
+    positions of its flattened form, drawn from a fixed seed (the same positions for every tensor of that size)."""
+    import numpy as np
+    t = t.detach()
+    if sample and t.numel() > DUMP_SAMPLE:
+        idx = np.sort(np.random.default_rng(0).choice(t.numel(), DUMP_SAMPLE, replace=False))
+        t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+    a = t.cpu().numpy()
+    return a if a.dtype == np.float64 else a.astype(np.float32)
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: write {name: array} as out_dir/<name>.npy (refuses more than DUMP_CAP_BYTES in all)."""
+    import numpy as np
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_CAP_BYTES:
+        raise ValueError(f"--dump-outputs: {total} bytes exceed the {DUMP_CAP_BYTES}-byte cap")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def sync_replicas(opt):
@@ -517,9 +554,11 @@ def run_lfo_config(args, env, cfg_id):
     if args.conv_precision:
         module.model.conv_precision = args.conv_precision
     runner = tr.Trainer(log_fn=None)
+    last = {}
 
     def step():
-        return runner.train_step(module, opt, batcher.next_batch())
+        last["batch"] = batcher.next_batch()
+        return runner.train_step(module, opt, last["batch"])
 
     for _ in range(args.warmup):
         step()
@@ -528,6 +567,11 @@ def run_lfo_config(args, env, cfg_id):
                                             conv_key)
     if rank != 0:
         return None
+    if args.dump_outputs:
+        dry, wet, mod, _ = last["batch"]
+        dump_outputs(args.dump_outputs, {"loss": dump_array(loss), "params": dump_array(opt.flat_param),
+                                         "grads": dump_array(opt.flat_grad), "dry": dump_array(dry, sample=True),
+                                         "wet": dump_array(wet, sample=True), "mod": dump_array(mod, sample=True)})
     audio_s = world * batch * (N_SAMPLES / SR) * args.steps
     kernels = {}
     fx_live = {}
@@ -589,6 +633,8 @@ def run_lfo_config(args, env, cfg_id):
         "final_loss": None if loss is None else float(loss.detach()),
     }
     out.update(scale_fields(step_ms, opt.flat_grad.numel() * 4))
+    if not args.full:
+        return out
     # the effect kernels: live durations (side stream, concurrent with the train step) and an isolated pass with the
     # measured serial floor
     with torch.no_grad():
@@ -685,8 +731,10 @@ def run_config4(args, env):
         part[0].wait_stream(torch.cuda.current_stream(device))
         torch.cuda.set_stream(part[0])
 
+    last = {}
+
     def step():
-        dry, wet, _, _ = bt.next_batch()
+        dry, wet, _, _ = last["batch"] = bt.next_batch()
         out = mod.training_step((dry, wet, None, None), 0, optimizer=opt, world_size=world, prep=bt.last_ahead)
         kept.append(mod.last_kept)
         return out
@@ -700,6 +748,56 @@ def run_config4(args, env):
     dt, timings, step_ms, loss = timed_loop(step, args.steps, world, device, names)
     if rank != 0:
         return None
+    if args.dump_outputs:
+        dry, wet, _, _ = last["batch"]
+        arrays = {"params": dump_array(opt.flat_param), "grads": dump_array(opt.flat_grad),
+                  "dry": dump_array(dry, sample=True), "wet": dump_array(wet, sample=True)}
+        if loss is not None:                # (no loss when the validity filter kept no clip of the batch)
+            arrays["loss"] = dump_array(loss)
+        dump_outputs(args.dump_outputs, arrays)
+    audio_s = world * B * cfg["seconds"] * args.steps
+    live = {k: mean(v) for k, v in timings.items()}
+    per_batch = {k: round(sum(v) / args.steps, 3) for k, v in timings.items()}
+    kernels = {}
+    if args.full:
+        kernels = config4_isolated(device, em, B, S, bt)
+    out = {
+        "metric": METRIC[4], "value": audio_s / dt, "unit": "audio-seconds/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": 1e3 * dt / args.steps, "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "config": {"workload": f"train_em_dry_wet: frozen 2D-CNN LFO extractor + LSTM-64 effect model, truncated BPTT with "
+                               f"{W}-sample warm-up and {n_chunks} optimizer steps of {S} samples per batch, L1 loss, bs={B} x 2 s "
+                               f"@44.1 kHz per GPU, synthetic dry + this package's phaser render as the wet target",
+                   "baseline_config": 4, "global_batch": world * B, "n_samples": N_SAMPLES, "parallelism": f"dp{world}",
+                   "optimizer_steps_per_batch": n_chunks, "loss_dict": loss_dict,
+                   "lfo_filter": ("model_smooth_n_frames 8, should_stretch, discard_invalid_lfos (train_em_dry_wet.yml); frozen CNN forward "
+                                  "runs in full, its output is replaced by the ground-truth LFO + 1 % noise (no pretrained extractor in "
+                                  "this image; an untrained one leaves no valid row)") if discard else "none (--em-no-discard)",
+                   "clips_trained_per_batch": {"mean": round(mean(kept), 1), "min": min(kept), "of": B},
+                   "pipelining": ("batch render + frozen extractor forward of batch i+1 on a side stream under the TBPTT loop of "
+                                  "batch i" + ("; recurrence on 20 CUs of every XCD, prefetch work on the other 12 of every XCD (CU-masked streams)" if part is not None
+                                               else "")) if not args.no_overlap else "none"},
+        "roofline": kernels.get("lstm_fwd_kernel"),
+        "kernels": kernels,
+        "ms_per_batch_by_entry_point": per_batch,
+        "avg_launch_ms_in_step": {k: round(v, 4) for k, v in live.items()},
+        "step_ms": step_ms,
+        "final_loss": None if loss is None else float(loss.detach()),
+    }
+    # reference semantics: `value` counts every clip of the batch (all are rendered and pass the frozen extractor); the
+    # LSTM trains on the rows that survive the LFO validity filter -- both rates are quoted
+    out["value_clips_rendered"] = out["value"]
+    out["value_clips_trained"] = world * mean(kept) * cfg["seconds"] * args.steps / dt
+    out.update(scale_fields(step_ms, opt.flat_grad.numel() * 4))
+    if world == 1 and args.full and not args.no_cpu_baseline:
+        out["cpu_baseline"] = cpu_baseline_tbptt()
+    return out
+
+
+def config4_isolated(device, em, B, S, bt):
+    """--full, config 4: the LSTM launches of one chunk in isolation with their serial and independent floors, and the
+    phaser launch of one batch with its floors."""
+    from mod_extraction_amd import _hip, models
     # isolated chunk launches with the serial floor
     x = torch.rand(B, 1, S, device=device) * 2 - 1
     lat, wet = torch.rand(B, 1, S, device=device), torch.rand(B, 1, S, device=device) * 2 - 1
@@ -750,46 +848,13 @@ def run_config4(args, env):
                 "; no global memory, input term, stash, output layer or weight gradients")
         except Exception as e:
             kernels[key]["independent_floor_error"] = repr(e)
-    live = {k: mean(v) for k, v in timings.items()}
-    per_batch = {k: round(sum(v) / args.steps, 3) for k, v in timings.items()}
     with torch.no_grad():
         params = bt.sample_params()
     torch.cuda.synchronize()
     ahead, bt.ahead_fn = bt.ahead_fn, None
     kernels.update(fx_blocks(bt, params, fx_floor_pass(bt, params)))
     bt.ahead_fn = ahead
-    audio_s = world * B * cfg["seconds"] * args.steps
-    out = {
-        "metric": METRIC[4], "value": audio_s / dt, "unit": "audio-seconds/s", "n_gpus": world, "steps": args.steps,
-        "warmup": args.warmup, "ms_per_step": 1e3 * dt / args.steps, "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-        "config": {"workload": f"train_em_dry_wet: frozen 2D-CNN LFO extractor + LSTM-64 effect model, truncated BPTT with "
-                               f"{W}-sample warm-up and {n_chunks} optimizer steps of {S} samples per batch, L1 loss, bs={B} x 2 s "
-                               f"@44.1 kHz per GPU, synthetic dry + this package's phaser render as the wet target",
-                   "baseline_config": 4, "global_batch": world * B, "n_samples": N_SAMPLES, "parallelism": f"dp{world}",
-                   "optimizer_steps_per_batch": n_chunks, "loss_dict": loss_dict,
-                   "lfo_filter": ("model_smooth_n_frames 8, should_stretch, discard_invalid_lfos (train_em_dry_wet.yml); frozen CNN forward "
-                                  "runs in full, its output is replaced by the ground-truth LFO + 1 % noise (no pretrained extractor in "
-                                  "this image; an untrained one leaves no valid row)") if discard else "none (--em-no-discard)",
-                   "clips_trained_per_batch": {"mean": round(mean(kept), 1), "min": min(kept), "of": B},
-                   "pipelining": ("batch render + frozen extractor forward of batch i+1 on a side stream under the TBPTT loop of "
-                                  "batch i" + ("; recurrence on 20 CUs of every XCD, prefetch work on the other 12 of every XCD (CU-masked streams)" if part is not None
-                                               else "")) if not args.no_overlap else "none"},
-        "roofline": kernels["lstm_fwd_kernel"],
-        "kernels": kernels,
-        "ms_per_batch_by_entry_point": per_batch,
-        "avg_launch_ms_in_step": {k: round(v, 4) for k, v in live.items()},
-        "step_ms": step_ms,
-        "final_loss": None if loss is None else float(loss.detach()),
-    }
-    # reference semantics: `value` counts every clip of the batch (all are rendered and pass the frozen extractor); the
-    # LSTM trains on the rows that survive the LFO validity filter -- both rates are quoted
-    out["value_clips_rendered"] = out["value"]
-    out["value_clips_trained"] = world * mean(kept) * cfg["seconds"] * args.steps / dt
-    out.update(scale_fields(step_ms, opt.flat_grad.numel() * 4))
-    if world == 1 and not args.no_cpu_baseline:
-        out["cpu_baseline"] = cpu_baseline_tbptt()
-    return out
+    return kernels
 
 
 def cpu_baseline_tbptt(batch_cpu: int = 4):
@@ -828,12 +893,15 @@ def run_config5(args, env):
     torch.manual_seed(45 + rank); np.random.seed(45 + rank)
     bt = data_modules.SyntheticFxBatcher(B, N, SR, cfg["kinds"], device, audio_seed=45 + rank, overlap=not args.no_overlap)
     loss_fn = losses.get_loss_func_by_name("mrstft")
+    last = {}
 
     def step():
         dry, wet, _, _ = bt.next_batch()
         pred = torch.lerp(dry, wet, 0.9).requires_grad_(True)      # stand-in prediction (one pass): the loss path is what is measured
         loss = loss_fn(pred, wet)
         loss.backward()
+        if args.dump_outputs:       # (only then: the kept tensors stay alive into the next step)
+            last.update(dry=dry, wet=wet, grad=pred.grad)
         return loss.detach()        # (a live graph of the previous step changes the allocator's pattern: one 40 ms hipMalloc)
 
     for _ in range(args.warmup):
@@ -841,12 +909,17 @@ def run_config5(args, env):
     dt, timings, step_ms, loss = timed_loop(step, args.steps, world, device, {"mx_flanger_fwd", "mx_mrstft_loss"})
     if rank != 0:
         return None
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"loss": dump_array(loss), "grad": dump_array(last["grad"], sample=True),
+                                         "dry": dump_array(last["dry"], sample=True), "wet": dump_array(last["wet"], sample=True)})
     live = {k: mean(v) for k, v in timings.items()}
-    with torch.no_grad():
-        params = bt.sample_params()
-    torch.cuda.synchronize()
-    kernels = fx_blocks(bt, params, fx_floor_pass(bt, params))
-    kernels["flanger_kernel"]["avg_launch_ms_in_step"] = round(live["mx_flanger_fwd"], 4)
+    kernels = {}
+    if args.full:
+        with torch.no_grad():
+            params = bt.sample_params()
+        torch.cuda.synchronize()
+        kernels = fx_blocks(bt, params, fx_floor_pass(bt, params))
+        kernels["flanger_kernel"]["avg_launch_ms_in_step"] = round(live["mx_flanger_fwd"], 4)
     mr = hbm_block("mr_onepass_kernel x {512, 1024, 2048} + mr_fold_all_kernel (losses.py:155-156)",
                    B * N * 12.0, live["mx_mrstft_loss"],
                    note="12 B/sample algorithmic: x, y read once, d loss / d x written once; three STFT resolutions forward and "
@@ -892,7 +965,7 @@ def run_config5(args, env):
         out["fx_kernel_frac_of_serial_floor"] = kernels["flanger_kernel"].get("frac_of_serial_floor")
         out["fx_kernel_frac_of_independent_floor"] = kernels["flanger_kernel"].get("frac_of_independent_floor")
         out["fx_kernel_frac_of_hbm"] = kernels["flanger_kernel"]["frac"]
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline_stress(N)
     return out
 
@@ -1049,22 +1122,29 @@ def parse_args(argv=None):
     ap.add_argument("--em-no-discard", action="store_true",
                     help="config 4: no LFO validity filter, random-init extractor output used as is (the round-1/2 form)")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="N = 1, config 3: do not append the configs 2 / 4 / 5 measurements (`other_configs`)")
+                    help="--full, N = 1, config 3: do not append the configs 2 / 4 / 5 measurements (`other_configs`)")
     ap.add_argument("--detail-out", default=None,
                     help="where the full measurement dict is written (default: bench_detail.json next to bench.py)")
     ap.add_argument("--worker", action="store_true",
                     help="run the measurement in THIS process (set by the launcher; use it under rocprofv3)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: isolated kernel launches and their floors, the "
+                         "exact-fp32 leg, the CPU baselines and (N = 1, config 3) the configs 2 / 4 / 5")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed to DIR/<name>.npy (float32 / float64, < 64 MB)")
     args = ap.parse_args(argv)
     if args.steps is None:
         args.steps = {2: 100, 3: 100, 4: 5, 5: 20}[args.config]
+    if args.dump_outputs:
+        args.dump_outputs = os.path.abspath(args.dump_outputs)        # (the launcher's workers run in this file's directory)
     return args
 
 
 # ---------------------------------------------------------------------------------------------------------------
 # launcher: `python bench.py --gpus N` outside torchrun.  This process never touches the GPU (it does not even import
 # torch); it starts fresh worker processes -- one per rank through torch.distributed.run for N > 1 -- and relays rank
-# 0's JSON line.  For the N = 1 headline it then runs the other BASELINE configurations the same way and appends
-# them to that line as `other_configs`, so one driver run carries every config.
+# 0's JSON line.  With --full, for the N = 1 headline it then runs the other BASELINE configurations the same way and
+# appends them to that line as `other_configs`, so one run carries every config.
 def _free_port() -> int:
     import socket
     with socket.socket() as s:
@@ -1114,6 +1194,8 @@ def _worker_cmd(args, config, steps, extra=()):
         cmd.append("--em-no-discard")
     if args.em_step != 1024:
         cmd += ["--em-step", str(args.em_step)]
+    if args.full:
+        cmd.append("--full")
     return cmd + list(extra)
 
 
@@ -1122,6 +1204,8 @@ def launch(args) -> int:
     import tempfile
     tmp_detail = os.path.join(tempfile.gettempdir(), f"bench_detail_{os.getpid()}.json")
     flags = (["--no-cpu-baseline"] if args.no_cpu_baseline else []) + (["--no-fp32-leg"] if args.no_fp32_leg else [])
+    if args.dump_outputs:                       # (the headline only: the other configs' legs write nothing)
+        flags += ["--dump-outputs", args.dump_outputs]
     for _ in range(4):                          # (a free port can be taken between finding it and torchrun's bind: try another one)
         if args.gpus > 1:
             cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus),
@@ -1141,7 +1225,7 @@ def launch(args) -> int:
     if rc != 0:
         out["worker_stderr_tail"] = err[-400:]
     worst = rc
-    if args.gpus == 1 and args.config == 3 and not args.no_other_configs and not args.batch and not args.conv_precision:
+    if args.full and args.gpus == 1 and args.config == 3 and not args.no_other_configs and not args.batch and not args.conv_precision:
         others = {}
         for c, steps in ((2, 30), (4, 5), (5, 20)):
             t0 = time.perf_counter()

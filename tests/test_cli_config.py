@@ -1,5 +1,5 @@
 """CPU: the YAML entry layer (mod_extraction_amd/cli.py) builds the same object graph from this repo's
-configs and -- where /root/reference is mounted -- from the reference's own shipped configs."""
+configs and from the reference's own shipped configs (stored as data in tests/golden/reference_configs.json)."""
 import os
 
 import pytest
@@ -8,8 +8,23 @@ import torch
 from mod_extraction_amd import cli, data_modules, lightning, models, optim
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference"
 CPU = torch.device("cpu")
+
+
+@pytest.fixture(scope="module")
+def ref_root(tmp_path_factory, golden_dir):
+    """The reference's configuration tree (tests/golden/make_golden_configs.py) written back out as YAML files in its
+    own layout, <root>/configs/..., so that its `../configs/...` indirections resolve as they do in the reference."""
+    import json
+    import yaml
+    root = tmp_path_factory.mktemp("reference")
+    with open(os.path.join(golden_dir, "reference_configs.json")) as f:
+        entries = json.load(f)
+    for rel, cfg in entries.items():
+        path = root / "configs" / rel
+        path.parent.mkdir(parents=True, exist_ok=True)
+        path.write_text(yaml.safe_dump(cfg, sort_keys=False))
+    return str(root)
 
 
 def build(path, cwd):
@@ -50,14 +65,13 @@ def test_other_configs(name, kind):
         assert c.model.model_smooth_n_frames == 4 and c.datamodule.batch_size == 16
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference checkout not mounted (GPU box)")
 @pytest.mark.parametrize("name", ["train_lfo_phaser.yml", "train_lfo_interwoven_all.yml", "train_lfo_flanger.yml",
                                   "train_em_dry_wet.yml", "train_baseline_em_dry_wet.yml", "prototyping_lfo_dry_wet.yml",
                                   "eval_lfo.yml", "eval_lfo_combined.yml", "eval_lfo_distorted.yml", "eval_lfo_quasi.yml",
                                   "eval_lfo_rand.yml", "eval_lfo_unseen_audio.yml", "eval_em_unseen_effect.yml"])
-def test_reference_configs_parse(name):
-    """EVERY top-level YAML the reference ships (read in place, never copied) resolves to this package's classes."""
-    cfg = cli.apply_links(cli.load_config(os.path.join(REF, "configs", name)))
+def test_reference_configs_parse(name, ref_root):
+    """EVERY top-level YAML the reference ships resolves to this package's classes."""
+    cfg = cli.apply_links(cli.load_config(os.path.join(ref_root, "configs", name)))
     # the pretrained LFO-net .pt / .ckpt are large blobs absent from the mount
     if "lfo_model_weights_path" in cfg["model"]["init_args"]:
         cfg["model"]["init_args"]["lfo_model_weights_path"] = None
@@ -103,13 +117,12 @@ def test_fractional_batch_limits():
     assert trainer._limit(100, 0.1) == 10 and trainer._limit(100, 1.0) == 100 and trainer._limit(100, 2.0) == 2
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference checkout not mounted (GPU box)")
-def test_reference_trained_and_model_configs_parse():
-    """configs/trained/*.yml (the 27 experiment configs behind the paper's tables) and configs/models/*.yml, read in
-    place: every object graph builds.  models/spectral_tcn.yml carries a stale `smooth_n_frames` argument that the
+def test_reference_trained_and_model_configs_parse(ref_root):
+    """configs/trained/*.yml (the 27 experiment configs behind the paper's tables) and configs/models/*.yml of the
+    reference: every object graph builds.  models/spectral_tcn.yml carries a stale `smooth_n_frames` argument that the
     reference's own SpectralTCN rejects; the mirror rejects it the same way."""
     import glob
-    trained = sorted(glob.glob(os.path.join(REF, "configs", "trained", "*.yml")))
+    trained = sorted(glob.glob(os.path.join(ref_root, "configs", "trained", "*.yml")))
     assert len(trained) >= 20
     for path in trained:
         cfg = cli.apply_links(cli.load_config(path))
@@ -119,7 +132,7 @@ def test_reference_trained_and_model_configs_parse():
         model, data = cli.instantiate(cfg["model"]), cli.instantiate(cfg["data"])
         assert type(model).__name__ == cfg["model"]["class_path"].rsplit(".", 1)[1], path
         assert type(data).__name__ == cfg["data"]["class_path"].rsplit(".", 1)[1], path
-    for path in sorted(glob.glob(os.path.join(REF, "configs", "models", "*.yml"))):
+    for path in sorted(glob.glob(os.path.join(ref_root, "configs", "models", "*.yml"))):
         cfg = cli.load_config(path)
         if os.path.basename(path) == "spectral_tcn.yml":
             with pytest.raises(TypeError):

@@ -336,13 +336,14 @@ def test_bench_two_ranks_sharing_the_gpu_over_gloo(config):
     """bench.py's N > 1 path -- torchrun environment, barrier + max-over-ranks timing, per-rank clip shards, the flat
     gradient all-reduce, rank 0 printing the one JSON line -- with TWO ranks on this box's single GPU.  RCCL refuses two
     ranks on one device, so the collectives go through gloo (MODEX_DIST_BACKEND) and LOCAL_RANK is folded onto the
-    existing device (MODEX_SHARE_GPU): the code path is the driver's multi-GPU launch, only the transport differs."""
+    existing device (MODEX_SHARE_GPU): the code path is the driver's multi-GPU launch, only the transport differs.
+    (--full: config 4's roofline is measured on isolated launches.)"""
     import json
     from tests.helpers.torchrun import run_torchrun
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, MODEX_SHARE_GPU="1", MODEX_DIST_BACKEND="gloo")
     res = run_torchrun(2, [os.path.join(root, "bench.py"), "--gpus", "2", "--config", str(config), "--steps", "2",
-                           "--warmup", "1", "--batch", "8"], env=env, cwd=root, timeout=600)
+                           "--warmup", "1", "--batch", "8", "--full"], env=env, cwd=root, timeout=600)
     assert res.returncode == 0, res.stderr[-2000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, res.stdout[-2000:]                 # rank 0 only
@@ -471,10 +472,10 @@ def test_tbptt_step_through_rccl_with_the_cu_partition_installed(dev):
 
 
 def test_bench_driver_command_prints_one_short_parseable_line():
-    """The driver's exact command (`python3 bench.py --gpus 1 --steps 20 --warmup 5`): the LAST stdout line is one
+    """The driver's full command (`python3 bench.py --gpus 1 --steps 20 --warmup 5 --full`): the LAST stdout line is one
     self-contained JSON object under 6 KB with `roofline` and `cpu_baseline`, the other BASELINE configurations as short
     summaries, nothing after it on stdout; the full per-kernel detail goes to bench_detail.json / stderr."""
-    out, detail = _run_bench(["--gpus", "1", "--steps", "20", "--warmup", "5"], timeout=1500, want_detail=True)
+    out, detail = _run_bench(["--gpus", "1", "--steps", "20", "--warmup", "5", "--full"], timeout=1500, want_detail=True)
     assert out["n_gpus"] == 1 and out["steps"] == 20 and out["warmup"] == 5 and out["dtype"] == "f32"
     assert out["config"]["baseline_config"] == 3 and out["config"]["global_batch"] == 256
     r = out["roofline"]
@@ -496,6 +497,31 @@ def test_bench_driver_command_prints_one_short_parseable_line():
         assert o["config"]["baseline_config"] == int(k) and "kernels" in o
     assert 0 < detail["other_configs"]["4"]["config"]["clips_trained_per_batch"]["mean"] <= 128   # the YAML's LFO validity filter is on
     assert all("tflops" not in v for k, v in detail["kernels"].items() if k.startswith("conv_prep"))
+
+
+def test_bench_plain_run_times_only_the_headline_and_dumps_its_outputs(tmp_path):
+    """The plain command (`bench.py --gpus 1 --steps K --warmup W`) times exactly K steps of the headline and measures
+    nothing else; `--dump-outputs DIR` writes the last timed step's outputs as float32 / float64 .npy files under 64 MB,
+    and a second run with the same arguments renders the same batches."""
+    runs = []
+    for i in range(2):
+        d = tmp_path / f"run{i}"
+        out = _run_bench(["--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(d)], timeout=600)
+        assert out["n_gpus"] == 1 and out["steps"] == 3 and out["warmup"] == 1 and out["config"]["baseline_config"] == 3
+        assert out["higher_is_better"] is True and out["dtype"] == "f32" and out["unit"] == "audio-seconds/s"
+        assert abs(out["value"] - 256 * 2.0 / (out["ms_per_step"] * 1e-3)) < 1e-6 * out["value"]
+        assert out["roofline"]["bound"] == "mfma" and out["roofline"]["frac"] > 0 and out["worker_rc"] == 0
+        for k in ("cpu_baseline", "other_configs", "exact_fp32_path", "fx_kernel_frac_of_serial_floor", "recurrent_kernels"):
+            assert k not in out, k
+        files = sorted(os.listdir(d))
+        assert files == ["dry.npy", "grads.npy", "loss.npy", "mod.npy", "params.npy", "wet.npy"], files
+        arrays = {f[:-4]: np.load(d / f) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in arrays.values())
+        assert sum(a.nbytes for a in arrays.values()) <= 64 * 10 ** 6
+        assert abs(float(arrays["loss"]) - out["final_loss"]) <= 1e-6 * abs(out["final_loss"])
+        runs.append(arrays)
+    for k in ("dry", "wet", "mod"):                     # the inputs of the last timed step
+        assert np.array_equal(runs[0][k], runs[1][k]), k
 
 
 @pytest.mark.parametrize("mode", ["lfo", "tbptt"])
