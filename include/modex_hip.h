@@ -129,7 +129,8 @@ int mx_phaser_fwd_probe(const float *x, int64_t x_stride, const float *rate, con
  * fb (n_fft/2+1, n_mels) row-major; band_lo/band_hi (n_mels,) int32 non-zero row range per mel band.
  * out (planes, n_mels, out_pitch) = log(clip(mel, eps)); out_pitch >= n_frames (352 for 345);
  * columns >= n_frames are zero.  SpecAugment: mel rows [f0,f1) and frames [t0,t1) are set to 0
- * before clip/log (0,0 = no mask). */
+ * before clip/log (0,0 = no mask).  hop <= 0, n_frames < 0 or n_frames > N/hop + 1 (frames beyond the padded clip):
+ * MX_ERR_ARG, before any launch. */
 int mx_logmel_fwd(const float *x, int64_t planes, int64_t N, const float *window, const float *twiddle,
                   const float *fb, const int32_t *band_lo, const int32_t *band_hi, int64_t n_fft,
                   int64_t hop, int64_t n_mels, int64_t n_frames, int64_t out_pitch, float eps, int32_t f0,
