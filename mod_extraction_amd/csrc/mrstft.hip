@@ -14,7 +14,7 @@
 //   alpha_r g1_r + g2_r:  nothing per bin is written to memory (the two-pass version parked 12 B per bin and re-read
 //   them once the norms were known: 25 GB per 256 x 4 s step, 46x the algorithmic bytes).
 //   onepass : a STREAM (64 lanes; 32 for N = 512, two streams per wavefront) walks a RUN of F consecutive frames of one
-//             clip, two frames at a time: forward FFT of x + i*y per frame (register-staged radix-4 Stockham, see below)
+//             clip, two frames at a time: forward FFT of x + i*s*y per frame (register-staged radix-4 Stockham, see below)
 //             -> both spectra by Hermitian separation -> loss sums and the frame's G1, G2; the pair's G1 spectra are
 //             completed to Hermitian ones and go through ONE inverse FFT as G1~_a + i G1~_b (real / imaginary part = the
 //             two frames' time-domain gradients), likewise G2: two transforms per frame (it was 1.5, plus 24 B per bin
@@ -25,6 +25,11 @@
 //   fold    : dx[n] = sum_r sum_{padded positions p of n} ( alpha_r g1_r[p] + g2_r[p] ),  g[p] = run sums + the tails of the
 //             (<= 2) earlier runs that reach p -- a gather: deterministic, no atomics
 // Value only (dx == NULL): pass A (mr_stats_kernel) + finish.
+// Packing (both forward kernels): the Hermitian split leaves an error of about u ||louder windowed frame|| on BOTH spectra, so
+// each frame's target is scaled by s = 2^k, k = round(log2(||x_w|| / ||y_w||)) clamped to +-60 (0 for an all-zero frame and
+// for |k| < 2), to the prediction's level before packing, and |Y|^2 = |D|^2 s^-2 exactly (pack_gain).  The gradient transforms
+// carry X only.
+// Frames whose windowed x and y are bit-identical or bit-negated take |Y| := |X| (frame_same, on the unscaled frames).
 // Measured per 256 clips x 4 s (all three resolutions, value + gradient): 19.2 ms (frame spread over 256 threads, an LDS
 // round trip and a __syncthreads per pass, twiddles from global memory) -> 14.9 (twiddles staged in LDS) -> 11.4 ms (one frame
 // per wavefront) -> 7.0 ms (parked bins, paired inverse, hardware transcendentals, LDS spans) -> this file.
@@ -129,6 +134,83 @@ __device__ __forceinline__ void split_bins(const cf *Z, int k, cf &X, cf &Y)
     Y = {0.5f * (z.y + zc.y), -0.5f * (z.x - zc.x)};
 }
 
+// sum over the L lanes of a frame (the whole wave; a half for 512), the same value on every lane of the frame: within each row
+// of 16 lanes by DPP (lane xor 1, xor 2, mirror within 8, mirror within 16 -- each step adds two operands that the partner lane
+// adds in the other order), then the row sums by v_readlane (no LDS round trip on the path into the transform)
+template <int L>
+__device__ __forceinline__ float frame_sum(float v)
+{
+    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xF, 0xF, false));     // quad_perm [1,0,3,2]
+    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xF, 0xF, false));     // quad_perm [2,3,0,1]
+    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x141, 0xF, 0xF, false));    // row_half_mirror
+    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x140, 0xF, 0xF, false));    // row_mirror
+    const float r0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 0));
+    const float r1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 16));
+    const float r2 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 32));
+    const float r3 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 48));
+    if (L == 64) return (r0 + r1) + (r2 + r3);
+    return (threadIdx.x & 32) ? r2 + r3 : r0 + r1;
+}
+
+// (sum x_w^2, sum y_w^2) of the lane's frame, on every lane of the frame
+template <int N>
+__device__ __forceinline__ cf frame_energy(const cf (&R)[WF<N>::NB][4])
+{
+    cf e = {0.0f, 0.0f};
+#pragma unroll
+    for (int bq = 0; bq < WF<N>::NB; ++bq)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) asm("v_pk_fma_f32 %0, %1, %1, %0" : "+v"(e) : "v"(R[bq][c]));
+    return {frame_sum<WF<N>::L>(e.x), frame_sum<WF<N>::L>(e.y)};
+}
+
+// A frame whose windowed signals are bit-identical (x == y) or bit-negated (x == -y) has |X| == |Y| bin for bin in the
+// reference (the transform of -y is the negated transform of y): keep that exact (loss 0, gradient 0), where the packed
+// transform's split would leave |X| != |Y| at rounding level.  Taken on the UNSCALED windowed frame (before pack_gain).  Such a
+// frame has e.x == e.y exactly (the same squares summed in the same order), so the element-wise test runs only then.
+template <int N>
+__device__ __forceinline__ bool frame_same(const cf (&R)[WF<N>::NB][4], int g, cf e)
+{
+    const bool level = e.x == e.y;                            // the same on every lane of the frame
+    if (__ballot(level) == 0ull) return false;
+    bool eq = true, neg = true;
+#pragma unroll
+    for (int bq = 0; bq < WF<N>::NB; ++bq)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            eq = eq && R[bq][c].x == R[bq][c].y;
+            neg = neg && R[bq][c].x == -R[bq][c].y;
+        }
+    const unsigned long long me = __ballot(eq), mn = __ballot(neg);
+    if (WF<N>::L == 64) return level && (me == ~0ull || mn == ~0ull);
+    const unsigned long long h = 0xffffffffull << (32 * g);
+    return level && ((me & h) == h || (mn & h) == h);
+}
+
+// Level equalisation of the packed pair.  Separating the two spectra from ONE transform of x + i y leaves an error of about
+// u ||louder windowed frame|| on BOTH spectra, which on the quieter signal's bins can be large relative to the bins (and the
+// log term and its 1 / |X| gradient amplify it).  So the target frame is packed as s y, s = 2^k, k = round(log2(||x_w|| /
+// ||y_w||)) clamped to [-60, 60] (0 when |k| < 2, when either frame is all zeros, or for a `same` frame): both halves carry the same
+// level and each spectrum gets the error of its own transform.  A power of two scales exactly, so |Y|^2 = |D|^2 s^-2 with
+// nothing lost; the return value is s^-2.  e: frame_energy of the unscaled frame.
+template <int N>
+__device__ __forceinline__ float pack_gain(cf (&R)[WF<N>::NB][4], bool same, cf e)
+{
+    const float ex = e.x, ey = e.y;
+    float kf = 0.5f * (__builtin_amdgcn_logf(ex) - __builtin_amdgcn_logf(ey));
+    kf = fminf(fmaxf(rintf(kf), -60.0f), 60.0f);              // (fmaxf drops a NaN of inf - inf)
+    // k = +-1 is left at 0: a level difference below ~2.8x costs the quieter spectrum at most that factor, and frames at
+    // comparable levels (a prediction close to its target) keep the arithmetic, and the rounding, of the unscaled pack
+    const int k = (same || !(ex > 0.0f) || !(ey > 0.0f) || fabsf(kf) < 2.0f) ? 0 : (int)kf;
+    if (k == 0) return 1.0f;
+    const float s = ldexpf(1.0f, k);
+#pragma unroll
+    for (int bq = 0; bq < WF<N>::NB; ++bq)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) R[bq][c].y *= s;
+    return ldexpf(1.0f, -2 * k);
+}
+
 // the lane's frame slot of iteration `it`: frame index within the workgroup's MR_FPG frames
 template <int N> __device__ __forceinline__ int frame_slot(int it, int wave, int g)
 {
@@ -170,14 +252,9 @@ __global__ __launch_bounds__(WF<N>::WAVES * 64) __attribute__((amdgpu_waves_per_
             if (interior) load_frame<N, true>(R, xb, yb, win, f, hop, T, a);
             else load_frame<N, false>(R, xb, yb, win, live ? f : n_frames - 1, hop, T, a);
         }
-        // a frame whose windowed signals are bit-identical has identical spectra in the reference: keep that exact
-        bool same_lane = true;
-#pragma unroll
-        for (int bq = 0; bq < WF<N>::NB; ++bq)
-#pragma unroll
-            for (int c = 0; c < 4; ++c) same_lane = same_lane && R[bq][c].x == R[bq][c].y;
-        const unsigned long long same_mask = __ballot(same_lane);
-        const bool same = L == 64 ? same_mask == ~0ull : ((same_mask >> (32 * g)) & 0xffffffffull) == 0xffffffffull;
+        const cf e = frame_energy<N>(R);
+        const bool same = frame_same<N>(R, g, e);
+        const float sinv2 = pack_gain<N>(R, same, e);
         wave_fft<N, false>(R, Z, fl);
 #pragma unroll
         for (int i = 0; i < E; ++i) buf[pos_final<N>(i, a)] = Z[i];
@@ -190,8 +267,8 @@ __global__ __launch_bounds__(WF<N>::WAVES * 64) __attribute__((amdgpu_waves_per_
             auto bin = [&](int k) {
                 cf X, Y;
                 split_bins<N>(buf, k, X, Y);
-                if (same) Y = X;
-                const float cx = fmaxf(X.x * X.x + X.y * X.y, eps), cy = fmaxf(Y.x * Y.x + Y.y * Y.y, eps);
+                const float px = X.x * X.x + X.y * X.y;
+                const float cx = fmaxf(px, eps), cy = fmaxf(same ? px : (Y.x * Y.x + Y.y * Y.y) * sinv2, eps);
                 const float d = __builtin_amdgcn_sqrtf(cy) - __builtin_amdgcn_sqrtf(cx);
                 fd += d * d;
                 fy += cy;
@@ -269,10 +346,12 @@ __device__ __forceinline__ cf mirror_h(cf ga, cf gb)        // conj(ga) + i conj
     return r;
 }
 struct BinOut { float s1, s2; };
-__device__ __forceinline__ BinOut bin_terms(const cf &X2, const cf &D, bool same, float eps4, float c_log, float &fd, float &fy, float &fl)
+// D comes from the level-equalised pack (pack_gain): |D|^2 sinv2 is the target's, exactly.
+__device__ __forceinline__ BinOut bin_terms(const cf &X2, const cf &D, bool same, float sinv2, float eps4, float c_log, float &fd,
+                                            float &fy, float &fl)
 {
     const float px = __builtin_fmaf(X2.x, X2.x, X2.y * X2.y);
-    const float py = same ? px : __builtin_fmaf(D.x, D.x, D.y * D.y);
+    const float py = same ? px : __builtin_fmaf(D.x, D.x, D.y * D.y) * sinv2;
     const float cx = fmaxf(px, eps4), cy = fmaxf(py, eps4);
     const float xm = __builtin_amdgcn_sqrtf(cx), ym = __builtin_amdgcn_sqrtf(cy);
     const float d = xm - ym;
@@ -427,13 +506,9 @@ __global__ __launch_bounds__(MR_OPW * 64) __attribute__((amdgpu_waves_per_eu(N =
                 if (__ballot(!inter_lane) == 0ull) load_frame_w<N, true>(R, xb, yb, wv, fl_, hop, T, a);
                 else load_frame_w<N, false>(R, xb, yb, wv, fl_, hop, T, a);
             }
-            bool same_lane = true;
-#pragma unroll
-            for (int bq = 0; bq < NB; ++bq)
-#pragma unroll
-                for (int c = 0; c < 4; ++c) same_lane = same_lane && R[bq][c].x == R[bq][c].y;
-            const unsigned long long same_mask = __ballot(same_lane);
-            const bool same = L == 64 ? same_mask == ~0ull : ((same_mask >> (32 * g)) & 0xffffffffull) == 0xffffffffull;
+            const cf e = frame_energy<N>(R);
+            const bool same = frame_same<N>(R, g, e);
+            const float sinv2 = pack_gain<N>(R, same, e);
             wave_fft<N, false>(R, Z, fl);
 #pragma unroll
             for (int i = 0; i < E; ++i) buf[pos_final<N>(i, a)] = Z[i];
@@ -445,7 +520,7 @@ __global__ __launch_bounds__(MR_OPW * 64) __attribute__((amdgpu_waves_per_eu(N =
                 const int k = a + L * j;
                 const cf z = buf[k], zc = buf[(N - k) & (N - 1)];
                 const cf X2 = add_conj(z, zc), D = sub_conj(z, zc);
-                const BinOut t = bin_terms(X2, D, same, 4.0f * eps, c_log, fd, fy, fl);
+                const BinOut t = bin_terms(X2, D, same, sinv2, 4.0f * eps, c_log, fd, fy, fl);
                 const bool dc = (j == 0) && (a == 0);                          // DC: real, not halved
                 const float s1 = (dc ? 2.0f * lm : lm) * t.s1, s2 = (dc ? 2.0f * lm : lm) * t.s2;
                 const cf g1 = X2 * s1, g2 = X2 * s2;
@@ -464,7 +539,7 @@ __global__ __launch_bounds__(MR_OPW * 64) __attribute__((amdgpu_waves_per_eu(N =
             if (a == 0) {                                                       // Nyquist bin: real, not halved
                 const cf z = buf[N / 2];
                 const cf X2 = {2.0f * z.x, 0.0f}, D = {0.0f, 2.0f * z.y};
-                const BinOut t = bin_terms(X2, D, same, 4.0f * eps, c_log, fd, fy, fl);
+                const BinOut t = bin_terms(X2, D, same, sinv2, 4.0f * eps, c_log, fd, fy, fl);
                 const float n1 = 2.0f * lm * t.s1 * X2.x, n2 = 2.0f * lm * t.s2 * X2.x;
                 if (u == 0) { ny1a = n1; ny2a = n2; }
                 else { buf[N / 2] = {ny1a, n1}; h2ny_re = ny2a; h2ny_im = n2; }

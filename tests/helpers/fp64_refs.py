@@ -1,4 +1,4 @@
-"""Independent fp64 references for the mel front end and the phaser (TEST INFRASTRUCTURE ONLY).
+"""Independent fp64 references for the mel front end, the phaser and the MR-STFT loss (TEST INFRASTRUCTURE ONLY).
 
 Everything here is written from the definitions of the operations, not from the product or the oracle: this module
 imports numpy, scipy and math only (tests/test_fp64_refs.py checks that), so a formula shared by the product and the
@@ -8,6 +8,10 @@ oracle cannot hide in both sides of a comparison.
 * ``logmel64``      centre/reflect pad -> periodic Hann -> rfft -> |X|^2 -> @ fb -> masks -> clip -> log.
                     ``dtype=numpy.float32`` runs the same pipeline in fp32 (scipy.fft): the yardstick of how large a
                     plain fp32 evaluation's error is.
+* ``mrstft64``      the multi-resolution STFT loss (auraloss definition: spectral convergence + log-magnitude L1, mean over
+                    resolutions), its per-resolution terms, and d total / d x by the explicit adjoint (inverse transform
+                    of the per-bin gradient, window, overlap-add, reflect fold) -- no autograd.  ``dtype=numpy.float32``
+                    runs it on SEPARATE complex64 transforms: the fp32 yardstick.
 * ``phaser_ir64``   the phaser at depth 0 (a constant cut-off, so an LTI system) as a closed-form transfer function,
                     turned into an impulse response on an M-point frequency grid.
 """
@@ -121,3 +125,79 @@ def phaser_ir64(centre: float, feedback: float, mix: float, sr: float, M: int = 
     z = np.exp(2j * math.pi * np.arange(M // 2 + 1) / M)
     h = np.fft.irfft(phaser_response(centre, feedback, mix, sr, z), n=M)
     return h, float(np.abs(h[-(M // 8):]).max())
+
+
+# ---- multi-resolution STFT loss ----------------------------------------------------------------------------------------
+def mr_window(n_fft: int, win_length: int, dtype=np.float64) -> np.ndarray:
+    """The periodic Hann window of win_length placed in an n_fft frame at offset (n_fft - win_length) // 2, zeros around."""
+    w = np.zeros(n_fft, dtype=np.float64)
+    left = (n_fft - win_length) // 2
+    w[left:left + win_length] = hann_periodic(win_length)
+    return w.astype(dtype)
+
+
+def stft(x, n_fft: int, hop: int, win_length: int, dtype=np.float64) -> np.ndarray:
+    """(..., N) -> (..., 1 + N // hop, n_fft/2 + 1) complex: rfft of every centre / reflect-padded frame times mr_window.
+    dtype float32: scipy.fft on float32 frames (complex64 out)."""
+    x = np.asarray(x).astype(dtype)
+    fr = frames_reflect(x, n_fft, hop, x.shape[-1] // hop + 1) * mr_window(n_fft, win_length, dtype)
+    return np.fft.rfft(fr, axis=-1) if dtype == np.float64 else scipy.fft.rfft(fr, axis=-1)
+
+
+def mrstft64(x, y, fft_sizes, hops, win_lengths, eps=1e-8, w_sc=1.0, w_log=1.0, dtype=np.float64):
+    """x (prediction), y (target): (..., N).  Returns (total, [(sc_r, logmag_r) per resolution], d total / d x).
+
+    Per resolution: mag = sqrt(max(|X|^2, eps)) over every bin of every frame of the whole batch,
+    sc = ||Ym - Xm||_F / ||Ym||_F, logmag = mean |log Xm - log Ym|;  total = mean_r (w_sc sc_r + w_log logmag_r).
+    Gradient: per bin G = dL/d|X| * X / |X| (0 where |X|^2 <= eps; sign(0) = 0; the sc part 0 when ||Ym - Xm|| = 0), per
+    frame n_fft * Re(ifft(G zero-extended to n_fft bins)) times the window, overlap-added into the padded signal, whose
+    reflect padding is then folded back onto the clip.  X and Y come from separate transforms in either dtype."""
+    x = np.asarray(x).astype(dtype)
+    y = np.asarray(y).astype(dtype)
+    assert x.shape == y.shape
+    shape, N = x.shape, x.shape[-1]
+    x, y = x.reshape(-1, N), y.reshape(-1, N)
+    B = x.shape[0]
+    n_res = len(fft_sizes)
+    eps_t = dtype(eps)
+    total = dtype(0.0)
+    terms = []
+    dx = np.zeros((B, N), dtype=dtype)
+    for n_fft, hop, wl in zip(fft_sizes, hops, win_lengths):
+        half = n_fft // 2
+        n_frames = N // hop + 1
+        X = stft(x, n_fft, hop, wl, dtype)
+        Y = stft(y, n_fft, hop, wl, dtype)
+        px = X.real * X.real + X.imag * X.imag
+        py = Y.real * Y.real + Y.imag * Y.imag
+        xm = np.sqrt(np.maximum(px, eps_t))
+        ym = np.sqrt(np.maximum(py, eps_t))
+        nd = np.sqrt(np.sum((ym - xm) ** 2))
+        ny = np.sqrt(np.sum(ym ** 2))
+        sc = nd / ny
+        ld = np.log(xm) - np.log(ym)
+        lm = np.mean(np.abs(ld))
+        terms.append((sc, lm))
+        total = total + dtype(w_sc) * sc + dtype(w_log) * lm
+        # d total / d |X| per bin, then G = that * X / |X| on the bins above the floor
+        alpha = dtype(w_sc) / (dtype(n_res) * nd * ny) if nd > 0 else dtype(0.0)
+        c_log = dtype(w_log) / (dtype(n_res) * dtype(ld.size))
+        dm = alpha * (xm - ym) + c_log * np.sign(ld) / xm
+        G = np.where(px > eps_t, dm / xm, dtype(0.0)) * X
+        Gext = np.zeros(G.shape[:-1] + (n_fft,), dtype=G.dtype)
+        Gext[..., :half + 1] = G
+        ifft = np.fft.ifft if dtype == np.float64 else scipy.fft.ifft
+        gf = dtype(n_fft) * ifft(Gext, axis=-1).real.astype(dtype) * mr_window(n_fft, wl, dtype)    # (B, frames, n_fft)
+        # overlap-add into the padded signal (padded position p = sample p - n_fft/2)
+        P = (n_frames - 1) * hop + n_fft
+        pos = (np.arange(n_frames)[:, None] * hop + np.arange(n_fft)[None, :]).ravel()
+        rows = np.arange(B)[:, None] * P
+        padded = np.bincount((rows + pos[None, :]).ravel(), weights=gf.reshape(B, -1).ravel().astype(np.float64),
+                             minlength=B * P).astype(dtype).reshape(B, P)
+        # fold the reflect padding back: padded position p holds sample reflect(p - n_fft/2)
+        s = np.arange(P) - half
+        s = np.where(s < 0, -s, s)
+        s = np.where(s >= N, 2 * (N - 1) - s, s)
+        dx += np.bincount((np.arange(B)[:, None] * N + s[None, :]).ravel(), weights=padded.ravel().astype(np.float64),
+                          minlength=B * N).astype(dtype).reshape(B, N)
+    return total / dtype(n_res), terms, dx.reshape(shape)

@@ -8,6 +8,9 @@ values, and the product's filter bank / the C phaser oracle checked against them
   partition of unity within 1e-6 between the first and the last band centre, the same empty bands
 * the phaser's closed form: |A| = 1 on the unit circle, H(1) and H(-1) from the loop gain, a negligible tail
 * orc_phaser (the arbiter of every other phaser test) at depth 0 against the closed form's impulse response
+* mrstft64: its magnitudes against torch.stft in fp64 (centred short windows included), its value against the fp64
+  evaluation of oracle/losses.py, its adjoint gradient against central finite differences, and the closed forms of
+  x = a y and x = -y
 """
 import ast
 import itertools
@@ -144,3 +147,113 @@ def test_orc_phaser_depth0_against_closed_form(sr):
         S = float(np.abs(fftconvolve(x.astype(np.float64), h2[:N])[:N] - y64).max())
         err = float(np.abs(y - y64).max())
         assert err <= 2e-6 + 1.5 * S, (centre, fbk, mix, err, S)
+
+
+# ---- MR-STFT loss -------------------------------------------------------------------------------------------------------
+MR_DEFAULT = ((1024, 2048, 512), (120, 240, 50), (600, 1200, 240))
+
+
+@pytest.mark.parametrize("n_fft,hop,win", [(1024, 120, 600), (2048, 240, 1200), (512, 50, 240), (512, 64, 301),
+                                           (1024, 100, 1023)])
+def test_mr_stft_magnitudes_match_torch_stft_fp64(n_fft, hop, win):
+    """(512, 301) and (1024, 1023): windows shorter than n_fft by an odd amount (torch centres them at (n - win) // 2)."""
+    g = np.random.default_rng(n_fft + win)
+    x = g.uniform(-1, 1, (2, 5000))
+    S = torch.stft(torch.from_numpy(x), n_fft, hop, win, torch.hann_window(win, dtype=torch.float64), center=True,
+                   pad_mode="reflect", return_complex=True).transpose(-1, -2).numpy()
+    X = R.stft(x, n_fft, hop, win)
+    assert X.shape == S.shape
+    assert float(np.abs(np.abs(X) - np.abs(S)).max() / np.abs(S).max()) <= 1e-12
+    assert float(np.abs(X - S).max() / np.abs(S).max()) <= 1e-12
+
+
+def _mr64(*cfg):
+    """oracle/losses.py evaluated in fp64 (its fp32 window table replaced by torch's fp64 one)."""
+    from oracle import losses as olosses
+
+    class MR64(olosses.MultiResolutionSTFTLoss):
+        def _mag(self, v, n_fft, hop, win):
+            s = torch.stft(v.reshape(-1, v.size(-1)), n_fft, hop, win, torch.hann_window(win, dtype=torch.float64),
+                           return_complex=True)
+            return torch.sqrt(torch.clamp(s.real ** 2 + s.imag ** 2, min=self.eps))
+    return MR64(*cfg)
+
+
+@pytest.mark.parametrize("cfg", [MR_DEFAULT, ((512, 1024), (64, 100), (301, 1024))])
+def test_mrstft64_value_matches_oracle_fp64(cfg):
+    g = np.random.default_rng(7)
+    y = g.uniform(-0.5, 0.5, (3, 7000))
+    x = 0.7 * y + 0.2 * np.roll(y, 5, -1) + 0.05 * g.standard_normal(y.shape)
+    x[1] *= 1e-3                                                  # a level mismatch: bins on both sides of the floor
+    tot, terms, _ = R.mrstft64(x, y, *cfg)
+    want = float(_mr64(*cfg)(torch.from_numpy(x), torch.from_numpy(y)))
+    assert len(terms) == len(cfg[0])
+    assert abs(float(tot) - want) <= 1e-12 * abs(want)
+    assert abs(float(np.mean([sc + lm for sc, lm in terms])) - want) <= 1e-12 * abs(want)
+
+
+def test_mrstft64_gradient_matches_central_differences():
+    """40 sample positions: both reflect folds (the first and last n_fft/2 samples), around multiples of 32 hop (the
+    kernel's runs of 32 frames) for each resolution, interior ones.  Step 1e-6 (measured 1.0e-7 of the largest tested
+    gradient; 1e-5 and 1e-4 are worse: the curvature of the log term near weak bins).  The loss has kinks where a bin's
+    |X| crosses |Y| (sign of the log term): T - 1024 of row 1 lies within 1e-6 of one and is not used."""
+    T = 8000
+    g = np.random.default_rng(3)
+    y = g.uniform(-0.5, 0.5, (2, T))
+    x = 0.7 * y + 0.2 * np.roll(y, 5, -1) + 0.05 * g.standard_normal((2, T))
+    x[0, 2000:5000] *= 0.05
+    for w_sc, w_log in ((1.0, 1.0), (0.3, 0.0), (0.0, 2.0)):
+        _, _, dx = R.mrstft64(x, y, *MR_DEFAULT, w_sc=w_sc, w_log=w_log)
+        pos = [(1, p) for p in (0, 1, 2, 7, 255, 511, 1023, T - 1, T - 2, T - 3, T - 256, T - 1000)]
+        pos += [(r, p) for r, q in ((0, 32 * 50), (1, 64 * 50), (0, 96 * 50), (1, 128 * 50), (1, 32 * 120),
+                                    (0, 64 * 120), (1, 32 * 240)) for p in (q - 1, q, q + 1)]
+        pos += [(0, 2000), (0, 4999), (0, 3333), (1, 1234), (1, 4321), (0, 6789), (1, 2500)]
+        assert len(pos) == 40
+        h = 1e-6
+        err = 0.0
+        for r, p in pos:
+            xp, xm = x.copy(), x.copy()
+            xp[r, p] += h
+            xm[r, p] -= h
+            fd = (R.mrstft64(xp, y, *MR_DEFAULT, w_sc=w_sc, w_log=w_log)[0]
+                  - R.mrstft64(xm, y, *MR_DEFAULT, w_sc=w_sc, w_log=w_log)[0]) / (2 * h)
+            err = max(err, abs(fd - dx[r, p]))
+        scale = max(abs(dx[r, p]) for r, p in pos)
+        assert scale > 0
+        assert err / scale <= 1e-6, (w_sc, w_log, err / scale)
+
+
+@pytest.mark.parametrize("a", [0.5, 1.7, 0.1, 8.0])
+def test_mrstft64_closed_form_scaled_and_negated(a):
+    """x = a y with every bin of both above the floor: sc_r = |1 - a|, logmag_r = |ln a| exactly (to 1e-12).  x = -y:
+    |X| = |Y| bit for bit (the transform of -y is the negated transform of y), so the loss and the gradient are exactly 0."""
+    g = np.random.default_rng(11)
+    T = 6000
+    n = np.arange(T)
+    y = 0.3 * np.sin(2 * math.pi * 0.01 * n)[None, :] + g.uniform(-0.3, 0.3, (2, T))
+    x = a * y
+    for (n_fft, hop, win) in zip(*MR_DEFAULT):
+        P = np.abs(R.stft(y, n_fft, hop, win)) ** 2
+        assert float(P.min()) * min(a, 1.0) ** 2 > 1e-8 * 1.01, (n_fft, float(P.min()))
+    tot, terms, dx = R.mrstft64(x, y, *MR_DEFAULT)
+    for sc, lm in terms:
+        assert abs(sc - abs(1 - a)) <= 1e-12 * max(abs(1 - a), 1.0)
+        assert abs(lm - abs(math.log(a))) <= 1e-12 * max(abs(math.log(a)), 1.0)
+    assert abs(tot - (abs(1 - a) + abs(math.log(a)))) <= 1e-12 * (abs(1 - a) + abs(math.log(a)))
+    tot, terms, dx = R.mrstft64(-y, y, *MR_DEFAULT)
+    assert tot == 0.0 and all(sc == 0.0 and lm == 0.0 for sc, lm in terms)
+    assert not np.any(dx)
+    tot, terms, dx = R.mrstft64(-y.astype(np.float32), y.astype(np.float32), *MR_DEFAULT, dtype=np.float32)
+    assert tot == 0.0 and not np.any(dx)
+
+
+def test_mrstft64_float32_yardstick():
+    """dtype float32: separate complex64 transforms, a plain fp32 evaluation close to fp64 at equal levels."""
+    g = np.random.default_rng(2)
+    y = g.uniform(-0.5, 0.5, (2, 8000))
+    x = 0.8 * y + 0.05 * g.standard_normal(y.shape)
+    t64, terms64, d64 = R.mrstft64(x, y, *MR_DEFAULT)
+    t32, terms32, d32 = R.mrstft64(x.astype(np.float32), y.astype(np.float32), *MR_DEFAULT, dtype=np.float32)
+    assert d32.dtype == np.float32 and isinstance(t32, np.float32)
+    assert abs(float(t32) - t64) <= 1e-5 * t64
+    assert float(np.abs(d32 - d64).max() / np.abs(d64).max()) <= 2e-3
