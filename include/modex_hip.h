@@ -527,6 +527,25 @@ int mx_mrstft_loss(const float *y_hat, int64_t y_hat_stride, const float *y, int
                    double *part, float *coef, float *scratch, float *terms, float *dx, int64_t dx_stride,
                    void *stream);
 
+/* ---- K13: log-mel L1 loss -- mod_extraction/losses.py:105-130 (LogMelLoss: torchaudio MelSpectrogram with centre / reflect
+ * padding of n_fft/2, periodic hann, power 2, HTK filter bank, no norm):
+ * value = scale * mean |log max(mel(y_hat), eps) - log max(mel(y), eps)| over B x n_mels x frames, frames = 1 + T/hop, and
+ * dx (+)= d value / d y_hat (torch's conventions: sgn(0) = 0, the clamp passes the gradient where mel >= eps).
+ * y_hat, y: B rows of T samples (row strides); window (n_fft,); twiddle (n_fft, 2) = exp(-2 pi i m / n_fft);
+ * fb (n_fft/2+1, n_mels) row-major; band_lo / band_hi (n_mels,) int32 non-zero row range of each band (mx_logmel_fwd's tables).
+ * n_fft in {512, 1024, 2048} (else MX_ERR_UNSUPPORTED); any hop > 0; n_mels <= 2048 within the LDS budget (else
+ * MX_ERR_UNSUPPORTED); eps > 0; T <= n_fft/2 (the reflect padding needs more samples): MX_ERR_ARG, before any launch.
+ * value: one device float (written, never accumulated).  dx (B rows, stride dx_stride) or NULL (value only: no inverse
+ * transforms); accumulate != 0 adds the scaled gradient onto what dx holds.  Workspaces (device): part >= B * ceil(frames / 32)
+ * doubles (per-workgroup partial sums); scratch (only when dx != NULL) >= B * (frames * hop + runs * max(n_fft - hop, 0))
+ * floats with runs = ceil(frames / F), F = max(32, ceil(n_fft / hop)) rounded up to even: the time-domain gradient as
+ * per-run overlap-add sums plus one tail per run; nothing per bin is stored.  Deterministic: no float atomics. */
+int mx_logmel_l1_loss(const float *y_hat, int64_t y_hat_stride, const float *y, int64_t y_stride, int64_t B, int64_t T,
+                      const float *window, const float *twiddle, const float *fb, const int32_t *band_lo,
+                      const int32_t *band_hi, int64_t n_fft, int64_t hop, int64_t n_mels, float eps, float scale,
+                      int32_t accumulate, double *part, float *scratch, float *value, float *dx, int64_t dx_stride,
+                      void *stream);
+
 /* ---- K12: AdamW -- torch.optim.AdamW (configs/opt/adam_w.yml), flat fp32 buffers of n elements;
  * step = 1-based step index; grad_scale multiplies the gradient first (1/world after a sum
  * all-reduce). */

@@ -415,7 +415,7 @@ class TBPTTLFOEffectModeling(BaseLightingModule):
                     if self._fused_l1:
                         dlat = em.bptt_chunk_dlfo(x, lat, y, stash, h0, c0, lstm_grad, wet=tgt, loss_scale=w_l1 / (B * S))
                     else:
-                        dy = effect_loss_grad(y, tgt, self.loss_dict, mrstft=self._loss_module("mrstft") if "mrstft" in self.loss_dict else None)
+                        dy = effect_loss_grad(y, tgt, self.loss_dict, **self._grad_modules())
                         dlat = em.bptt_chunk_dlfo(x, lat, y, stash, h0, c0, lstm_grad, dy=dy)
                     d_hs = linear_interpolate_last_dim_bwd(dlat[:, 0, :], n_f, n, start)
                     if self.should_stretch:
@@ -439,7 +439,7 @@ class TBPTTLFOEffectModeling(BaseLightingModule):
                     if self._fused_l1:
                         em.bptt_l1_chunk(x, lat, y, tgt, stash, h0, c0, w_l1 / (B * S), optimizer.flat_grad)
                     else:       # lightning.py:380-382 with any loss_dict: d loss / d y from the loss kernels, then BPTT
-                        dy = effect_loss_grad(y, tgt, self.loss_dict, mrstft=self._loss_module("mrstft") if "mrstft" in self.loss_dict else None)
+                        dy = effect_loss_grad(y, tgt, self.loss_dict, **self._grad_modules())
                         em.bptt_chunk(x, lat, y, dy, stash, h0, c0, optimizer.flat_grad)
                     optimizer.step(grad_scale=allreduce_flat_grad(optimizer.flat_grad, world_size))
                     em.detach_hidden()
@@ -501,8 +501,7 @@ class TBPTTLFOEffectModeling(BaseLightingModule):
             p = self.param_model(wet).unsqueeze(-1) if self.param_model is not None else None       # lightning.py:371-373
             y = em(x, self._with_params(lat_lfo, p))
         tgt = tgt.expand_as(y) if tgt.shape != y.shape else tgt
-        dy = effect_loss_grad(_channel_rows(y.detach()), _channel_rows(tgt), self.loss_dict,
-                              mrstft=self._loss_module("mrstft") if "mrstft" in self.loss_dict else None)
+        dy = effect_loss_grad(_channel_rows(y.detach()), _channel_rows(tgt), self.loss_dict, **self._grad_modules())
         y.backward(dy.view_as(y))
         if hat is not None:
             d_hs = linear_interpolate_last_dim_bwd(lat_lfo.grad[:, 0, :].contiguous(), hst.size(-1), n, start)
@@ -523,6 +522,11 @@ class TBPTTLFOEffectModeling(BaseLightingModule):
             if name == "mrstft":
                 self._mrstft = mod
         return mod
+
+    def _grad_modules(self):
+        """The loss modules ``effect_loss_grad`` reuses (their device tables are built once; the same objects log the terms)."""
+        return {"mrstft": self._loss_module("mrstft") if "mrstft" in self.loss_dict else None,
+                "logmel": self._loss_module("log_mel_l1") if "log_mel_l1" in self.loss_dict else None}
 
     def training_step(self, batch, batch_idx: int = 0, optimizer=None, world_size: int = 1, prep=None):
         assert optimizer is not None, "manual optimisation: pass the FlatAdamW optimizer"

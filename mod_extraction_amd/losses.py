@@ -5,7 +5,7 @@ call signature; l1 / fdl1 / sdl1 / mse -- the LFO-extraction losses -- are evalu
 ``mx_lfo_loss`` HIP kernel (all four terms and d/d(y_hat) in one launch).  ``lfo_loss`` is the fused
 weighted form that ``lightning.LFOExtraction`` uses (lightning.py:33-62).
 """
-from typing import Dict, Tuple
+from typing import Dict, Optional, Tuple
 
 import torch
 from torch import Tensor as T, nn
@@ -87,30 +87,71 @@ class MSELoss(_SingleTerm):
     term = "mse"
 
 
+def logmel_scratch_floats(B: int, Tn: int, n_fft: int, hop: int) -> int:
+    """Workspace floats of ``mx_logmel_l1_loss`` for the gradient (include/modex_hip.h): per clip frames * hop run sums plus
+    one tail of n_fft - hop positions per run of F frames."""
+    frames = 1 + Tn // hop
+    run = max(32, -(-n_fft // hop))
+    run += run & 1
+    runs = -(-frames // run)
+    return B * (frames * hop + runs * max(n_fft - hop, 0))
+
+
+def logmel_l1_value_and_grad(mod: "LogMelLoss", a: T, t: T, need_grad: bool = True, scale: float = 1.0,
+                             dx: Optional[T] = None, accumulate: bool = False) -> Tuple[T, Optional[T]]:
+    """a (prediction), t (target): (rows, T) with unit inner stride.  Returns (scale * loss as a device scalar,
+    d (scale * loss) / d a or None) from ONE ``mx_logmel_l1_loss`` call.  ``dx``: a (rows, T) float32 tensor with unit inner
+    stride to write the gradient into (``accumulate``: add it onto what ``dx`` holds) instead of a fresh one."""
+    assert a.shape == t.shape and a.ndim == 2 and a.stride(1) == 1 and t.stride(1) == 1
+    assert a.dtype == torch.float32 and t.dtype == torch.float32
+    B, Tn = a.shape
+    sp = mod.spectrogram
+    n_fft, hop = sp.n_fft, sp.hop_length
+    if Tn <= n_fft // 2:
+        raise ValueError(f"log_mel_l1: reflect padding needs more than n_fft/2 = {n_fft // 2} samples, got {Tn}")
+    dev = a.device
+    if sp.mel_scale.fb.device != dev:
+        sp.to(dev)
+    frames = 1 + Tn // hop
+    part = torch.empty(B * -(-frames // 32), device=dev, dtype=torch.float64)
+    value = torch.empty((), device=dev, dtype=torch.float32)
+    if need_grad:
+        if dx is None:
+            dx = torch.empty((B, Tn), device=dev, dtype=torch.float32)
+            accumulate = False
+        assert dx.shape == (B, Tn) and dx.stride(1) == 1 and dx.dtype == torch.float32
+        scratch = torch.empty(logmel_scratch_floats(B, Tn, n_fft, hop), device=dev, dtype=torch.float32)
+    else:
+        dx, scratch = None, None
+    lo, hi = sp.bands()
+    _hip.call("mx_logmel_l1_loss", a.data_ptr(), a.stride(0), t.data_ptr(), t.stride(0), B, Tn,
+              _hip.ptr(sp.spectrogram.window), _hip.ptr(sp.twiddle), _hip.ptr(sp.mel_scale.fb), _hip.ptr(lo), _hip.ptr(hi),
+              n_fft, hop, sp.n_mels, float(mod.eps), float(scale), int(bool(accumulate)), _hip.ptr(part), _hip.ptr(scratch),
+              _hip.ptr(value), None if dx is None else dx.data_ptr(), 0 if dx is None else dx.stride(0), _hip.stream())
+    return value, dx
+
+
 class LogMelLoss(nn.Module):
-    """losses.py:105-130 (``log_mel_l1``; no shipped config uses it): L1 between the log-mel spectrograms of input and
-    target on the K4 kernel.  A METRIC here: the log-mel kernel has no backward, so a prediction that requires grad
-    raises instead of silently returning a constant."""
+    """losses.py:105-130 (``log_mel_l1``): L1 between the log-mel spectrograms of input and target, evaluated by
+    ``mx_logmel_l1_loss`` in value-only mode (any clip length above n_fft/2; no spectrogram is materialised).  The
+    gradient reaches training through ``effect_losses.effect_loss_grad`` (``logmel_l1_value_and_grad``), not autograd:
+    a prediction that requires grad raises instead of silently returning a constant."""
 
     def __init__(self, sr: float = 44100, n_fft: int = 1024, hop_len: int = 256, n_mels: int = 256,
                  eps: float = 1e-7) -> None:
         super().__init__()
-        from .models import MelSpectrogramHIP, PITCH
-        self.eps, self.hop_len, self.pitch = eps, hop_len, PITCH
+        from .models import MelSpectrogramHIP
+        self.eps, self.hop_len = eps, hop_len
         self.spectrogram = MelSpectrogramHIP(int(sr), n_fft, hop_len, n_mels)
 
     def forward(self, input: T, target: T) -> T:
         if input.requires_grad and torch.is_grad_enabled():
             raise NotImplementedError("log_mel_l1 is forward-only on this path (evaluation metric)")
         assert input.shape == target.shape and input.ndim == 3
-        n_frames = input.size(-1) // self.hop_len + 1
-        if n_frames > self.pitch:
-            raise NotImplementedError(f"log_mel_l1: at most {self.pitch} frames per clip")
-        if self.spectrogram.mel_scale.fb.device != input.device:
-            self.spectrogram.to(input.device)
-        a = self.spectrogram.log_mel(input.detach(), n_frames, self.eps)[..., :n_frames]
-        b = self.spectrogram.log_mel(target.detach(), n_frames, self.eps)[..., :n_frames]
-        return (a - b).abs().mean()
+        n = input.size(-1)
+        a = input.detach().reshape(-1, n).contiguous().float()
+        t = target.detach().reshape(-1, n).contiguous().float()
+        return logmel_l1_value_and_grad(self, a, t, need_grad=False)[0]
 
 
 def apply_reduction(losses: T, reduction: str = "none") -> T:
