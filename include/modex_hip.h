@@ -91,6 +91,30 @@ int mx_flanger_fwd_probe(const float *x, int64_t x_stride, const float *mod, int
                    int32_t max_delay_max, const int32_t *rows, int64_t n_rows, int64_t B, int64_t N,
                    float *y, int64_t y_stride, float *mod_up, int64_t *dbg_prev, float *dbg_frac, void *stream);
 
+/* Forward of the flanger adjoint -- fx.py:72-119: mx_flanger_fwd (y bit-identical) that also writes the interpolated tap
+ * v[n] of fx.py:113 of every sample to stash (B,N), dense rows (row b at stash + b*N).  mod must be full rate: n_mod != N
+ * returns MX_ERR_UNSUPPORTED.  Other arguments, limits and the rows subset as mx_flanger_fwd. */
+int mx_flanger_fwd_stash(const float *x, int64_t x_stride, const float *mod, int64_t n_mod, const float *lfo_scale,
+                         const float *min_delay, const float *feedback, const float *depth,
+                         const float *mix, const float *one_minus_mix, const int32_t *max_delay,
+                         int32_t max_delay_max, const int32_t *rows, int64_t n_rows, int64_t B, int64_t N,
+                         float *y, int64_t y_stride, float *stash, void *stream);
+/* Adjoint of fx.py:72-119 (the reference's own autograd fails there: its loop writes into delay_buf after gather saved it).
+ * The derivative of the loop restated without in-place writes: floor / prev / next have zero derivative, the read
+ * fraction and % derivative 1, clip passes the gradient on [-1, 1] inclusive, never-written slots read 0.
+ * dy (B,N) row stride dy_stride; x as in the forward; mod (B,N) full rate and stash (B,N) from mx_flanger_fwd_stash, dense
+ * rows; per-clip constants, max_delay, max_delay_max, rows / n_rows as mx_flanger_fwd.  ws: (B,N) floats of workspace.
+ * Outputs, each optional (NULL skips it): dx, dmod (B,N) with row strides dx_stride / dmod_stride; per-clip fp64
+ * d_lfo_scale, d_min_delay, d_feedback, d_depth, d_mix (B,) (d_mix includes the one_minus_mix = 1 - mix path).
+ * Deterministic: no float atomics whose order depends on arrival; per-clip sums in fp64 in a fixed order. */
+int mx_flanger_bwd(const float *dy, int64_t dy_stride, const float *x, int64_t x_stride, const float *mod,
+                   const float *stash, const float *lfo_scale, const float *min_delay, const float *feedback,
+                   const float *depth, const float *mix, const float *one_minus_mix, const int32_t *max_delay,
+                   int32_t max_delay_max, const int32_t *rows, int64_t n_rows, int64_t B, int64_t N,
+                   float *ws, float *dx, int64_t dx_stride, float *dmod, int64_t dmod_stride,
+                   double *d_lfo_scale, double *d_min_delay, double *d_feedback, double *d_depth,
+                   double *d_mix, void *stream);
+
 /* Measurement aid (bench.py): `steps` dependent LDS round trips of the flanger lock-step's shape (two ds_read_b32 of the
  * slot the previous step wrote, the five fp32 operations of fx.py:113-115, one ds_write_b32) on one wavefront, nothing
  * else.  Its time per step x the lock-steps of a clip is a floor of mx_flanger_fwd that does not come from that kernel.

@@ -37,6 +37,10 @@ __device__ __forceinline__ unsigned lds_byte_addr(const float *p) {
     return (unsigned)(size_t)(__attribute__((address_space(3))) const float *)p;
 }
 
+// STASH (mx_flanger_fwd_stash, the forward of the adjoint in flanger_bwd.hip): also store every sample's interpolated tap
+// v[n] (fx.py:113) to stash (B,N), dense rows.  The waveform is the same instruction sequence; STASH = false is
+// mx_flanger_fwd.
+template <bool STASH>
 __global__ __launch_bounds__(FL_THREADS) void flanger_kernel(
     const float *__restrict__ x, long long x_stride, const float *__restrict__ mod, int n_mod, float mod_scale,
     const float *__restrict__ lfo_scale, const float *__restrict__ min_delay,
@@ -44,7 +48,7 @@ __global__ __launch_bounds__(FL_THREADS) void flanger_kernel(
     const float *__restrict__ mix, const float *__restrict__ one_minus_mix,
     const int *__restrict__ max_delay, const int *__restrict__ rows, int N, int lfo_off, int ring_off,
     float *__restrict__ y, long long y_stride, float *__restrict__ mod_up, long long *__restrict__ dbg_prev,
-    float *__restrict__ dbg_frac, int probe)
+    float *__restrict__ dbg_frac, int probe, float *__restrict__ stash)
 {
     extern __shared__ __attribute__((aligned(16))) float buf[];   // [M delay line | n_mod LFO row (when resampled in-kernel) | ring]
     const int lane = threadIdx.x & 63;
@@ -172,6 +176,7 @@ __global__ __launch_bounds__(FL_THREADS) void flanger_kernel(
                 a_prev_[j] = lds_byte_addr(buf + prev); a_next_[j] = lds_byte_addr(buf + next); a_w_[j] = lds_byte_addr(buf + w);
             }
             float o[FL_V];
+            float tap[FL_V];
 #pragma unroll
             for (int j = 0; j < FL_V; ++j) {
                 const float xs = rc[j].x, frac = rc[j].y, omf = rc[j].z;
@@ -236,6 +241,7 @@ __global__ __launch_bounds__(FL_THREADS) void flanger_kernel(
                     : "memory", "scc", "vcc", "v84", "v85", "v86", "v87");
                 const float oj = __fadd_rn(xs, __fmul_rn(dp, it));                                   // fx.py:115
                 o[j] = oj;
+                if (STASH) tap[j] = it;
             }
 #pragma unroll
             for (int j = 0; j < FL_V; ++j) {
@@ -243,6 +249,7 @@ __global__ __launch_bounds__(FL_THREADS) void flanger_kernel(
                 if (n < N && (!probe || c + 1 == n_chunks)) {  // probe: only the last chunk is stored (keeps the chain live)
                     const float v = __fadd_rn(__fmul_rn(omm, rc[j].x), __fmul_rn(mx, o[j]));         // fx.py:117
                     yb[n] = fminf(fmaxf(v, -1.0f), 1.0f);                                           // fx.py:118
+                    if (STASH) stash[(size_t)b * N + n] = tap[j];
                 }
             }
         }
@@ -262,7 +269,7 @@ static int flanger_fwd_launch(const float *x, int64_t x_stride, const float *mod
                              const float *mix, const float *one_minus_mix, const int32_t *max_delay,
                              int32_t max_delay_max, const int32_t *rows, int64_t n_rows, int64_t B,
                              int64_t N, float *y, int64_t y_stride, float *mod_up, int64_t *dbg_prev, float *dbg_frac,
-                             void *stream, int probe)
+                             void *stream, int probe, float *stash = nullptr)
 {
     if (!x || !mod || !lfo_scale || !min_delay || !feedback || !depth || !mix || !one_minus_mix ||
         !max_delay || !y || B <= 0 || N <= 0 || n_mod <= 0)
@@ -271,13 +278,14 @@ static int flanger_fwd_launch(const float *x, int64_t x_stride, const float *mod
     if (max_delay_max > FL_MAX_M || max_delay_max > 65535 || N >= (1ll << 30)) return MX_ERR_UNSUPPORTED;
     const int64_t items = rows ? n_rows : B;
     if (items <= 0) return MX_OK;
-    static bool attr_set[64] = {};                       // per device: one process may drive several GPUs
+    static bool attr_set[2][64] = {};                    // per kernel and device: one process may drive several GPUs
+    const void *kern = stash ? (const void *)flanger_kernel<true> : (const void *)flanger_kernel<false>;
     int dev = 0;
     (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= 64 || !attr_set[dev]) {
-        (void)hipFuncSetAttribute((const void *)flanger_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+    if (dev < 0 || dev >= 64 || !attr_set[stash != nullptr][dev]) {
+        (void)hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize,
                             (FL_MAX_M + FL_RING_FLOATS) * sizeof(float));
-        if (dev >= 0 && dev < 64) attr_set[dev] = true;
+        if (dev >= 0 && dev < 64) attr_set[stash != nullptr][dev] = true;
     }
     // LDS: delay line (max over the batch) + the LFO row when it is resampled in-kernel (n_mod < N) + the record ring
     const int lfo_off = max_delay_max;
@@ -286,10 +294,16 @@ static int flanger_fwd_launch(const float *x, int64_t x_stride, const float *mod
     const int ring_off = (int)lds_floats;
     if (lds_floats > FL_MAX_M) return MX_ERR_UNSUPPORTED;
     const size_t lds = (lds_floats + FL_RING_FLOATS) * sizeof(float);
-    hipLaunchKernelGGL(flanger_kernel, dim3((unsigned)items), dim3(FL_THREADS), lds, (hipStream_t)stream, x, (long long)x_stride, mod,
-                       (int)n_mod, interp_scale_host(n_mod, N), lfo_scale, min_delay, feedback, depth,
-                       mix, one_minus_mix, max_delay, rows, (int)N, lfo_off, ring_off, y, (long long)y_stride, mod_up,
-                       (long long *)dbg_prev, dbg_frac, probe);
+    if (stash)
+        hipLaunchKernelGGL(flanger_kernel<true>, dim3((unsigned)items), dim3(FL_THREADS), lds, (hipStream_t)stream, x,
+                           (long long)x_stride, mod, (int)n_mod, interp_scale_host(n_mod, N), lfo_scale, min_delay, feedback,
+                           depth, mix, one_minus_mix, max_delay, rows, (int)N, lfo_off, ring_off, y, (long long)y_stride,
+                           mod_up, (long long *)dbg_prev, dbg_frac, probe, stash);
+    else
+        hipLaunchKernelGGL(flanger_kernel<false>, dim3((unsigned)items), dim3(FL_THREADS), lds, (hipStream_t)stream, x, (long long)x_stride, mod,
+                           (int)n_mod, interp_scale_host(n_mod, N), lfo_scale, min_delay, feedback, depth,
+                           mix, one_minus_mix, max_delay, rows, (int)N, lfo_off, ring_off, y, (long long)y_stride, mod_up,
+                           (long long *)dbg_prev, dbg_frac, probe, (float *)nullptr);
     return mx_launch_status();
 }
 
@@ -312,6 +326,20 @@ MX_EXPORT int mx_flanger_fwd_probe(const float *x, int64_t x_stride, const float
                              void *stream)
 {
     return flanger_fwd_launch(x, x_stride, mod, n_mod, lfo_scale, min_delay, feedback, depth, mix, one_minus_mix, max_delay, max_delay_max, rows, n_rows, B, N, y, y_stride, mod_up, dbg_prev, dbg_frac, stream, 1);
+}
+
+// Forward of the adjoint (flanger_bwd.hip): mx_flanger_fwd plus the tap v[n] of every sample in stash (B,N), dense rows.
+// The LFO must be full rate (n_mod == N): the adjoint does not differentiate the in-kernel resampling.
+MX_EXPORT int mx_flanger_fwd_stash(const float *x, int64_t x_stride, const float *mod, int64_t n_mod, const float *lfo_scale,
+                                   const float *min_delay, const float *feedback, const float *depth,
+                                   const float *mix, const float *one_minus_mix, const int32_t *max_delay,
+                                   int32_t max_delay_max, const int32_t *rows, int64_t n_rows, int64_t B,
+                                   int64_t N, float *y, int64_t y_stride, float *stash, void *stream)
+{
+    if (!stash) return MX_ERR_ARG;
+    if (n_mod != N) return MX_ERR_UNSUPPORTED;
+    return flanger_fwd_launch(x, x_stride, mod, n_mod, lfo_scale, min_delay, feedback, depth, mix, one_minus_mix, max_delay,
+                              max_delay_max, rows, n_rows, B, N, y, y_stride, nullptr, nullptr, nullptr, stream, 0, stash);
 }
 
 // ---- measurement aid: the LDS round trip of one lock-step -------------------------------------------------------------

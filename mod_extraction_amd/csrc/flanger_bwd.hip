@@ -1,0 +1,295 @@
+// flanger_bwd.hip -- K2 adjoint: gradient of the mono flanger / chorus (reference: mod_extraction/fx.py:72-119) with
+// respect to x, mod_sig and the per-clip constants, from the taps v[n] that mx_flanger_fwd_stash (flanger.hip) stored.
+//
+// The gradient is the derivative of the reference loop restated without in-place writes: floor (prev / next) has zero
+// derivative, the read fraction and torch.remainder derivative 1, clip passes the gradient where -1 <= z <= 1, and slots
+// read before they were ever written read 0 (gradient sent there is dropped).  Per sample n (v the tap, d = x + fb v the
+// value written, o = x + depth v, z = (1-mix) x + mix o):
+//   g_z = dy [-1 <= z <= 1],  g_o = mix g_z,  g_v = depth g_o + fb g_d,
+//   g_d[n] = sum over the later reads of d[n] of their interpolation weight x g_v   (reverse-time recurrence)
+//   dx = (1-mix) g_z + g_o + g_d,  g_f = g_v (d[next] - d[prev]),  dmod = -lfo_scale g_f
+//   d feedback = sum g_d v, d depth = sum g_o v, d mix = sum g_z (o - x), d lfo_scale = -sum g_f mod, d min_delay = -sum g_f
+//
+// Two launches.
+//  1. fb_recur_kernel -- the serial part, g_d.  One workgroup = one clip = a consumer wave + FB_V producer waves, as in
+//     the forward, walking the clip BACKWARDS in chunks of 512 samples.  An LDS accumulator A[M] is indexed like the
+//     delay line: A[s] holds the gradient already sent to the value slot s currently holds.  Reverse of one sample
+//     (read prev / next, then write w): g_d = A[w], A[w] = 0; then A[prev] += (1-f) g_v, A[next] += f g_v.  The forward's
+//     dependency-free runs (no read of a run sees a write of the same run) are valid lock-steps of this reverse sweep: the
+//     whole run takes its g_d first, then scatters.  The producers additionally split a run where the age of the value
+//     read at prev (or at next) does not increase from one sample to the next: inside a dependency-free run equal slots
+//     mean equal ages, so every scatter instruction of a lock-step has pairwise distinct addresses (one ds_add_f32 for all
+//     prev halves, then one for all next halves; LDS executes one wave's instructions in order).  No two lanes ever race on
+//     an address, so the sums are the same on every run.
+//  2. fb_out_kernel -- everything else is independent per sample: one workgroup per clip recomputes the slots, z and the
+//     two values d read (x and the stash at most M samples back, L2-resident), writes dx and dmod, and sums the five
+//     parameter partials in fp64 in a fixed order (per thread, then a butterfly, then the waves in order).
+#include "common.h"
+
+#define FB_V 8                                           // rows of 64 samples per chunk (the forward's FL_V)
+#define FB_CHUNK (64 * FB_V)
+#define FB_SLOT_FLOATS (FB_CHUNK * 6 + 2 * FB_V)         // FB_CHUNK float4 records, FB_CHUNK 64-bit run masks, FB_V run counts
+#define FB_RING_FLOATS (2 * FB_SLOT_FLOATS)
+#define FB_MAX_M (40960 - FB_RING_FLOATS)                // the forward's FL_MAX_M: 160 KB LDS minus the ring
+#define FB_THREADS (64 * (1 + FB_V))
+#define FB_OUT_THREADS 512
+
+// fx.py:95-103 for one sample, exactly as flanger.hip's producers evaluate it (fp32, no contraction): write slot w = n % M,
+// read slots prev / next and the read fraction.
+__device__ __forceinline__ void fb_slots(int w, float m, float ls, float md, int M, float Mf, int &prev, int &next,
+                                         float &frac)
+{
+    const float d = __fadd_rn(__fmul_rn(ls, m), md);                    // fx.py:99
+    const float r1 = __fadd_rn(__fsub_rn((float)w, d), Mf);             // fx.py:100
+    float r;
+    if (r1 >= 0.0f && r1 < Mf) r = r1;
+    else if (r1 >= Mf && r1 < __fadd_rn(Mf, Mf)) r = __fsub_rn(r1, Mf);
+    else r = torch_remainderf(r1, Mf);
+    const float fl = floorf(r);
+    int p = (int)fl;                                                    // fx.py:102
+    if (p < 0) p = 0;
+    if (p >= M) p = M - 1;
+    prev = p;
+    next = p + 1 == M ? 0 : p + 1;                                      // fx.py:103
+    frac = __fsub_rn(r, fl);                                            // fx.py:101
+}
+
+// distance back from the write at slot w to the last write of slot s (slot w itself: M samples ago)
+__device__ __forceinline__ int fb_dist(int w, int s, int M)
+{
+    int d = w - s;
+    return d <= 0 ? d + M : d;
+}
+
+// the forward's output z (fx.py:115-117, before the clip) and o, recomputed bit-exactly from x and the tap
+__device__ __forceinline__ float fb_z(float xv, float v, float dp, float mx, float omm, float &o)
+{
+    o = __fadd_rn(xv, __fmul_rn(dp, v));
+    return __fadd_rn(__fmul_rn(omm, xv), __fmul_rn(mx, o));
+}
+
+__global__ __launch_bounds__(FB_THREADS) void fb_recur_kernel(
+    const float *__restrict__ dy, long long dy_stride, const float *__restrict__ x, long long x_stride,
+    const float *__restrict__ mod, const float *__restrict__ stash, const float *__restrict__ lfo_scale,
+    const float *__restrict__ min_delay, const float *__restrict__ feedback, const float *__restrict__ depth,
+    const float *__restrict__ mix, const float *__restrict__ one_minus_mix, const int *__restrict__ max_delay,
+    const int *__restrict__ rows, int N, int ring_off, float *__restrict__ gd_out)
+{
+    extern __shared__ __attribute__((aligned(16))) float buf[];        // [A: M floats | ring]
+    const int lane = threadIdx.x & 63;
+    const bool producer = threadIdx.x >= 64;
+    const int pw = (int)(threadIdx.x >> 6) - 1;
+    const int b = rows ? rows[blockIdx.x] : (int)blockIdx.x;
+    const int M = max_delay[b];
+    const float Mf = (float)M;
+    const float ls = lfo_scale[b], md = min_delay[b], fb = feedback[b], dp = depth[b];
+    const float mx = mix[b], omm = one_minus_mix[b];
+    const float *dyb = dy + (size_t)b * dy_stride;
+    const float *xb = x + (size_t)b * x_stride;
+    const float *mb = mod + (size_t)b * N;
+    const float *sb = stash + (size_t)b * N;
+    float *gb = gd_out + (size_t)b * N;
+    float *ring = buf + ring_off;
+    constexpr int SLOT = FB_SLOT_FLOATS;
+
+    for (int i = threadIdx.x; i < M; i += FB_THREADS) buf[i] = 0.0f;
+
+    const int n_chunks = (N + FB_CHUNK - 1) / FB_CHUNK;
+    // producer: inputs of the chunk it builds next, loaded one chunk ahead
+    float xr = 0.0f, mr = 0.0f, vr = 0.0f, gr = 0.0f;
+    auto load = [&](int c) {
+        const int n = c * FB_CHUNK + pw * 64 + lane;
+        const bool ok = c >= 0 && n < N;
+        xr = ok ? xb[n] : 0.0f;
+        mr = ok ? mb[n] : 0.0f;
+        vr = ok ? sb[n] : 0.0f;
+        gr = ok ? dyb[n] : 0.0f;
+    };
+    // records of row pw of chunk c -> ring slot c & 1: {depth g_o, f, 1 - f, w | prev << 16} and the lane masks of the
+    // row's lock-steps (run r in lane r)
+    auto build = [&](int c) {
+        const int n = c * FB_CHUNK + pw * 64 + lane;
+        float4 *rec = reinterpret_cast<float4 *>(ring + (c & 1) * SLOT);
+        unsigned long long *run_mask = reinterpret_cast<unsigned long long *>(ring + (c & 1) * SLOT + 4 * FB_CHUNK);
+        int *n_runs = reinterpret_cast<int *>(ring + (c & 1) * SLOT + 6 * FB_CHUNK);
+        const float xv = xr, m = mr, v = vr, g = gr;
+        load(c - 1);
+        const bool valid = n < N;
+        const int w = valid ? n % M : 0;
+        int prev, next;
+        float frac;
+        fb_slots(w, m, ls, md, M, Mf, prev, next, frac);
+        float o;
+        const float z = fb_z(xv, v, dp, mx, omm, o);
+        const float gz = (z >= -1.0f && z <= 1.0f) ? g : 0.0f;         // clamp's backward: inclusive bounds
+        const float gvo = valid ? __fmul_rn(dp, __fmul_rn(mx, gz)) : 0.0f;
+        rec[pw * 64 + lane] = make_float4(gvo, frac, __fsub_rn(1.0f, frac), __int_as_float(w | (prev << 16)));
+        const int dpr = fb_dist(w, prev, M), dnx = fb_dist(w, next, M);
+        const int dep = min(dpr, dnx);
+        int tk = !valid || dep > lane ? -1 : lane - dep;               // newest sample of this row the reads depend on
+        // ages of the two values read; inside a dependency-free run equal slots <=> equal ages: split where an age does
+        // not increase, so that the scatter addresses of a lock-step are distinct
+        const int age_p = n - dpr, age_n = n - dnx;
+        const int age_p1 = __shfl_up(age_p, 1, 64), age_n1 = __shfl_up(age_n, 1, 64);
+        if (valid && lane > 0 && (age_p <= age_p1 || age_n <= age_n1)) tk = max(tk, lane - 1);
+        const unsigned long long live = __ballot(valid);
+        unsigned long long mine = 0ull;
+        int a = 0, run = 0;
+        while (a < 64) {
+            const unsigned long long conflict = __ballot(lane >= a && tk >= a);
+            const int bnd = conflict ? (int)__builtin_ctzll(conflict) : 64;
+            if (lane == run) mine = (~0ull << a) & (~0ull >> (64 - bnd)) & live;
+            a = bnd;
+            ++run;
+        }
+        run_mask[pw * 64 + lane] = mine;
+        if (lane == 0) n_runs[pw] = run;
+    };
+
+    if (producer) {
+        load(n_chunks - 1);
+        build(n_chunks - 1);
+    }
+    for (int c = n_chunks - 1; c >= 0; --c) {
+        __syncthreads();                                               // records of chunk c complete; slot (c - 1) & 1 free
+        if (producer) {
+            if (c > 0) build(c - 1);
+        } else {
+            const float4 *rec = reinterpret_cast<const float4 *>(ring + (c & 1) * SLOT);
+            const unsigned long long *run_mask = reinterpret_cast<const unsigned long long *>(ring + (c & 1) * SLOT + 4 * FB_CHUNK);
+            const int *n_runs = reinterpret_cast<const int *>(ring + (c & 1) * SLOT + 6 * FB_CHUNK);
+            float gd_[FB_V];
+#pragma unroll
+            for (int j = FB_V - 1; j >= 0; --j) {
+                const float4 rc = rec[j * 64 + lane];
+                const unsigned long long m64 = run_mask[j * 64 + lane];
+                const unsigned m_lo = (unsigned)m64, m_hi = (unsigned)(m64 >> 32);
+                const int nr = __builtin_amdgcn_readfirstlane(n_runs[j]);
+                const int pk = __float_as_int(rc.w), w = pk & 0xffff, prev = (pk >> 16) & 0xffff;
+                const int next = prev + 1 == M ? 0 : prev + 1;
+                const float gvo = rc.x, frac = rc.y, omf = rc.z;
+                float gd = 0.0f;
+                for (int r = nr - 1; r >= 0; --r) {
+                    // (readlane returns int: zero-extend the low half, or bit 31 would set lanes 32-63)
+                    const unsigned long long msk = ((unsigned long long)(unsigned)__builtin_amdgcn_readlane(m_hi, r) << 32) |
+                                                   (unsigned)__builtin_amdgcn_readlane(m_lo, r);
+                    asm volatile("" ::: "memory");                     // keep this lock-step's LDS traffic behind the last
+                    if ((msk >> lane) & 1ull) {
+                        gd = __hip_atomic_exchange(buf + w, 0.0f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                        const float gv = __fadd_rn(gvo, __fmul_rn(fb, gd));
+                        __hip_atomic_fetch_add(buf + prev, __fmul_rn(omf, gv), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                        asm volatile("" ::: "memory");                 // all prev halves, then all next halves
+                        __hip_atomic_fetch_add(buf + next, __fmul_rn(frac, gv), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    }
+                }
+                gd_[j] = gd;
+            }
+#pragma unroll
+            for (int j = 0; j < FB_V; ++j) {
+                const int n = c * FB_CHUNK + j * 64 + lane;
+                if (n < N) gb[n] = gd_[j];
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(FB_OUT_THREADS) void fb_out_kernel(
+    const float *__restrict__ dy, long long dy_stride, const float *__restrict__ x, long long x_stride,
+    const float *__restrict__ mod, const float *__restrict__ stash, const float *__restrict__ gd_in,
+    const float *__restrict__ lfo_scale, const float *__restrict__ min_delay, const float *__restrict__ feedback,
+    const float *__restrict__ depth, const float *__restrict__ mix, const float *__restrict__ one_minus_mix,
+    const int *__restrict__ max_delay, const int *__restrict__ rows, int N, float *__restrict__ dx, long long dx_stride,
+    float *__restrict__ dmod, long long dmod_stride, double *__restrict__ d_ls, double *__restrict__ d_md,
+    double *__restrict__ d_fb, double *__restrict__ d_dp, double *__restrict__ d_mx)
+{
+    __shared__ double red[5][FB_OUT_THREADS / 64];
+    const int b = rows ? rows[blockIdx.x] : (int)blockIdx.x;
+    const int M = max_delay[b];
+    const float Mf = (float)M;
+    const float ls = lfo_scale[b], md = min_delay[b], fb = feedback[b], dp = depth[b];
+    const float mx = mix[b], omm = one_minus_mix[b];
+    const float *dyb = dy + (size_t)b * dy_stride;
+    const float *xb = x + (size_t)b * x_stride;
+    const float *mb = mod + (size_t)b * N;
+    const float *sb = stash + (size_t)b * N;
+    const float *gb = gd_in + (size_t)b * N;
+    double s_ls = 0.0, s_md = 0.0, s_fb = 0.0, s_dp = 0.0, s_mx = 0.0;
+    for (int n = threadIdx.x; n < N; n += FB_OUT_THREADS) {
+        const float xv = xb[n], v = sb[n], m = mb[n], g = dyb[n], gd = gb[n];
+        const int w = n % M;
+        int prev, next;
+        float frac;
+        fb_slots(w, m, ls, md, M, Mf, prev, next, frac);
+        float o;
+        const float z = fb_z(xv, v, dp, mx, omm, o);
+        const double gz = (z >= -1.0f && z <= 1.0f) ? (double)g : 0.0;
+        const double go = (double)mx * gz;
+        const double gv = (double)dp * go + (double)fb * (double)gd;
+        // the two values the reads of step n saw: d of the last write of each slot before n (0 if never written)
+        const int mp = n - fb_dist(w, prev, M), mn = n - fb_dist(w, next, M);
+        const float d_p = mp >= 0 ? __fadd_rn(xb[mp], __fmul_rn(fb, sb[mp])) : 0.0f;
+        const float d_n = mn >= 0 ? __fadd_rn(xb[mn], __fmul_rn(fb, sb[mn])) : 0.0f;
+        const double gf = gv * ((double)d_n - (double)d_p);
+        if (dx) dx[(size_t)b * dx_stride + n] = (float)((double)omm * gz + go + (double)gd);
+        if (dmod) dmod[(size_t)b * dmod_stride + n] = (float)(-(double)ls * gf);
+        s_ls += gf * (double)m;
+        s_md += gf;
+        s_fb += (double)gd * (double)v;
+        s_dp += go * (double)v;
+        s_mx += gz * ((double)o - (double)xv);
+    }
+    const double s[5] = {s_ls, s_md, s_fb, s_dp, s_mx};
+    const int wv = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < 5; ++k) {
+        const double t = wave_sum_f64(s[k]);
+        if ((threadIdx.x & 63) == 0) red[k][wv] = t;
+    }
+    __syncthreads();
+    if (threadIdx.x < 5) {
+        const int k = threadIdx.x;
+        double t = 0.0;
+        for (int i = 0; i < FB_OUT_THREADS / 64; ++i) t += red[k][i];
+        double *dst = k == 0 ? d_ls : k == 1 ? d_md : k == 2 ? d_fb : k == 3 ? d_dp : d_mx;
+        if (dst) dst[b] = k < 2 ? -t : t;
+    }
+}
+
+// C ABI ---------------------------------------------------------------------------------------
+MX_EXPORT int mx_flanger_bwd(const float *dy, int64_t dy_stride, const float *x, int64_t x_stride, const float *mod,
+                             const float *stash, const float *lfo_scale, const float *min_delay, const float *feedback,
+                             const float *depth, const float *mix, const float *one_minus_mix, const int32_t *max_delay,
+                             int32_t max_delay_max, const int32_t *rows, int64_t n_rows, int64_t B, int64_t N,
+                             float *ws, float *dx, int64_t dx_stride, float *dmod, int64_t dmod_stride,
+                             double *d_lfo_scale, double *d_min_delay, double *d_feedback, double *d_depth,
+                             double *d_mix, void *stream)
+{
+    if (!dy || !x || !mod || !stash || !lfo_scale || !min_delay || !feedback || !depth || !mix || !one_minus_mix ||
+        !max_delay || !ws || B <= 0 || N <= 0)
+        return MX_ERR_ARG;
+    if (max_delay_max < 2 || dy_stride < N || x_stride < N || (dx && dx_stride < N) || (dmod && dmod_stride < N))
+        return MX_ERR_ARG;
+    if (max_delay_max > FB_MAX_M || max_delay_max > 65535 || N >= (1ll << 30)) return MX_ERR_UNSUPPORTED;
+    const int64_t items = rows ? n_rows : B;
+    if (items <= 0) return MX_OK;
+    static bool attr_set[64] = {};
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    if (dev < 0 || dev >= 64 || !attr_set[dev]) {
+        (void)hipFuncSetAttribute((const void *)fb_recur_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (FB_MAX_M + FB_RING_FLOATS) * sizeof(float));
+        if (dev >= 0 && dev < 64) attr_set[dev] = true;
+    }
+    const int ring_off = (max_delay_max + 3) & ~3;                      // the ring holds float4 records
+    const size_t lds = ((size_t)ring_off + FB_RING_FLOATS) * sizeof(float);
+    hipLaunchKernelGGL(fb_recur_kernel, dim3((unsigned)items), dim3(FB_THREADS), lds, (hipStream_t)stream, dy,
+                       (long long)dy_stride, x, (long long)x_stride, mod, stash, lfo_scale, min_delay, feedback, depth, mix,
+                       one_minus_mix, max_delay, rows, (int)N, ring_off, ws);
+    int rc = mx_launch_status();
+    if (rc != MX_OK) return rc;
+    hipLaunchKernelGGL(fb_out_kernel, dim3((unsigned)items), dim3(FB_OUT_THREADS), 0, (hipStream_t)stream, dy,
+                       (long long)dy_stride, x, (long long)x_stride, mod, stash, (const float *)ws, lfo_scale, min_delay,
+                       feedback, depth, mix, one_minus_mix, max_delay, rows, (int)N, dx, (long long)dx_stride, dmod,
+                       (long long)dmod_stride, d_lfo_scale, d_min_delay, d_feedback, d_depth, d_mix);
+    return mx_launch_status();
+}

@@ -1,11 +1,14 @@
 """Host mirror of mod_extraction/fx.py: same class, constructor and forward signature
 (fx.py:25-44,121-130); the per-sample delay-line recurrence runs in the ``mx_flanger_fwd`` HIP
 kernel (one wavefront per clip, delay line in LDS) instead of 88 200 python iterations.
+``apply_effect`` is differentiable (``mx_flanger_fwd_stash`` + ``mx_flanger_bwd``) when grad mode is on and an input
+requires grad.
 """
 from typing import Dict, Optional, Tuple, Union
 
 import torch
 from torch import Tensor as T, nn
+from torch.autograd.function import once_differentiable
 
 from . import _hip
 
@@ -95,6 +98,88 @@ def flanger_forward(x: T, mod_sig: T, consts: Dict[str, T], max_delay: T, max_de
     return y
 
 
+def flanger_forward_stash(x: T, mod_sig: T, consts: Dict[str, T], max_delay: T, max_delay_max: int,
+                          rows: Optional[T] = None, out: Optional[T] = None,
+                          stash: Optional[T] = None) -> Tuple[T, T]:
+    """Launch mx_flanger_fwd_stash: ``flanger_forward`` (same y, bit for bit) that also returns the tap v[n] of fx.py:113 of
+    every sample, (B,N) dense, for ``flanger_backward``.  mod_sig must be full rate (B,N)."""
+    B, N = x.shape
+    assert mod_sig.shape == (B, N)
+    y = out if out is not None else torch.empty_like(x)
+    st = stash if stash is not None else torch.empty((B, N), device=x.device, dtype=torch.float32)
+    xp, xs = _rows_view(x)
+    yp, ys = _rows_view(y)
+    _hip.call("mx_flanger_fwd_stash", xp, xs, _hip.ptr(mod_sig), N,
+              _hip.ptr(consts["lfo_scale"]), _hip.ptr(consts["min_delay"]), _hip.ptr(consts["feedback"]),
+              _hip.ptr(consts["depth"]), _hip.ptr(consts["mix"]), _hip.ptr(consts["one_minus_mix"]),
+              _hip.ptr(max_delay), int(max_delay_max), _hip.ptr(rows), 0 if rows is None else rows.numel(),
+              B, N, yp, ys, _hip.ptr(st), _hip.stream())
+    return y, st
+
+
+PARAM_GRADS = ("lfo_scale", "min_delay", "feedback", "depth", "mix")
+
+
+def flanger_backward(dy: T, x: T, mod_sig: T, stash: T, consts: Dict[str, T], max_delay: T, max_delay_max: int,
+                     rows: Optional[T] = None, need_dx: bool = True, need_dmod: bool = True,
+                     params: Tuple[str, ...] = PARAM_GRADS, dx: Optional[T] = None,
+                     dmod: Optional[T] = None) -> Tuple[Optional[T], Optional[T], Dict[str, T]]:
+    """Launch mx_flanger_bwd: the adjoint of fx.py:72-119 (the gradient the DESIGN K-table row defines).
+    dy, x: (B,N) views with contiguous rows; mod_sig, stash (B,N) dense.  Returns dx, dmod (B,N) (None unless asked for)
+    and the per-clip fp64 gradients of the constants named in ``params`` (d mix includes the one_minus_mix path)."""
+    B, N = x.shape
+    dev = x.device
+    if dy.stride(-1) != 1 or dy.stride(0) < N:            # e.g. the expanded ones of y.sum().backward()
+        dy = dy.contiguous()
+    if need_dx and dx is None:
+        dx = torch.empty((B, N), device=dev, dtype=torch.float32)
+    if need_dmod and dmod is None:
+        dmod = torch.empty((B, N), device=dev, dtype=torch.float32)
+    dxp, dxs = _rows_view(dx) if need_dx else (None, 0)
+    dmp, dms = _rows_view(dmod) if need_dmod else (None, 0)
+    dyp, dys = _rows_view(dy)
+    xp, xs = _rows_view(x)
+    grads = {k: torch.zeros((B,), device=dev, dtype=torch.float64) for k in params}
+    ws = torch.empty((B, N), device=dev, dtype=torch.float32)
+    _hip.call("mx_flanger_bwd", dyp, dys, xp, xs, _hip.ptr(mod_sig), _hip.ptr(stash),
+              _hip.ptr(consts["lfo_scale"]), _hip.ptr(consts["min_delay"]), _hip.ptr(consts["feedback"]),
+              _hip.ptr(consts["depth"]), _hip.ptr(consts["mix"]), _hip.ptr(consts["one_minus_mix"]),
+              _hip.ptr(max_delay), int(max_delay_max), _hip.ptr(rows), 0 if rows is None else rows.numel(), B, N,
+              _hip.ptr(ws), dxp, dxs, dmp, dms, *[_hip.ptr(grads.get(k)) for k in PARAM_GRADS], _hip.stream())
+    return (dx if need_dx else None), (dmod if need_dmod else None), grads
+
+
+class _FlangerFunction(torch.autograd.Function):
+    """y = flanger(x, mod, constants) over (clip, channel) rows; the (bs,) constants are shared by a clip's n_ch rows, so
+    their gradients are summed over the channels (in fp64) before they are rounded to the constants' dtype."""
+
+    @staticmethod
+    def forward(ctx, x, mod_sig, lfo_scale, min_delay, feedback, depth, mix, one_minus_mix, n_ch, max_delay_samples):
+        rows = x.size(0)
+        consts = {"lfo_scale": lfo_scale, "min_delay": min_delay, "feedback": feedback, "depth": depth, "mix": mix,
+                  "one_minus_mix": one_minus_mix}
+        consts = {k: (v.detach().repeat_interleave(n_ch) if n_ch > 1 else v.detach()).contiguous()
+                  for k, v in consts.items()}
+        md = torch.full((rows,), max_delay_samples, device=x.device, dtype=torch.int32)
+        y, stash = flanger_forward_stash(x.detach(), mod_sig.detach(), consts, md, max_delay_samples)
+        ctx.save_for_backward(x, mod_sig, stash)
+        ctx.consts, ctx.md, ctx.n_ch, ctx.max_delay_samples = consts, md, n_ch, max_delay_samples
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        x, mod_sig, stash = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        params = tuple(k for k, n in zip(PARAM_GRADS, need[2:7]) if n)
+        dx, dmod, g = flanger_backward(dy, x, mod_sig, stash, ctx.consts, ctx.md, ctx.max_delay_samples,
+                                       need_dx=need[0], need_dmod=need[1], params=params)
+        out = [dx, dmod]
+        for k in PARAM_GRADS:
+            out.append(g[k].view(-1, ctx.n_ch).sum(1).float() if k in g else None)
+        return tuple(out) + (None, None, None)
+
+
 class MonoFlangerChorusModule(nn.Module):
     def __init__(self, batch_size: int, n_ch: int, n_samples: int, sr: float,
                  max_min_delay_ms: float, max_lfo_delay_ms: float) -> None:
@@ -129,8 +214,35 @@ class MonoFlangerChorusModule(nn.Module):
     def apply_effect(self, x: T, mod_sig: T, feedback: Param, min_delay_width: Param, width: Param, depth: Param,
                      mix: Param) -> T:
         """fx.py:72-119 (the per-sample loop) = one kernel launch here; ``forward`` is this under no_grad, as in the
-        reference."""
+        reference.  With grad mode on and x, mod_sig or a tensor parameter requiring grad, the output carries a grad_fn
+        (``mx_flanger_fwd_stash`` forward, ``mx_flanger_bwd`` backward; y is the same, bit for bit).  mod_sig must then be
+        full rate; python-float parameters get no gradient."""
+        params = (feedback, min_delay_width, width, depth, mix)
+        if torch.is_grad_enabled() and (x.requires_grad or mod_sig.requires_grad or
+                                        any(isinstance(p, T) and p.requires_grad for p in params)):
+            return self._apply_effect_grad(x, mod_sig, *params)
         return self.forward(x, mod_sig, feedback, min_delay_width, width, depth, mix)
+
+    def _apply_effect_grad(self, x: T, mod_sig: T, feedback: Param, min_delay_width: Param, width: Param, depth: Param,
+                           mix: Param) -> T:
+        assert x.ndim == 3
+        bs, n_ch, n = x.shape
+        assert n_ch == self.n_ch
+        assert mod_sig.size(0) == bs and mod_sig.size(-1) == n
+        if mod_sig.ndim == 3:
+            assert mod_sig.size(1) in (1, n_ch)
+        consts = derive_clip_constants(bs, x.device, self.max_min_delay_samples, self.max_lfo_delay_samples,
+                                       feedback, min_delay_width, width, depth, mix)
+        rows = bs * n_ch
+        xr = x.reshape(rows, n).float()
+        if xr.stride(-1) != 1:
+            xr = xr.contiguous()
+        if mod_sig.ndim == 2 or mod_sig.size(1) == 1:               # fx.py:84-85: shared by the channels
+            mod_sig = mod_sig.reshape(bs, 1, n).expand(-1, n_ch, -1)
+        mr = mod_sig.reshape(rows, n).float().contiguous()
+        y = _FlangerFunction.apply(xr, mr, consts["lfo_scale"], consts["min_delay"], consts["feedback"], consts["depth"],
+                                   consts["mix"], consts["one_minus_mix"], n_ch, self.max_delay_samples)
+        return y.view(bs, n_ch, n)
 
     def forward(self, x: T, mod_sig: T, feedback: Param = 0.0, min_delay_width: Param = 1.0,
                 width: Param = 1.0, depth: Param = 1.0, mix: Param = 1.0) -> T:
