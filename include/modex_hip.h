@@ -146,6 +146,41 @@ int mx_phaser_fwd_probe(const float *x, int64_t x_stride, const float *rate, con
                   const int32_t *rows, int64_t n_rows, int64_t B, int64_t N, double sr, int32_t exact_order,
                   float *y, int64_t y_stride, float *dry_out, float *workspace, int64_t workspace_stride, void *stream);
 
+/* Forward of the phaser adjoint: the linear scan of mx_phaser_fwd (y and dry_out bit-identical to it when mod is NULL) that
+ * can be driven by an external LFO and leaves a stash for mx_phaser_bwd.  x_width: valid floats of a row of x
+ * (N <= x_width <= x_stride).  CALLER'S CONTRACT: lead[b] + N <= x_width for every processed clip; lead lives on the device and is
+ * not checked by the host: the kernel SKIPS a clip that breaks it -- its y, dry_out and stash rows keep what they held, the
+ * status is still MX_OK (fx.phaser_forward_stash asserts the contract).  mod (optional): row b at mod + b*n_mod, one
+ * value in [0, 1] per cut-off update (4 samples, from sample 0 of the processed clip), n_mod >= ceil(x_width / 4) (any lead fits):
+ * osc = 1 - 2 mod replaces JUCE's sin(phase - pi) = -sin(phase), i.e. mod is the reference's ground-truth LFO
+ * make_mod_signal(.., pi / 2, "cos") = (1 + sin wt) / 2 (datasets.py:442, modulations.py:35) sampled every 4th sample; rate is then not read and may be NULL.
+ * stash: 16-byte aligned, row b at stash + b*stash_stride, laid out for stash_groups cut-off groups: stash_groups a multiple
+ * of 4 and >= ceil(x_width / 4), stash_stride a multiple of 4 and >= 4 stash_groups + 512 * 57 + 512 * 8 * ceil(ceil(stash_groups / 512) / 2) floats
+ * (per group G, the lfo before its clamp, osc and the output-clip decisions; per chunk the scan's map; the state at the
+ * start of every second group).  Other arguments as mx_phaser_fwd.  No reference counterpart (the reference's phaser is
+ * pedalboard's and has no gradient). */
+int mx_phaser_fwd_stash(const float *x, int64_t x_stride, int64_t x_width, const float *mod, int64_t n_mod,
+                        const float *rate, const float *depth, const float *centre, const float *feedback,
+                        const float *mix, const int32_t *lead, const int32_t *rows, int64_t n_rows, int64_t B,
+                        int64_t N, double sr, float *y, int64_t y_stride, float *dry_out, float *stash,
+                        int64_t stash_groups, int64_t stash_stride, void *stream);
+/* Adjoint of the phaser recurrence (oracle_ref.c:orc_phaser): both clips pass the gradient on their closed interval
+ * (-1 <= m <= 1, 0 <= lfo <= 1 before clamping: aten's clamp rule).  dy: row b at dy + b*dy_stride, N floats on the output
+ * window; x, x_stride, x_width, the parameters, lead, rows / n_rows, B, N, sr and the stash as given to / left by
+ * mx_phaser_fwd_stash.  Outputs, each optional (NULL skips it): dx, row b at dx + b*dx_stride, x_width floats: the gradient
+ * with respect to EVERY processed source sample, the lead included, zeros beyond lead[b] + N; dmod, row b at
+ * dmod + b*dmod_stride, n_mod >= ceil(x_width / 4) floats: the gradient with respect to the external LFO (with the
+ * built-in oscillator: with respect to (1 - osc) / 2), zeros beyond the clip's groups; per-clip fp64 d_depth, d_centre
+ * (centre_frequency_hz), d_feedback, d_mix (B,).  A clip with lead[b] + N > x_width is skipped as in the forward (outputs
+ * untouched, MX_OK; fx.phaser_backward asserts the contract).  No gradient with respect to the rate (see fx.PhaserModule).
+ * Deterministic: no atomics; per-clip sums in fp64 in a fixed order. */
+int mx_phaser_bwd(const float *dy, int64_t dy_stride, const float *x, int64_t x_stride, int64_t x_width,
+                  const float *stash, int64_t stash_groups, int64_t stash_stride, const float *depth,
+                  const float *centre, const float *feedback, const float *mix, const int32_t *lead,
+                  const int32_t *rows, int64_t n_rows, int64_t B, int64_t N, double sr, float *dx,
+                  int64_t dx_stride, float *dmod, int64_t dmod_stride, int64_t n_mod, double *d_depth,
+                  double *d_centre, double *d_feedback, double *d_mix, void *stream);
+
 /* ---- K4: log-mel front end -- mod_extraction/models.py:170-181,199-208
  * (torchaudio MelSpectrogram: n_fft in {512, 1024, 2048} -- every shipped config: 1024 --, hann, centre/reflect, power 2,
  * mel filter bank `fb`; other n_fft: MX_ERR_UNSUPPORTED)

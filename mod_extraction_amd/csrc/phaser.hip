@@ -11,7 +11,7 @@
 // `lead` samples are processed (filter warm-up, LFO phase) before the N output samples: the
 // reference renders n + sr/rate samples and crops at a random offset (datasets.py:428-449).
 // Algorithmic HBM traffic: 8 B/sample (+4 B/sample when the cropped dry clip is also written).
-#include "common.h"
+#include "phaser_common.h"
 
 #define PH_BLOCK 256
 #ifndef PH_WPB
@@ -134,10 +134,17 @@ __global__ __launch_bounds__(64 * PH_WPB) void phaser_kernel(const float *__rest
 // The LFO phase at a chunk start must equal what 44 100 sequential fp32 additions give (JUCE accumulates in fp32; a
 // closed form in fp64 is 1e-5 rad off after a few thousand steps): ps_phase_after() below reproduces them exactly in
 // O(binades) steps.
-#define PS_WAVES 8
-#define PS_P (64 * PS_WAVES)       // chunks (lanes) per clip
-#define PS_MV 57                   // floats per chunk map: M column-major (49) + v (7) + pad
-#define PS_LDS_FLOATS (PS_P * PS_MV + (PS_P + 1) * 8)
+// (PS_P, PS_MV, PS_LDS_FLOATS: phaser_common.h)
+//
+// STASH = true (mx_phaser_fwd_stash) is the forward of the adjoint in phaser_bwd.hip: the same scan, y bit-identical, that
+//  * may take the LFO from outside: `mod`, one value in [0, 1] per cut-off update, osc = 1 - 2 mod in place of
+//    sin(phase - pi) (the rate is then not read).  The sign makes mod the reference's phaser ground truth
+//    make_mod_signal(.., pi / 2, "cos") = (cos(wt + pi / 2 + pi) + 1) / 2 = (1 + sin wt) / 2 (modulations.py:35,
+//    datasets.py:442), since JUCE's sin(phase - pi) = -sin(phase);
+//  * leaves per group G, pre (the lfo before its clamp), osc and the four output-clip decisions, per chunk the map M of
+//    phase A (its transpose is the chunk map of the adjoint: the backward does not run seven unit adjoints), and the state
+//    at the start of every PS_SUB-th group (phase C), from which the backward recomputes 8 samples at a time in registers.
+// The STASH = false instantiation compiles to the instructions it had before the template existed.
 
 // phase after g cut-off updates:  p <- fl(p + inc);  while (p >= 2 pi) p <- fl(p - 2 pi)   (oracle_ref.c:orc_phaser)
 // Inside one binade [2^e, 2^(e+1)) every representable p is a multiple of ulp = 2^(e-23), so fl(p + inc) = p + d with ONE
@@ -182,6 +189,7 @@ __device__ float ps_phase_after(int g, float inc, float two_pi)
     return p;
 }
 
+template <bool STASH>
 __global__ __launch_bounds__(PS_P) void phaser_scan_kernel(const float *__restrict__ x, long long x_stride,
                                                            const float *__restrict__ rate,
                                                            const float *__restrict__ depth,
@@ -192,7 +200,10 @@ __global__ __launch_bounds__(PS_P) void phaser_scan_kernel(const float *__restri
                                                            const int *__restrict__ rows, int n_items, int N, double sr,
                                                            float *__restrict__ y, long long y_stride,
                                                            float *__restrict__ dry_out, float *__restrict__ gws,
-                                                           long long gws_stride, int probe)
+                                                           long long gws_stride, int probe,
+                                                           const float *__restrict__ mod, long long mod_stride, int n_mod,
+                                                           float *__restrict__ stash, long long stash_stride, int sg,
+                                                           int x_width)
 {
     extern __shared__ __attribute__((aligned(16))) float ps_lds[];
     float *mv = ps_lds, *zs = ps_lds + PS_P * PS_MV;
@@ -205,12 +216,22 @@ __global__ __launch_bounds__(PS_P) void phaser_scan_kernel(const float *__restri
     float *yb = y + (size_t)b * y_stride;
     float *db = dry_out ? dry_out + (size_t)b * y_stride : nullptr;
     float *gw = gws + (size_t)item * gws_stride;
+    // STASH: the group records double as the cut-off workspace; a clip that does not fit its row is left alone
+    float *st = nullptr;
+    const float *mb = nullptr;
+    if constexpr (STASH) {
+        if (total > x_width || ((total + 3) >> 2) > sg) return;
+        st = stash + (size_t)b * stash_stride;
+        gw = st;
+        if (mod) mb = mod + (size_t)b * mod_stride;
+    }
+    const bool ext = STASH && mb != nullptr;                     // the LFO comes from outside
 
     const float two_pi = 6.283185307179586476925286766559f;
     const float pi_f = 3.14159265358979323846f;
     const float fmax_hz = (float)fmin(20000.0, 0.49 * sr);
     const float log_min = (float)log10(20.0), log_max = (float)log10((double)fmax_hz);
-    const float inc = __fmul_rn(__fdiv_rn(two_pi, (float)(sr / 4.0)), rate[b]);
+    const float inc = __fmul_rn(__fdiv_rn(two_pi, (float)(sr / 4.0)), ext ? 0.0f : rate[b]);
     const float norm_centre = __fdiv_rn(__fsub_rn((float)log10((double)centre[b]), log_min), __fsub_rn(log_max, log_min));
     const float osc_vol = __fmul_rn(depth[b], 0.5f);
     const float fb = feedback[b];
@@ -220,12 +241,20 @@ __global__ __launch_bounds__(PS_P) void phaser_scan_kernel(const float *__restri
     const int gpc = (n_groups + PS_P - 1) / PS_P;                // groups per chunk
     const int g0 = p * gpc, g1 = min(g0 + gpc, n_groups);        // this lane's groups [g0, g1) (empty beyond the clip)
 
-    const bool use_ws = gws != nullptr && (long long)n_groups <= gws_stride;
+    const bool use_ws = STASH || (gws != nullptr && (long long)n_groups <= gws_stride);
     // one cut-off update (oracle_ref.c:orc_phaser; sin / pow / tan in fp64 and rounded once = the host libm's float results)
     auto cutoff = [&](float ph) {
         const float osc = (float)sin((double)__fsub_rn(ph, pi_f));
         float lfo = __fadd_rn(__fmul_rn(osc, osc_vol), norm_centre);
         lfo = lfo < 0.0f ? 0.0f : (lfo > 1.0f ? 1.0f : lfo);
+        const float fc = (float)pow(10.0, (double)__fadd_rn(__fmul_rn(lfo, __fsub_rn(log_max, log_min)), log_min));
+        const float gg = (float)tan(3.14159265358979323846 * (double)fc / sr);
+        return __fdiv_rn(gg, __fadd_rn(1.0f, gg));
+    };
+    // the same update from a given osc, which also hands out the lfo before its clamp (STASH only)
+    auto coef = [&](float osc, float &pre) {
+        pre = __fadd_rn(__fmul_rn(osc, osc_vol), norm_centre);
+        const float lfo = pre < 0.0f ? 0.0f : (pre > 1.0f ? 1.0f : pre);
         const float fc = (float)pow(10.0, (double)__fadd_rn(__fmul_rn(lfo, __fsub_rn(log_max, log_min)), log_min));
         const float gg = (float)tan(3.14159265358979323846 * (double)fc / sr);
         return __fdiv_rn(gg, __fadd_rn(1.0f, gg));
@@ -243,7 +272,7 @@ __global__ __launch_bounds__(PS_P) void phaser_scan_kernel(const float *__restri
     for (int r = 0; r < 8; ++r)
 #pragma unroll
         for (int c = 0; c < 7; ++c) S[r][c] = r == c ? 1.0f : 0.0f;
-    float phase = ps_phase_after(min(g0, n_groups), inc, two_pi);
+    float phase = ext ? 0.0f : ps_phase_after(min(g0, n_groups), inc, two_pi);
     for (int g = g0; g < g1; ++g) {
         float xv[4];
 #pragma unroll
@@ -251,7 +280,17 @@ __global__ __launch_bounds__(PS_P) void phaser_scan_kernel(const float *__restri
             const int n = 4 * g + j;
             xv[j] = probe ? 0.25f : (n < total ? xb[n] : 0.0f);
         }
-        const float G = cutoff(phase);
+        float G;
+        if constexpr (STASH) {
+            float pre;
+            const float osc = ext ? __fsub_rn(1.0f, __fmul_rn(2.0f, g < n_mod ? mb[g] : 0.5f))
+                                  : (float)sin((double)__fsub_rn(phase, pi_f));
+            G = coef(osc, pre);
+            st[sg + g] = pre;
+            st[2 * sg + g] = osc;
+        } else {
+            G = cutoff(phase);
+        }
         phase = ps_step(phase, inc, two_pi);
         if (use_ws) gw[g] = G;
 #pragma unroll
@@ -294,6 +333,10 @@ __global__ __launch_bounds__(PS_P) void phaser_scan_kernel(const float *__restri
         }
     }
     __syncthreads();
+    if constexpr (STASH) {                                       // the chunk maps, as they lie in LDS
+        float *sm = st + 4 * (size_t)sg;
+        for (int i = p; i < PS_P * PS_MV; i += PS_P) sm[i] = mv[i];
+    }
 
     // ---- C: the chunk from its true start state, JUCE's operation order, output window
     {
@@ -313,6 +356,15 @@ __global__ __launch_bounds__(PS_P) void phaser_scan_kernel(const float *__restri
                 const int n = 4 * g + j;
                 xv[j] = probe ? 0.25f : (n < total ? xb[n] : 0.0f);
             }
+            int passed = 0;
+            if constexpr (STASH) {
+                if (((g - g0) & (PS_SUB - 1)) == 0) {
+                    float4 *ck = reinterpret_cast<float4 *>(st + 4 * (size_t)sg + PS_P * PS_MV) +
+                                 2 * ((size_t)p * ((gpc + PS_SUB - 1) / PS_SUB) + ((g - g0) / PS_SUB));
+                    ck[0] = make_float4(s0, s1, s2, s3);
+                    ck[1] = make_float4(s4, s5, last, 0.0f);
+                }
+            }
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const int n = 4 * g + j;
@@ -321,12 +373,14 @@ __global__ __launch_bounds__(PS_P) void phaser_scan_kernel(const float *__restri
                 PS_STAGE(s0) PS_STAGE(s1) PS_STAGE(s2) PS_STAGE(s3) PS_STAGE(s4) PS_STAGE(s5)
                 last = __fmul_rn(out, fb);
                 float m = __fadd_rn(__fmul_rn(out, wet_g), __fmul_rn(in, dry_g));
+                if constexpr (STASH) passed |= (m >= -1.0f && m <= 1.0f) ? 1 << j : 0;
                 m = m < -1.0f ? -1.0f : (m > 1.0f ? 1.0f : m);
                 if (n >= lead && n < total && (!probe || g + 1 == g1)) {
                     yb[n - lead] = m;
                     if (db) db[n - lead] = in;
                 }
             }
+            if constexpr (STASH) reinterpret_cast<int *>(st)[3 * (size_t)sg + g] = passed;
         }
     }
 #undef PS_STAGE
@@ -361,12 +415,13 @@ static int phaser_fwd_launch(const float *x, int64_t x_stride, const float *rate
         int dev = 0;
         (void)hipGetDevice(&dev);
         if (dev < 0 || dev >= 64 || !attr_set[dev]) {
-            (void)hipFuncSetAttribute((const void *)phaser_scan_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            (void)hipFuncSetAttribute((const void *)phaser_scan_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
             if (dev >= 0 && dev < 64) attr_set[dev] = true;
         }
-        hipLaunchKernelGGL(phaser_scan_kernel, dim3((unsigned)items), dim3(PS_P), lds, (hipStream_t)stream, x, (long long)x_stride,
+        hipLaunchKernelGGL(phaser_scan_kernel<false>, dim3((unsigned)items), dim3(PS_P), lds, (hipStream_t)stream, x, (long long)x_stride,
                            rate, depth, centre, feedback, mix, lead, rows, (int)items, (int)N, sr, y, (long long)y_stride,
-                           dry_out, workspace, (long long)workspace_stride, probe);
+                           dry_out, workspace, (long long)workspace_stride, probe, (const float *)nullptr, 0ll, 0,
+                           (float *)nullptr, 0ll, 0, 0);
     }
     return mx_launch_status();
 }
@@ -378,6 +433,35 @@ MX_EXPORT int mx_phaser_fwd(const float *x, int64_t x_stride, const float *rate,
                             void *stream)
 {
     return phaser_fwd_launch(x, x_stride, rate, depth, centre, feedback, mix, lead, rows, n_rows, B, N, sr, exact_order, y, y_stride, dry_out, workspace, workspace_stride, stream, 0);
+}
+
+// Forward of the adjoint (phaser_bwd.hip): the scan with STASH, see the kernel's header.  x_width: valid floats of an x row
+// (a clip whose lead + N exceeds it is SKIPPED: outputs untouched, status MX_OK -- lead is device data, the caller keeps
+// the contract); mod (optional): row b at mod + b*n_mod, n_mod >= ceil(x_width / 4) values in [0, 1], rate may then be NULL;
+// stash: 16-byte aligned, row b at stash + b*stash_stride (a multiple of 4), laid out for stash_groups groups
+// (phaser_common.h), stash_groups a multiple of 4 and >= ceil(x_width / 4).
+MX_EXPORT int mx_phaser_fwd_stash(const float *x, int64_t x_stride, int64_t x_width, const float *mod, int64_t n_mod,
+                                  const float *rate, const float *depth, const float *centre, const float *feedback,
+                                  const float *mix, const int32_t *lead, const int32_t *rows, int64_t n_rows, int64_t B,
+                                  int64_t N, double sr, float *y, int64_t y_stride, float *dry_out, float *stash,
+                                  int64_t stash_groups, int64_t stash_stride, void *stream)
+{
+    if (!x || !(mod || rate) || !depth || !centre || !feedback || !mix || !y || !stash || B <= 0 || N <= 0 || sr <= 0.0)
+        return MX_ERR_ARG;
+    if (x_width < N || x_stride < x_width || y_stride < N || (mod && n_mod < (x_width + 3) / 4)) return MX_ERR_ARG;
+    if (x_width >= (1ll << 30)) return MX_ERR_UNSUPPORTED;
+    if (stash_groups < (x_width + 3) / 4 || (stash_groups & 3) || stash_stride < ps_stash_floats(stash_groups)) return MX_ERR_ARG;
+    if ((stash_stride & 3) || ((uintptr_t)stash & 15)) return MX_ERR_ARG;      // the checkpoints are float4
+    const int64_t items = rows ? n_rows : B;
+    if (items <= 0) return MX_OK;
+    const size_t lds = PS_LDS_FLOATS * sizeof(float);
+    static MxLdsLatch latch = {};
+    if (mx_set_dyn_lds(latch, (const void *)phaser_scan_kernel<true>, lds) != MX_OK) return MX_ERR_LAUNCH;
+    hipLaunchKernelGGL(phaser_scan_kernel<true>, dim3((unsigned)items), dim3(PS_P), lds, (hipStream_t)stream, x, (long long)x_stride,
+                       rate, depth, centre, feedback, mix, lead, rows, (int)items, (int)N, sr, y, (long long)y_stride, dry_out,
+                       (float *)nullptr, 0ll, 0, mod, (long long)n_mod, (int)n_mod, stash, (long long)stash_stride,
+                       (int)stash_groups, (int)x_width);
+    return mx_launch_status();
 }
 
 // Measurement twin (bench.py's serial floor): the SAME launch with no global-memory traffic inside the sample loop -- inputs are constants, only the last chunk is stored.  Results are meaningless; nothing in the product calls it.

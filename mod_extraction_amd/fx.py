@@ -2,7 +2,8 @@
 (fx.py:25-44,121-130); the per-sample delay-line recurrence runs in the ``mx_flanger_fwd`` HIP
 kernel (one wavefront per clip, delay line in LDS) instead of 88 200 python iterations.
 ``apply_effect`` is differentiable (``mx_flanger_fwd_stash`` + ``mx_flanger_bwd``) when grad mode is on and an input
-requires grad.
+requires grad.  ``PhaserModule`` is the same for the phaser (``mx_phaser_fwd_stash`` + ``mx_phaser_bwd``), with the LFO
+either JUCE's built-in oscillator or an external signal.
 """
 from typing import Dict, Optional, Tuple, Union
 
@@ -295,3 +296,232 @@ def phaser_forward(src: T, params: Dict[str, T], lead: Optional[T], sr: float, n
               _hip.ptr(lead), _hip.ptr(rows), 0 if rows is None else rows.numel(), B, n_samples, float(sr),
               1 if exact_order else 0, yp, ys, dp, _hip.ptr(ws), ws_stride, _hip.stream())
     return y
+
+
+PHASER_PARAM_GRADS = ("depth", "centre_frequency_hz", "feedback", "mix")
+_PS_P, _PS_MV, _PS_SUB = 512, 57, 2                 # csrc/phaser_common.h
+
+
+def phaser_stash_shape(width: int) -> Tuple[int, int]:
+    """(stash_groups, floats per stash row) for source rows of ``width`` samples (csrc/phaser_common.h)."""
+    sg = ((width + 3) // 4 + 3) // 4 * 4
+    gpc = (sg + _PS_P - 1) // _PS_P
+    return sg, 4 * sg + _PS_P * _PS_MV + _PS_P * 8 * ((gpc + _PS_SUB - 1) // _PS_SUB)
+
+
+def phaser_forward_stash(src: T, params: Dict[str, T], lead: Optional[T], sr: float, n_samples: int,
+                         mod: Optional[T] = None, rows: Optional[T] = None, out: Optional[T] = None,
+                         dry_out: Optional[T] = None, stash: Optional[T] = None) -> Tuple[T, T]:
+    """Launch mx_phaser_fwd_stash: ``phaser_forward`` (the scan; same y and dry_out, bit for bit, when ``mod`` is None) that
+    also returns the stash ``phaser_backward`` needs.  mod (B, n_mod >= ceil(W / 4)) fp32 dense: an
+    external LFO in [0, 1], one value per cut-off update (4 samples), in the convention of the reference's phaser ground
+    truth ``make_mod_signal(.., pi / 2, "cos")`` (osc = 1 - 2 mod); params["rate_hz"] is then not needed.  lead + n_samples must not exceed
+    a source row (asserted here: the kernel would skip such a clip without an error)."""
+    B, W = src.shape
+    total = n_samples + (0 if lead is None else int(lead.max()))
+    assert total <= W, "lead + n_samples exceeds a source row (the kernel would leave such a clip alone)"
+    if mod is not None:
+        assert mod.size(1) >= (W + 3) // 4, "mod: one value per 4 samples of a source row (any lead fits)"
+    y = out if out is not None else torch.empty((B, n_samples), device=src.device, dtype=torch.float32)
+    sp, ss = _rows_view(src)
+    yp, ys = _rows_view(y)
+    dp = None
+    if dry_out is not None:
+        dp, ds = _rows_view(dry_out)
+        assert ds == ys
+    sg, row = phaser_stash_shape(W)
+    st = stash if stash is not None else torch.empty((B, row), device=src.device, dtype=torch.float32)
+    assert st.shape == (B, row) and st.dtype == torch.float32
+    if mod is not None:
+        assert mod.ndim == 2 and mod.size(0) == B and mod.dtype == torch.float32
+    _hip.call("mx_phaser_fwd_stash", sp, ss, W, _hip.ptr(mod), 0 if mod is None else mod.size(1),
+              _hip.ptr(params.get("rate_hz")), _hip.ptr(params["depth"]), _hip.ptr(params["centre_frequency_hz"]),
+              _hip.ptr(params["feedback"]), _hip.ptr(params["mix"]), _hip.ptr(lead), _hip.ptr(rows),
+              0 if rows is None else rows.numel(), B, n_samples, float(sr), yp, ys, dp, _hip.ptr(st), sg, row,
+              _hip.stream())
+    return y, st
+
+
+def phaser_backward(dy: T, src: T, stash: T, params: Dict[str, T], lead: Optional[T], sr: float, n_samples: int,
+                    rows: Optional[T] = None, need_dx: bool = True, need_dmod: bool = True,
+                    params_wanted: Tuple[str, ...] = PHASER_PARAM_GRADS, dx: Optional[T] = None,
+                    dmod: Optional[T] = None) -> Tuple[Optional[T], Optional[T], Dict[str, T]]:
+    """Launch mx_phaser_bwd: the adjoint of the phaser recurrence (the gradient the DESIGN K3b row defines).
+    dy (B, n_samples) and src (B, W) views with contiguous rows; stash from ``phaser_forward_stash`` on the same src, params,
+    lead.  Returns dx (B, W): the gradient with respect to every processed source sample, the lead included, zeros beyond
+    lead + n_samples; dmod (B, ceil(W / 4)): with respect to the external LFO (with the built-in oscillator: with respect to
+    (1 - osc) / 2) (both None unless asked for); and the per-clip fp64 gradients of the parameters named in
+    ``params_wanted``.  There is no gradient with respect to rate_hz."""
+    B, W = src.shape
+    dev = src.device
+    if dy.stride(-1) != 1 or dy.stride(0) < n_samples:      # e.g. the expanded ones of y.sum().backward()
+        dy = dy.contiguous()
+    assert dy.shape == (B, n_samples)
+    assert n_samples + (0 if lead is None else int(lead.max())) <= W, "lead + n_samples exceeds a source row"
+    n_mod = (W + 3) // 4
+    if need_dx and dx is None:
+        dx = torch.empty((B, W), device=dev, dtype=torch.float32)
+    if need_dmod and dmod is None:
+        dmod = torch.empty((B, n_mod), device=dev, dtype=torch.float32)
+    dxp, dxs = _rows_view(dx) if need_dx else (None, 0)
+    dmp, dms = _rows_view(dmod) if need_dmod else (None, 0)
+    assert not need_dx or dx.size(1) == W
+    assert not need_dmod or dmod.size(1) >= n_mod                 # every group of the longest possible clip
+    dyp, dys = _rows_view(dy)
+    sp, ss = _rows_view(src)
+    sg, row = phaser_stash_shape(W)
+    assert stash.shape == (B, row)
+    grads = {k: torch.zeros((B,), device=dev, dtype=torch.float64) for k in params_wanted}
+    _hip.call("mx_phaser_bwd", dyp, dys, sp, ss, W, _hip.ptr(stash), sg, row, _hip.ptr(params["depth"]),
+              _hip.ptr(params["centre_frequency_hz"]), _hip.ptr(params["feedback"]), _hip.ptr(params["mix"]),
+              _hip.ptr(lead), _hip.ptr(rows), 0 if rows is None else rows.numel(), B, n_samples, float(sr), dxp, dxs,
+              dmp, dms, dmod.size(1) if need_dmod else 0, *[_hip.ptr(grads.get(k)) for k in PHASER_PARAM_GRADS],
+              _hip.stream())
+    return (dx if need_dx else None), (dmod if need_dmod else None), grads
+
+
+class _PhaserFunction(torch.autograd.Function):
+    """y = phaser(x, mod | rate, parameters) over (clip, channel) rows; the (bs,) parameters are shared by a clip's n_ch
+    rows, so their gradients are summed over the channels (in fp64) before they are rounded to the parameters' dtype."""
+
+    @staticmethod
+    def forward(ctx, x, mod, rate, depth, centre, feedback, mix, lead, n_ch, sr, n):
+        def rows_of(v):
+            v = v.detach().float()
+            return (v.repeat_interleave(n_ch) if n_ch > 1 else v).contiguous()
+
+        params = {"depth": rows_of(depth), "centre_frequency_hz": rows_of(centre), "feedback": rows_of(feedback),
+                  "mix": rows_of(mix)}
+        if rate is not None:
+            params["rate_hz"] = rows_of(rate)
+        y, stash = phaser_forward_stash(x.detach(), params, lead, sr, n, mod=None if mod is None else mod.detach())
+        ctx.save_for_backward(x, stash)
+        ctx.params, ctx.lead, ctx.n_ch, ctx.sr, ctx.n, ctx.has_mod = params, lead, n_ch, sr, n, mod is not None
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        x, stash = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        wanted = tuple(k for k, n in zip(PHASER_PARAM_GRADS, need[3:7]) if n)
+        need_dmod = ctx.has_mod and need[1]
+        dx, dmod, g = phaser_backward(dy, x, stash, ctx.params, ctx.lead, ctx.sr, ctx.n, need_dx=need[0],
+                                      need_dmod=need_dmod, params_wanted=wanted)
+        out = [dx, dmod, None]
+        for k in PHASER_PARAM_GRADS:
+            out.append(g[k].view(-1, ctx.n_ch).sum(1).float() if k in g else None)
+        return tuple(out) + (None, None, None, None)
+
+
+def _check_phaser_param(param: Param, bs: int, lo: float, hi: float, lo_open: bool = False, hi_open: bool = False) -> None:
+    """Range check in the manner of ``_check_param``: a (bs,) tensor or a float inside [lo, hi] (open ends where said)."""
+    if isinstance(param, T):
+        assert param.shape == (bs,)
+        a, b = float(param.min()), float(param.max())
+    else:
+        a = b = float(param)
+    assert a > lo if lo_open else a >= lo
+    assert b < hi if hi_open else b <= hi
+
+
+class PhaserModule(nn.Module):
+    """The phaser of the data pipeline (pedalboard.Phaser = JUCE dsp::Phaser semantics, ``phaser_forward``) as a module in
+    the shape of ``MonoFlangerChorusModule``; the reference has no counterpart (its phaser is pedalboard's, on the CPU,
+    without a gradient).
+
+    x (bs, n_ch, lead + n): the channels are rows that share their clip's parameters.  ``lead`` warm-up samples are
+    processed before the n output samples (None: 0; an int; or a (bs,) integer tensor, n = width - max(lead)); the output
+    is (bs, n_ch, n).  Exactly one of ``mod_sig`` and ``rate_hz`` drives the cut-off:
+    * rate_hz (float or (bs,)): JUCE's built-in sine oscillator, phase 0 at sample 0;
+    * mod_sig, values in [0, 1], in the convention of the reference's phaser ground truth
+      ``make_mod_signal(.., pi / 2, "cos")`` = (1 + sin wt) / 2, so that JUCE's osc = 1 - 2 mod: (bs, ceil(width / 4)), one value per cut-off update, or full rate
+      (bs, width), which is sampled at samples 0, 4, 8, ...; optionally with a channel axis of 1 or n_ch.
+    depth, mix in [0, 1], feedback in (-1, 1) (JUCE's range), centre_frequency_hz > 0 (centres outside 20 Hz .. 20 kHz
+    clamp): python floats or (bs,) tensors.
+
+    ``forward`` runs under no_grad (bit-identical to ``phaser_forward`` when rate_hz is given).  ``apply_effect`` carries a
+    grad_fn when grad mode is on and x, mod_sig or a tensor parameter requires grad (``mx_phaser_fwd_stash`` forward,
+    ``mx_phaser_bwd`` backward); python-float parameters get no gradient.  There is deliberately NO gradient with respect
+    to rate_hz (a rate_hz that requires grad raises): the phase is tens of thousands of sequential fp32 additions with
+    wrap-around and its derivative with respect to the rate grows linearly in time, which is of no use to an optimiser; to
+    fit a rate, build the LFO in torch and pass it as mod_sig."""
+
+    def __init__(self, sr: float) -> None:
+        super().__init__()
+        self.sr = sr
+
+    def _prepare(self, x: T, mod_sig: Optional[T], rate_hz: Optional[Param], depth: Param, centre_frequency_hz: Param,
+                 feedback: Param, mix: Param, lead):
+        assert x.ndim == 3
+        bs, n_ch, W = x.shape
+        assert (mod_sig is None) != (rate_hz is None), "exactly one of mod_sig and rate_hz"
+        _check_phaser_param(depth, bs, 0.0, 1.0)
+        _check_phaser_param(mix, bs, 0.0, 1.0)
+        _check_phaser_param(feedback, bs, -1.0, 1.0, lo_open=True, hi_open=True)
+        _check_phaser_param(centre_frequency_hz, bs, 0.0, float("inf"), lo_open=True)
+        if isinstance(rate_hz, T) and rate_hz.requires_grad:
+            raise ValueError("PhaserModule has no gradient with respect to rate_hz: pass the LFO as mod_sig instead")
+        dev = x.device
+        rows = bs * n_ch
+        if lead is None:
+            lead_rows, n = None, W
+        elif isinstance(lead, T):
+            assert lead.shape == (bs,) and not lead.is_floating_point() and int(lead.min()) >= 0
+            n = W - int(lead.max())
+            lead_rows = lead.to(device=dev, dtype=torch.int32).repeat_interleave(n_ch).contiguous()
+        else:
+            assert 0 <= int(lead) < W
+            n = W - int(lead)
+            lead_rows = torch.full((rows,), int(lead), device=dev, dtype=torch.int32)
+        assert n > 0
+
+        def vec(p: Param) -> T:
+            if isinstance(p, T):
+                assert p.shape == (bs,)
+                return p.to(dev)
+            return torch.full((bs,), float(p), device=dev, dtype=torch.float32)
+
+        xr = x.reshape(rows, W).float()
+        if xr.stride(-1) != 1:
+            xr = xr.contiguous()
+        mr = None
+        if mod_sig is not None:
+            n_mod = (W + 3) // 4
+            assert mod_sig.size(0) == bs and mod_sig.ndim in (2, 3)
+            if mod_sig.ndim == 3:
+                assert mod_sig.size(1) in (1, n_ch)
+            if mod_sig.size(-1) != n_mod:
+                assert mod_sig.size(-1) == W, "mod_sig: one value per 4 samples or full rate"
+                mod_sig = mod_sig[..., ::4]                           # samples 0, 4, 8, ...: a slice autograd handles
+            if mod_sig.ndim == 2 or mod_sig.size(1) == 1:
+                mod_sig = mod_sig.reshape(bs, 1, n_mod).expand(-1, n_ch, -1)
+            mr = mod_sig.reshape(rows, n_mod).float().contiguous()
+        ps = (None if rate_hz is None else vec(rate_hz), vec(depth), vec(centre_frequency_hz), vec(feedback), vec(mix))
+        return xr, mr, ps, lead_rows, n, (bs, n_ch)
+
+    def apply_effect(self, x: T, mod_sig: Optional[T] = None, rate_hz: Optional[Param] = None, depth: Param = 1.0,
+                     centre_frequency_hz: Param = 1300.0, feedback: Param = 0.0, mix: Param = 1.0, lead=None) -> T:
+        params = (depth, centre_frequency_hz, feedback, mix)
+        if not (torch.is_grad_enabled() and (x.requires_grad or (mod_sig is not None and mod_sig.requires_grad) or
+                                             any(isinstance(p, T) and p.requires_grad for p in params))):
+            if isinstance(rate_hz, T) and rate_hz.requires_grad and torch.is_grad_enabled():
+                raise ValueError("PhaserModule has no gradient with respect to rate_hz: pass the LFO as mod_sig instead")
+            return self.forward(x, mod_sig, rate_hz, depth, centre_frequency_hz, feedback, mix, lead)
+        xr, mr, ps, lead_rows, n, (bs, n_ch) = self._prepare(x, mod_sig, rate_hz, *params, lead)
+        y = _PhaserFunction.apply(xr, mr, *ps, lead_rows, n_ch, self.sr, n)
+        return y.view(bs, n_ch, n)
+
+    def forward(self, x: T, mod_sig: Optional[T] = None, rate_hz: Optional[Param] = None, depth: Param = 1.0,
+                centre_frequency_hz: Param = 1300.0, feedback: Param = 0.0, mix: Param = 1.0, lead=None) -> T:
+        with torch.no_grad():
+            xr, mr, ps, lead_rows, n, (bs, n_ch) = self._prepare(x, mod_sig, rate_hz, depth, centre_frequency_hz, feedback,
+                                                                 mix, lead)
+            rows_of = lambda v: (v.float().repeat_interleave(n_ch) if n_ch > 1 else v.float()).contiguous()
+            p = {k: rows_of(v) for k, v in zip(("rate_hz", "depth", "centre_frequency_hz", "feedback", "mix"), ps)
+                 if v is not None}
+            if mr is None:
+                y = phaser_forward(xr, p, lead_rows, self.sr, n)
+            else:
+                y, _ = phaser_forward_stash(xr, p, lead_rows, self.sr, n, mod=mr)
+        return y.view(bs, n_ch, n)
