@@ -22,17 +22,8 @@
 // Results are bit-identical to the reference for identical mod_sig input.
 // Algorithmic HBM traffic: 12 B/sample (x, mod in; y out), 8 B/sample with the 882-point LFO
 // resampled in-kernel (util.py:15-29).
-#include "common.h"
+#include "flanger_common.h"     // FL_V, the chunk / ring geometry, fl_slots, fl_dist, fl_run_masks, the slot word
 
-#ifndef FL_V
-#define FL_V 8                 // rows of 64 samples per chunk (4: 0.58 of the independent floor on config 3, 6: 0.60, 8: 0.62 -- the per-chunk barrier and the consumer's record loads amortise over more rows; 12 would need 132 consumer registers)
-#endif
-#define FL_CHUNK (64 * FL_V)
-#define FL_SLOT_FLOATS (FL_CHUNK * 6 + 2 * FL_V)          // FL_CHUNK float4 records, FL_CHUNK 64-bit lane masks (run r of a row in lane r), FL_V run counts
-#define FL_RING_FLOATS (2 * FL_SLOT_FLOATS)
-#define FL_MAX_M (40960 - FL_RING_FLOATS)                // 160 KB LDS = 40960 floats, minus the ring
-
-#define FL_THREADS (64 * (1 + FL_V))   // consumer wave + one producer wave per row of a chunk
 __device__ __forceinline__ unsigned lds_byte_addr(const float *p) {
     return (unsigned)(size_t)(__attribute__((address_space(3))) const float *)p;
 }
@@ -63,7 +54,6 @@ __global__ __launch_bounds__(FL_THREADS) void flanger_kernel(
     const float *mb = mod + (size_t)b * n_mod;
     float *yb = y + (size_t)b * y_stride;
     float *ring = buf + ring_off;                              // slot s at ring + s * FL_SLOT_FLOATS
-    constexpr int SLOT = FL_SLOT_FLOATS;
 
     for (int i = threadIdx.x; i < M; i += FL_THREADS) buf[i] = 0.0f;  // fx.py:92
     const bool resample = (n_mod != N);
@@ -84,9 +74,7 @@ __global__ __launch_bounds__(FL_THREADS) void flanger_kernel(
     // records of row pw of chunk c -> ring slot c & 1
     auto build = [&](int c) {
         const int c0 = c * FL_CHUNK, j = pw;
-        float4 *rec = reinterpret_cast<float4 *>(ring + (c & 1) * SLOT);
-        unsigned long long *run_mask = reinterpret_cast<unsigned long long *>(ring + (c & 1) * SLOT + 4 * FL_CHUNK);
-        int *n_runs = reinterpret_cast<int *>(ring + (c & 1) * SLOT + 6 * FL_CHUNK);
+        const FlSlot slot = fl_slot(ring, c);
         float xn, mn;
         {                                                      // prefetch chunk c + 1
             const int n = c0 + FL_CHUNK + j * 64 + lane;
@@ -106,41 +94,19 @@ __global__ __launch_bounds__(FL_THREADS) void flanger_kernel(
             }
             int w = w_chunk + j * 64 + lane;                   // fx.py:95: n % M without a division
             while (w >= M) w -= M;
-            const float d = __fadd_rn(__fmul_rn(ls, m), md);   // fx.py:99
-            const float r1 = __fadd_rn(__fsub_rn((float)w, d), Mf);  // fx.py:100
-            float r;
-            if (r1 >= 0.0f && r1 < Mf) r = r1;                 // fmod is the identity here
-            else if (r1 >= Mf && r1 < __fadd_rn(Mf, Mf)) r = __fsub_rn(r1, Mf);  // exact (Sterbenz)
-            else r = torch_remainderf(r1, Mf);                 // out-of-contract mod_sig: generic path
-            const float fl = floorf(r);
-            int prev = (int)fl;                                // fx.py:102
-            if (prev < 0) prev = 0;                            // NaN / garbage guard (never hit in contract)
-            if (prev >= M) prev = M - 1;
-            const int next = prev + 1 == M ? 0 : prev + 1;     // fx.py:103
-            const float frac = __fsub_rn(r, fl);               // fx.py:101
-            int dp_ = w - prev; if (dp_ <= 0) dp_ += M;        // slot w itself is "M samples ago"
-            int dn_ = w - next; if (dn_ <= 0) dn_ += M;
-            const int dep = valid ? min(dp_, dn_) : 0x7fffffff;
+            int prev, next;
+            float frac;
+            fl_slots(w, m, ls, md, M, Mf, prev, next, frac);   // fx.py:99-103
+            const int dep = valid ? min(fl_dist(w, prev, M), fl_dist(w, next, M)) : 0x7fffffff;
             if (dbg_prev && valid) dbg_prev[(size_t)b * N + n] = prev;
             if (dbg_frac && valid) dbg_frac[(size_t)b * N + n] = frac;
-            // record: x, frac, 1 - frac (fx.py:113, rounded here exactly as there), slots (w | prev << 16; M < 65536)
-            rec[j * 64 + lane] = make_float4(xr, frac, __fsub_rn(1.0f, frac), __int_as_float(w | (prev << 16)));
-            // maximal dependency-free runs of the row: the run starting at a ends in front of the first k >= a whose
-            // newest dependency t[k] = k - dep[k] is inside the run (t[k] >= a).  dep >= 1, so every run is non-empty.
+            // record: x, frac, 1 - frac (fx.py:113, rounded here exactly as there), the slot word
+            slot.rec[j * 64 + lane] = make_float4(xr, frac, __fsub_rn(1.0f, frac), fl_pack(w, prev));
+            // the row's maximal dependency-free runs: the newest dependency of sample k is t[k] = k - dep[k] (dep >= 1)
             const int tk = dep > lane ? -1 : lane - dep;
-            // Lane r keeps the lane mask of run r (lanes [a, bnd) as a 64-bit exec image): the consumer fetches a step's mask
-            // with two v_readlane instead of deriving it.
-            unsigned long long mine = 0ull;
-            int a = 0, run = 0;
-            while (a < 64) {
-                const unsigned long long conflict = __ballot(lane >= a && tk >= a);
-                const int bnd = conflict ? (int)__builtin_ctzll(conflict) : 64;
-                if (lane == run) mine = (~0ull << a) & (~0ull >> (64 - bnd));
-                a = bnd;
-                ++run;
-            }
-            run_mask[j * 64 + lane] = mine;
-            if (lane == 0) n_runs[j] = run;
+            int run;
+            slot.run_mask[j * 64 + lane] = fl_run_masks(lane, tk, ~0ull, run);
+            if (lane == 0) slot.n_runs[j] = run;
         }
         xr = xn;
         mr = mn;
@@ -155,12 +121,10 @@ __global__ __launch_bounds__(FL_THREADS) void flanger_kernel(
             if (c + 1 < n_chunks) build(c + 1);
         } else {
             const int c0 = c * FL_CHUNK;
-            const float4 *rec = reinterpret_cast<const float4 *>(ring + (c & 1) * SLOT);
-            const unsigned long long *run_mask = reinterpret_cast<const unsigned long long *>(ring + (c & 1) * SLOT + 4 * FL_CHUNK);
-            const int *n_runs = reinterpret_cast<const int *>(ring + (c & 1) * SLOT + 6 * FL_CHUNK);
+            const FlSlot slot = fl_slot(ring, c);
             float4 rc[FL_V];
 #pragma unroll
-            for (int j = 0; j < FL_V; ++j) rc[j] = rec[j * 64 + lane];
+            for (int j = 0; j < FL_V; ++j) rc[j] = slot.rec[j * 64 + lane];
             // everything a row needs from LDS and the slot arithmetic, for all four rows, BEFORE the first lock-step loop (the
             // loops are opaque to the compiler and fence memory: whatever is left between two of them is serial time)
             unsigned m_lo_[FL_V], m_hi_[FL_V];
@@ -168,11 +132,11 @@ __global__ __launch_bounds__(FL_THREADS) void flanger_kernel(
             unsigned a_prev_[FL_V], a_next_[FL_V], a_w_[FL_V];
 #pragma unroll
             for (int j = 0; j < FL_V; ++j) {
-                const int pk = __float_as_int(rc[j].w), w = pk & 0xffff, prev = (pk >> 16) & 0xffff;
-                const int next = prev + 1 == M ? 0 : prev + 1;
-                const unsigned long long m64 = run_mask[j * 64 + lane];
+                int w, prev, next;
+                fl_unpack(rc[j].w, M, w, prev, next);
+                const unsigned long long m64 = slot.run_mask[j * 64 + lane];
                 m_lo_[j] = (unsigned)m64; m_hi_[j] = (unsigned)(m64 >> 32);
-                n_runs_[j] = __builtin_amdgcn_readfirstlane(n_runs[j]);
+                n_runs_[j] = __builtin_amdgcn_readfirstlane(slot.n_runs[j]);
                 a_prev_[j] = lds_byte_addr(buf + prev); a_next_[j] = lds_byte_addr(buf + next); a_w_[j] = lds_byte_addr(buf + w);
             }
             float o[FL_V];
@@ -264,12 +228,13 @@ __global__ __launch_bounds__(FL_THREADS) void flanger_kernel(
 // one batch); rows: optional list of n_rows clip indices to process (others untouched).
 // Optional outputs: mod_up (B,N) resampled LFO; dbg_prev (B,N) int64 / dbg_frac (B,N) for the
 // index-parity tests.
+template <bool STASH>
 static int flanger_fwd_launch(const float *x, int64_t x_stride, const float *mod, int64_t n_mod, const float *lfo_scale,
                              const float *min_delay, const float *feedback, const float *depth,
                              const float *mix, const float *one_minus_mix, const int32_t *max_delay,
                              int32_t max_delay_max, const int32_t *rows, int64_t n_rows, int64_t B,
                              int64_t N, float *y, int64_t y_stride, float *mod_up, int64_t *dbg_prev, float *dbg_frac,
-                             void *stream, int probe, float *stash = nullptr)
+                             void *stream, int probe, float *stash)
 {
     if (!x || !mod || !lfo_scale || !min_delay || !feedback || !depth || !mix || !one_minus_mix ||
         !max_delay || !y || B <= 0 || N <= 0 || n_mod <= 0)
@@ -278,15 +243,6 @@ static int flanger_fwd_launch(const float *x, int64_t x_stride, const float *mod
     if (max_delay_max > FL_MAX_M || max_delay_max > 65535 || N >= (1ll << 30)) return MX_ERR_UNSUPPORTED;
     const int64_t items = rows ? n_rows : B;
     if (items <= 0) return MX_OK;
-    static bool attr_set[2][64] = {};                    // per kernel and device: one process may drive several GPUs
-    const void *kern = stash ? (const void *)flanger_kernel<true> : (const void *)flanger_kernel<false>;
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= 64 || !attr_set[stash != nullptr][dev]) {
-        (void)hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (FL_MAX_M + FL_RING_FLOATS) * sizeof(float));
-        if (dev >= 0 && dev < 64) attr_set[stash != nullptr][dev] = true;
-    }
     // LDS: delay line (max over the batch) + the LFO row when it is resampled in-kernel (n_mod < N) + the record ring
     const int lfo_off = max_delay_max;
     size_t lds_floats = (size_t)max_delay_max + (n_mod != N ? (size_t)n_mod : 0);
@@ -294,16 +250,13 @@ static int flanger_fwd_launch(const float *x, int64_t x_stride, const float *mod
     const int ring_off = (int)lds_floats;
     if (lds_floats > FL_MAX_M) return MX_ERR_UNSUPPORTED;
     const size_t lds = (lds_floats + FL_RING_FLOATS) * sizeof(float);
-    if (stash)
-        hipLaunchKernelGGL(flanger_kernel<true>, dim3((unsigned)items), dim3(FL_THREADS), lds, (hipStream_t)stream, x,
-                           (long long)x_stride, mod, (int)n_mod, interp_scale_host(n_mod, N), lfo_scale, min_delay, feedback,
-                           depth, mix, one_minus_mix, max_delay, rows, (int)N, lfo_off, ring_off, y, (long long)y_stride,
-                           mod_up, (long long *)dbg_prev, dbg_frac, probe, stash);
-    else
-        hipLaunchKernelGGL(flanger_kernel<false>, dim3((unsigned)items), dim3(FL_THREADS), lds, (hipStream_t)stream, x, (long long)x_stride, mod,
-                           (int)n_mod, interp_scale_host(n_mod, N), lfo_scale, min_delay, feedback, depth,
-                           mix, one_minus_mix, max_delay, rows, (int)N, lfo_off, ring_off, y, (long long)y_stride, mod_up,
-                           (long long *)dbg_prev, dbg_frac, probe, (float *)nullptr);
+    static MxLdsLatch latch = {};                                  // one per instance of this template = per kernel
+    if (mx_set_dyn_lds(latch, (const void *)flanger_kernel<STASH>, (FL_MAX_M + FL_RING_FLOATS) * sizeof(float)) != MX_OK)
+        return MX_ERR_LAUNCH;
+    hipLaunchKernelGGL(flanger_kernel<STASH>, dim3((unsigned)items), dim3(FL_THREADS), lds, (hipStream_t)stream, x,
+                       (long long)x_stride, mod, (int)n_mod, interp_scale_host(n_mod, N), lfo_scale, min_delay, feedback,
+                       depth, mix, one_minus_mix, max_delay, rows, (int)N, lfo_off, ring_off, y, (long long)y_stride,
+                       mod_up, (long long *)dbg_prev, dbg_frac, probe, stash);
     return mx_launch_status();
 }
 
@@ -314,7 +267,7 @@ MX_EXPORT int mx_flanger_fwd(const float *x, int64_t x_stride, const float *mod,
                              int64_t N, float *y, int64_t y_stride, float *mod_up, int64_t *dbg_prev, float *dbg_frac,
                              void *stream)
 {
-    return flanger_fwd_launch(x, x_stride, mod, n_mod, lfo_scale, min_delay, feedback, depth, mix, one_minus_mix, max_delay, max_delay_max, rows, n_rows, B, N, y, y_stride, mod_up, dbg_prev, dbg_frac, stream, 0);
+    return flanger_fwd_launch<false>(x, x_stride, mod, n_mod, lfo_scale, min_delay, feedback, depth, mix, one_minus_mix, max_delay, max_delay_max, rows, n_rows, B, N, y, y_stride, mod_up, dbg_prev, dbg_frac, stream, 0, nullptr);
 }
 
 // Measurement twin (bench.py's serial floor): the SAME launch with no global-memory traffic inside the sample loop -- inputs are constants, only the last chunk is stored.  Results are meaningless; nothing in the product calls it.
@@ -325,7 +278,7 @@ MX_EXPORT int mx_flanger_fwd_probe(const float *x, int64_t x_stride, const float
                              int64_t N, float *y, int64_t y_stride, float *mod_up, int64_t *dbg_prev, float *dbg_frac,
                              void *stream)
 {
-    return flanger_fwd_launch(x, x_stride, mod, n_mod, lfo_scale, min_delay, feedback, depth, mix, one_minus_mix, max_delay, max_delay_max, rows, n_rows, B, N, y, y_stride, mod_up, dbg_prev, dbg_frac, stream, 1);
+    return flanger_fwd_launch<false>(x, x_stride, mod, n_mod, lfo_scale, min_delay, feedback, depth, mix, one_minus_mix, max_delay, max_delay_max, rows, n_rows, B, N, y, y_stride, mod_up, dbg_prev, dbg_frac, stream, 1, nullptr);
 }
 
 // Forward of the adjoint (flanger_bwd.hip): mx_flanger_fwd plus the tap v[n] of every sample in stash (B,N), dense rows.
@@ -338,8 +291,8 @@ MX_EXPORT int mx_flanger_fwd_stash(const float *x, int64_t x_stride, const float
 {
     if (!stash) return MX_ERR_ARG;
     if (n_mod != N) return MX_ERR_UNSUPPORTED;
-    return flanger_fwd_launch(x, x_stride, mod, n_mod, lfo_scale, min_delay, feedback, depth, mix, one_minus_mix, max_delay,
-                              max_delay_max, rows, n_rows, B, N, y, y_stride, nullptr, nullptr, nullptr, stream, 0, stash);
+    return flanger_fwd_launch<true>(x, x_stride, mod, n_mod, lfo_scale, min_delay, feedback, depth, mix, one_minus_mix, max_delay,
+                                    max_delay_max, rows, n_rows, B, N, y, y_stride, nullptr, nullptr, nullptr, stream, 0, stash);
 }
 
 // ---- measurement aid: the LDS round trip of one lock-step -------------------------------------------------------------

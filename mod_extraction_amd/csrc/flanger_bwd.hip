@@ -11,7 +11,7 @@
 //   d feedback = sum g_d v, d depth = sum g_o v, d mix = sum g_z (o - x), d lfo_scale = -sum g_f mod, d min_delay = -sum g_f
 //
 // Two launches.
-//  1. fb_recur_kernel -- the serial part, g_d.  One workgroup = one clip = a consumer wave + FB_V producer waves, as in
+//  1. fb_recur_kernel -- the serial part, g_d.  One workgroup = one clip = a consumer wave + FL_V producer waves, as in
 //     the forward, walking the clip BACKWARDS in chunks of 512 samples.  An LDS accumulator A[M] is indexed like the
 //     delay line: A[s] holds the gradient already sent to the value slot s currently holds.  Reverse of one sample
 //     (read prev / next, then write w): g_d = A[w], A[w] = 0; then A[prev] += (1-f) g_v, A[next] += f g_v.  The forward's
@@ -24,42 +24,9 @@
 //  2. fb_out_kernel -- everything else is independent per sample: one workgroup per clip recomputes the slots, z and the
 //     two values d read (x and the stash at most M samples back, L2-resident), writes dx and dmod, and sums the five
 //     parameter partials in fp64 in a fixed order (per thread, then a butterfly, then the waves in order).
-#include "common.h"
+#include "flanger_common.h"     // the forward's geometry, fl_slots, fl_dist, fl_run_masks, the slot word
 
-#define FB_V 8                                           // rows of 64 samples per chunk (the forward's FL_V)
-#define FB_CHUNK (64 * FB_V)
-#define FB_SLOT_FLOATS (FB_CHUNK * 6 + 2 * FB_V)         // FB_CHUNK float4 records, FB_CHUNK 64-bit run masks, FB_V run counts
-#define FB_RING_FLOATS (2 * FB_SLOT_FLOATS)
-#define FB_MAX_M (40960 - FB_RING_FLOATS)                // the forward's FL_MAX_M: 160 KB LDS minus the ring
-#define FB_THREADS (64 * (1 + FB_V))
 #define FB_OUT_THREADS 512
-
-// fx.py:95-103 for one sample, exactly as flanger.hip's producers evaluate it (fp32, no contraction): write slot w = n % M,
-// read slots prev / next and the read fraction.
-__device__ __forceinline__ void fb_slots(int w, float m, float ls, float md, int M, float Mf, int &prev, int &next,
-                                         float &frac)
-{
-    const float d = __fadd_rn(__fmul_rn(ls, m), md);                    // fx.py:99
-    const float r1 = __fadd_rn(__fsub_rn((float)w, d), Mf);             // fx.py:100
-    float r;
-    if (r1 >= 0.0f && r1 < Mf) r = r1;
-    else if (r1 >= Mf && r1 < __fadd_rn(Mf, Mf)) r = __fsub_rn(r1, Mf);
-    else r = torch_remainderf(r1, Mf);
-    const float fl = floorf(r);
-    int p = (int)fl;                                                    // fx.py:102
-    if (p < 0) p = 0;
-    if (p >= M) p = M - 1;
-    prev = p;
-    next = p + 1 == M ? 0 : p + 1;                                      // fx.py:103
-    frac = __fsub_rn(r, fl);                                            // fx.py:101
-}
-
-// distance back from the write at slot w to the last write of slot s (slot w itself: M samples ago)
-__device__ __forceinline__ int fb_dist(int w, int s, int M)
-{
-    int d = w - s;
-    return d <= 0 ? d + M : d;
-}
 
 // the forward's output z (fx.py:115-117, before the clip) and o, recomputed bit-exactly from x and the tap
 __device__ __forceinline__ float fb_z(float xv, float v, float dp, float mx, float omm, float &o)
@@ -68,7 +35,7 @@ __device__ __forceinline__ float fb_z(float xv, float v, float dp, float mx, flo
     return __fadd_rn(__fmul_rn(omm, xv), __fmul_rn(mx, o));
 }
 
-__global__ __launch_bounds__(FB_THREADS) void fb_recur_kernel(
+__global__ __launch_bounds__(FL_THREADS) void fb_recur_kernel(
     const float *__restrict__ dy, long long dy_stride, const float *__restrict__ x, long long x_stride,
     const float *__restrict__ mod, const float *__restrict__ stash, const float *__restrict__ lfo_scale,
     const float *__restrict__ min_delay, const float *__restrict__ feedback, const float *__restrict__ depth,
@@ -90,15 +57,14 @@ __global__ __launch_bounds__(FB_THREADS) void fb_recur_kernel(
     const float *sb = stash + (size_t)b * N;
     float *gb = gd_out + (size_t)b * N;
     float *ring = buf + ring_off;
-    constexpr int SLOT = FB_SLOT_FLOATS;
 
-    for (int i = threadIdx.x; i < M; i += FB_THREADS) buf[i] = 0.0f;
+    for (int i = threadIdx.x; i < M; i += FL_THREADS) buf[i] = 0.0f;
 
-    const int n_chunks = (N + FB_CHUNK - 1) / FB_CHUNK;
+    const int n_chunks = (N + FL_CHUNK - 1) / FL_CHUNK;
     // producer: inputs of the chunk it builds next, loaded one chunk ahead
     float xr = 0.0f, mr = 0.0f, vr = 0.0f, gr = 0.0f;
     auto load = [&](int c) {
-        const int n = c * FB_CHUNK + pw * 64 + lane;
+        const int n = c * FL_CHUNK + pw * 64 + lane;
         const bool ok = c >= 0 && n < N;
         xr = ok ? xb[n] : 0.0f;
         mr = ok ? mb[n] : 0.0f;
@@ -108,23 +74,21 @@ __global__ __launch_bounds__(FB_THREADS) void fb_recur_kernel(
     // records of row pw of chunk c -> ring slot c & 1: {depth g_o, f, 1 - f, w | prev << 16} and the lane masks of the
     // row's lock-steps (run r in lane r)
     auto build = [&](int c) {
-        const int n = c * FB_CHUNK + pw * 64 + lane;
-        float4 *rec = reinterpret_cast<float4 *>(ring + (c & 1) * SLOT);
-        unsigned long long *run_mask = reinterpret_cast<unsigned long long *>(ring + (c & 1) * SLOT + 4 * FB_CHUNK);
-        int *n_runs = reinterpret_cast<int *>(ring + (c & 1) * SLOT + 6 * FB_CHUNK);
+        const int n = c * FL_CHUNK + pw * 64 + lane;
+        const FlSlot slot = fl_slot(ring, c);
         const float xv = xr, m = mr, v = vr, g = gr;
         load(c - 1);
         const bool valid = n < N;
         const int w = valid ? n % M : 0;
         int prev, next;
         float frac;
-        fb_slots(w, m, ls, md, M, Mf, prev, next, frac);
+        fl_slots(w, m, ls, md, M, Mf, prev, next, frac);
         float o;
         const float z = fb_z(xv, v, dp, mx, omm, o);
         const float gz = (z >= -1.0f && z <= 1.0f) ? g : 0.0f;         // clamp's backward: inclusive bounds
         const float gvo = valid ? __fmul_rn(dp, __fmul_rn(mx, gz)) : 0.0f;
-        rec[pw * 64 + lane] = make_float4(gvo, frac, __fsub_rn(1.0f, frac), __int_as_float(w | (prev << 16)));
-        const int dpr = fb_dist(w, prev, M), dnx = fb_dist(w, next, M);
+        slot.rec[pw * 64 + lane] = make_float4(gvo, frac, __fsub_rn(1.0f, frac), fl_pack(w, prev));
+        const int dpr = fl_dist(w, prev, M), dnx = fl_dist(w, next, M);
         const int dep = min(dpr, dnx);
         int tk = !valid || dep > lane ? -1 : lane - dep;               // newest sample of this row the reads depend on
         // ages of the two values read; inside a dependency-free run equal slots <=> equal ages: split where an age does
@@ -132,18 +96,9 @@ __global__ __launch_bounds__(FB_THREADS) void fb_recur_kernel(
         const int age_p = n - dpr, age_n = n - dnx;
         const int age_p1 = __shfl_up(age_p, 1, 64), age_n1 = __shfl_up(age_n, 1, 64);
         if (valid && lane > 0 && (age_p <= age_p1 || age_n <= age_n1)) tk = max(tk, lane - 1);
-        const unsigned long long live = __ballot(valid);
-        unsigned long long mine = 0ull;
-        int a = 0, run = 0;
-        while (a < 64) {
-            const unsigned long long conflict = __ballot(lane >= a && tk >= a);
-            const int bnd = conflict ? (int)__builtin_ctzll(conflict) : 64;
-            if (lane == run) mine = (~0ull << a) & (~0ull >> (64 - bnd)) & live;
-            a = bnd;
-            ++run;
-        }
-        run_mask[pw * 64 + lane] = mine;
-        if (lane == 0) n_runs[pw] = run;
+        int run;
+        slot.run_mask[pw * 64 + lane] = fl_run_masks(lane, tk, __ballot(valid), run);
+        if (lane == 0) slot.n_runs[pw] = run;
     };
 
     if (producer) {
@@ -155,18 +110,16 @@ __global__ __launch_bounds__(FB_THREADS) void fb_recur_kernel(
         if (producer) {
             if (c > 0) build(c - 1);
         } else {
-            const float4 *rec = reinterpret_cast<const float4 *>(ring + (c & 1) * SLOT);
-            const unsigned long long *run_mask = reinterpret_cast<const unsigned long long *>(ring + (c & 1) * SLOT + 4 * FB_CHUNK);
-            const int *n_runs = reinterpret_cast<const int *>(ring + (c & 1) * SLOT + 6 * FB_CHUNK);
-            float gd_[FB_V];
+            const FlSlot slot = fl_slot(ring, c);
+            float gd_[FL_V];
 #pragma unroll
-            for (int j = FB_V - 1; j >= 0; --j) {
-                const float4 rc = rec[j * 64 + lane];
-                const unsigned long long m64 = run_mask[j * 64 + lane];
+            for (int j = FL_V - 1; j >= 0; --j) {
+                const float4 rc = slot.rec[j * 64 + lane];
+                const unsigned long long m64 = slot.run_mask[j * 64 + lane];
                 const unsigned m_lo = (unsigned)m64, m_hi = (unsigned)(m64 >> 32);
-                const int nr = __builtin_amdgcn_readfirstlane(n_runs[j]);
-                const int pk = __float_as_int(rc.w), w = pk & 0xffff, prev = (pk >> 16) & 0xffff;
-                const int next = prev + 1 == M ? 0 : prev + 1;
+                const int nr = __builtin_amdgcn_readfirstlane(slot.n_runs[j]);
+                int w, prev, next;
+                fl_unpack(rc.w, M, w, prev, next);
                 const float gvo = rc.x, frac = rc.y, omf = rc.z;
                 float gd = 0.0f;
                 for (int r = nr - 1; r >= 0; --r) {
@@ -185,8 +138,8 @@ __global__ __launch_bounds__(FB_THREADS) void fb_recur_kernel(
                 gd_[j] = gd;
             }
 #pragma unroll
-            for (int j = 0; j < FB_V; ++j) {
-                const int n = c * FB_CHUNK + j * 64 + lane;
+            for (int j = 0; j < FL_V; ++j) {
+                const int n = c * FL_CHUNK + j * 64 + lane;
                 if (n < N) gb[n] = gd_[j];
             }
         }
@@ -219,14 +172,14 @@ __global__ __launch_bounds__(FB_OUT_THREADS) void fb_out_kernel(
         const int w = n % M;
         int prev, next;
         float frac;
-        fb_slots(w, m, ls, md, M, Mf, prev, next, frac);
+        fl_slots(w, m, ls, md, M, Mf, prev, next, frac);
         float o;
         const float z = fb_z(xv, v, dp, mx, omm, o);
         const double gz = (z >= -1.0f && z <= 1.0f) ? (double)g : 0.0;
         const double go = (double)mx * gz;
         const double gv = (double)dp * go + (double)fb * (double)gd;
         // the two values the reads of step n saw: d of the last write of each slot before n (0 if never written)
-        const int mp = n - fb_dist(w, prev, M), mn = n - fb_dist(w, next, M);
+        const int mp = n - fl_dist(w, prev, M), mn = n - fl_dist(w, next, M);
         const float d_p = mp >= 0 ? __fadd_rn(xb[mp], __fmul_rn(fb, sb[mp])) : 0.0f;
         const float d_n = mn >= 0 ? __fadd_rn(xb[mn], __fmul_rn(fb, sb[mn])) : 0.0f;
         const double gf = gv * ((double)d_n - (double)d_p);
@@ -269,20 +222,15 @@ MX_EXPORT int mx_flanger_bwd(const float *dy, int64_t dy_stride, const float *x,
         return MX_ERR_ARG;
     if (max_delay_max < 2 || dy_stride < N || x_stride < N || (dx && dx_stride < N) || (dmod && dmod_stride < N))
         return MX_ERR_ARG;
-    if (max_delay_max > FB_MAX_M || max_delay_max > 65535 || N >= (1ll << 30)) return MX_ERR_UNSUPPORTED;
+    if (max_delay_max > FL_MAX_M || max_delay_max > 65535 || N >= (1ll << 30)) return MX_ERR_UNSUPPORTED;
     const int64_t items = rows ? n_rows : B;
     if (items <= 0) return MX_OK;
-    static bool attr_set[64] = {};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= 64 || !attr_set[dev]) {
-        (void)hipFuncSetAttribute((const void *)fb_recur_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (FB_MAX_M + FB_RING_FLOATS) * sizeof(float));
-        if (dev >= 0 && dev < 64) attr_set[dev] = true;
-    }
+    static MxLdsLatch latch = {};
+    if (mx_set_dyn_lds(latch, (const void *)fb_recur_kernel, (FL_MAX_M + FL_RING_FLOATS) * sizeof(float)) != MX_OK)
+        return MX_ERR_LAUNCH;
     const int ring_off = (max_delay_max + 3) & ~3;                      // the ring holds float4 records
-    const size_t lds = ((size_t)ring_off + FB_RING_FLOATS) * sizeof(float);
-    hipLaunchKernelGGL(fb_recur_kernel, dim3((unsigned)items), dim3(FB_THREADS), lds, (hipStream_t)stream, dy,
+    const size_t lds = ((size_t)ring_off + FL_RING_FLOATS) * sizeof(float);
+    hipLaunchKernelGGL(fb_recur_kernel, dim3((unsigned)items), dim3(FL_THREADS), lds, (hipStream_t)stream, dy,
                        (long long)dy_stride, x, (long long)x_stride, mod, stash, lfo_scale, min_delay, feedback, depth, mix,
                        one_minus_mix, max_delay, rows, (int)N, ring_off, ws);
     int rc = mx_launch_status();

@@ -570,15 +570,9 @@ static int run_onepass(const float *x, long long xs, const float *y, long long y
     float *main1 = ws, *main2 = main1 + (size_t)B * n_frames * hop, *tails = main2 + (size_t)B * n_frames * hop;
     const long long count = (long long)B * n_frames * (N / 2 + 1);
     const float c_log = (float)((double)res_scale * w_log / (double)count);
-    static bool attr_set[64];
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= 64 || !attr_set[dev]) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(&mr_onepass_kernel<N>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)OP<N>::lds_bytes()) != hipSuccess)
-            return MX_ERR_LAUNCH;
-        if (dev >= 0 && dev < 64) attr_set[dev] = true;
-    }
+    static MxLdsLatch latch = {};                              // one per N, as the kernel is
+    if (mx_set_dyn_lds(latch, reinterpret_cast<const void *>(&mr_onepass_kernel<N>), OP<N>::lds_bytes()) != MX_OK)
+        return MX_ERR_LAUNCH;
     hipLaunchKernelGGL((mr_onepass_kernel<N>), dim3(groups, B), dim3(MR_OPW * 64), OP<N>::lds_bytes(), st, x, xs, y, ys, win, tw, T,
                        hop, n_frames, F, n_runs, eps, c_log, part, main1, main2, tails);
     hipLaunchKernelGGL(mr_finish_kernel, dim3(1), dim3(256), 0, st, part, groups * B, count, w_sc, w_log, res_scale, terms, alpha);

@@ -14,10 +14,8 @@
 #include "phaser_common.h"
 
 #define PH_BLOCK 256
-#ifndef PH_WPB
 #define PH_WPB 4          // clips (wavefronts) per workgroup: packs the long-running serial chains onto few CUs so
                           // that the 1-workgroup-per-CU matrix kernels of the train step keep the other CUs
-#endif
 
 __global__ __launch_bounds__(64 * PH_WPB) void phaser_kernel(const float *__restrict__ x, long long x_stride,
                                                     const float *__restrict__ rate,
@@ -26,7 +24,7 @@ __global__ __launch_bounds__(64 * PH_WPB) void phaser_kernel(const float *__rest
                                                     const float *__restrict__ feedback,
                                                     const float *__restrict__ mix,
                                                     const int *__restrict__ lead_arr,
-                                                    const int *__restrict__ rows, int n_items, int N, float sr_f,
+                                                    const int *__restrict__ rows, int n_items, int N,
                                                     double sr, float *__restrict__ y, long long y_stride,
                                                     float *__restrict__ dry_out)
 {
@@ -40,19 +38,10 @@ __global__ __launch_bounds__(64 * PH_WPB) void phaser_kernel(const float *__rest
     float *yb = y + (size_t)b * y_stride;
     float *db = dry_out ? dry_out + (size_t)b * y_stride : nullptr;
 
-    const float two_pi = 6.283185307179586476925286766559f;
-    const float pi_f = 3.14159265358979323846f;
-    const float fmax_hz = (float)fmin(20000.0, 0.49 * sr);
-    const float log_min = (float)log10(20.0), log_max = (float)log10((double)fmax_hz);
-    const float inc = __fmul_rn(__fdiv_rn(two_pi, (float)(sr / 4.0)), rate[b]);
-    const float norm_centre = __fdiv_rn(__fsub_rn((float)log10((double)centre[b]), log_min), __fsub_rn(log_max, log_min));
-    const float osc_vol = __fmul_rn(depth[b], 0.5f);
-    const float fb = feedback[b];
-    const float wet_g = mix[b], dry_g = __fsub_rn(1.0f, mix[b]);
-    (void)sr_f;
+    const PsClip k = ps_clip(sr, rate[b], depth[b], centre[b], feedback[b], mix[b]);
 
     float phase = 0.0f;
-    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f, s4 = 0.f, s5 = 0.f, last = 0.f;
+    float z[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};            // s0..s5, lastOut
 
     for (int n0 = 0; n0 < total; n0 += PH_BLOCK) {
         // (1) coalesced load of 256 input samples: lane l holds samples n0 + j*64 + l, j = 0..3
@@ -65,21 +54,13 @@ __global__ __launch_bounds__(64 * PH_WPB) void phaser_kernel(const float *__rest
         }
         // (2) sequential fp32 phase accumulation; lane k keeps the phase of update k
         float my_phase = 0.0f;
-        for (int k = 0; k < PH_BLOCK / 4; ++k) {
-            if (lane == k) my_phase = phase;
-            phase = __fadd_rn(phase, inc);
-            while (phase >= two_pi) phase = __fsub_rn(phase, two_pi);
+        for (int u = 0; u < PH_BLOCK / 4; ++u) {
+            if (lane == u) my_phase = phase;
+            phase = ps_step(phase, k.inc);
         }
-        // (3) one cut-off update per lane: lane k holds G of samples 4k .. 4k+3 of this block
-        float Greg;
-        {
-            float osc = (float)sin((double)__fsub_rn(my_phase, pi_f));
-            float lfo = __fadd_rn(__fmul_rn(osc, osc_vol), norm_centre);
-            lfo = lfo < 0.0f ? 0.0f : (lfo > 1.0f ? 1.0f : lfo);
-            float fc = (float)pow(10.0, (double)__fadd_rn(__fmul_rn(lfo, __fsub_rn(log_max, log_min)), log_min));
-            float g = (float)tan(3.14159265358979323846 * (double)fc / sr);
-            Greg = __fdiv_rn(g, __fadd_rn(1.0f, g));
-        }
+        // (3) one cut-off update per lane: lane u holds G of samples 4u .. 4u+3 of this block
+        float pre_unused;
+        const float Greg = ps_cutoff(k, ps_osc(my_phase), pre_unused);
         // (4) the dependent chain, wave-uniform; inputs and coefficients are broadcast from lane
         //     registers (v_readlane) so that no LDS round trip sits between two samples
         const int cnt = min(PH_BLOCK, total - n0);
@@ -88,18 +69,9 @@ __global__ __launch_bounds__(64 * PH_WPB) void phaser_kernel(const float *__rest
             const int lim = min(64, cnt - j * 64);
             for (int li = 0; li < lim; ++li) {
                 const float in = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(xr[j]), li));
-                float out = __fsub_rn(in, last);
                 const float G = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(Greg), (j * 64 + li) >> 2));
-                float v, yk;
-#define PH_STAGE(S)                                   \
-    v = __fmul_rn(G, __fsub_rn(out, S));             \
-    yk = __fadd_rn(v, S);                            \
-    S = __fadd_rn(v, yk);                            \
-    out = __fsub_rn(__fmul_rn(2.0f, yk), out);
-                PH_STAGE(s0) PH_STAGE(s1) PH_STAGE(s2) PH_STAGE(s3) PH_STAGE(s4) PH_STAGE(s5)
-#undef PH_STAGE
-                last = __fmul_rn(out, fb);
-                float m = __fadd_rn(__fmul_rn(out, wet_g), __fmul_rn(in, dry_g));
+                const float out = ps_sample(G, k.fb, in, z);
+                float m = __fadd_rn(__fmul_rn(out, k.wet_g), __fmul_rn(in, k.dry_g));
                 m = m < -1.0f ? -1.0f : (m > 1.0f ? 1.0f : m);
                 yr[j] = lane == li ? m : yr[j];
             }
@@ -144,7 +116,10 @@ __global__ __launch_bounds__(64 * PH_WPB) void phaser_kernel(const float *__rest
 //  * leaves per group G, pre (the lfo before its clamp), osc and the four output-clip decisions, per chunk the map M of
 //    phase A (its transpose is the chunk map of the adjoint: the backward does not run seven unit adjoints), and the state
 //    at the start of every PS_SUB-th group (phase C), from which the backward recomputes 8 samples at a time in registers.
-// The STASH = false instantiation compiles to the instructions it had before the template existed.
+// Both instantiations share their arithmetic with phaser_kernel and the adjoint through phaser_common.h.  What keeps
+// STASH = false the plain forward is checked on the device assembly whenever this code is restructured: the same VGPR /
+// SGPR counts, no scratch, and the same count of every fp32 / fp64 arithmetic opcode as before (instruction order and
+// register numbering may differ), and bit-equal outputs on the timing tools' draws.
 
 // phase after g cut-off updates:  p <- fl(p + inc);  while (p >= 2 pi) p <- fl(p - 2 pi)   (oracle_ref.c:orc_phaser)
 // Inside one binade [2^e, 2^(e+1)) every representable p is a multiple of ulp = 2^(e-23), so fl(p + inc) = p + d with ONE
@@ -153,24 +128,19 @@ __global__ __launch_bounds__(64 * PH_WPB) void phaser_kernel(const float *__rest
 // three values share a binade, jump  p += j d  (exact in fp32: stays inside the binade, below 2 pi, one step of margin),
 // then continue with real steps across the binade edge / the wrap.  ~25 rounds per LFO period; checked against the
 // sequential loop for 600 (rate, count) pairs including constructed ties (tools/probe/check_phase_jump.py).
-__device__ __forceinline__ float ps_step(float p, float inc, float two_pi)
+__device__ float ps_phase_after(int g, float inc)
 {
-    p = __fadd_rn(p, inc);
-    while (p >= two_pi) p = __fsub_rn(p, two_pi);
-    return p;
-}
-__device__ float ps_phase_after(int g, float inc, float two_pi)
-{
+    const float two_pi = PS_TWO_PI;
     float p = 0.0f;
     int rem = g;
     while (rem > 0) {
-        const float p1 = ps_step(p, inc, two_pi);
+        const float p1 = ps_step(p, inc);
         p = p1;
         if (--rem == 0) break;
-        const float p2 = ps_step(p1, inc, two_pi);
+        const float p2 = ps_step(p1, inc);
         p = p2;
         if (--rem == 0) break;
-        const float p3 = ps_step(p2, inc, two_pi);
+        const float p3 = ps_step(p2, inc);
         p = p3;
         if (--rem == 0) break;
         const float d1 = __fsub_rn(p2, p1), d2 = __fsub_rn(p3, p2);
@@ -217,54 +187,23 @@ __global__ __launch_bounds__(PS_P) void phaser_scan_kernel(const float *__restri
     float *db = dry_out ? dry_out + (size_t)b * y_stride : nullptr;
     float *gw = gws + (size_t)item * gws_stride;
     // STASH: the group records double as the cut-off workspace; a clip that does not fit its row is left alone
-    float *st = nullptr;
+    PsStash<float> st = {nullptr, sg};
     const float *mb = nullptr;
     if constexpr (STASH) {
         if (total > x_width || ((total + 3) >> 2) > sg) return;
-        st = stash + (size_t)b * stash_stride;
-        gw = st;
+        st.row = stash + (size_t)b * stash_stride;
+        gw = st.G();
         if (mod) mb = mod + (size_t)b * mod_stride;
     }
     const bool ext = STASH && mb != nullptr;                     // the LFO comes from outside
 
-    const float two_pi = 6.283185307179586476925286766559f;
-    const float pi_f = 3.14159265358979323846f;
-    const float fmax_hz = (float)fmin(20000.0, 0.49 * sr);
-    const float log_min = (float)log10(20.0), log_max = (float)log10((double)fmax_hz);
-    const float inc = __fmul_rn(__fdiv_rn(two_pi, (float)(sr / 4.0)), ext ? 0.0f : rate[b]);
-    const float norm_centre = __fdiv_rn(__fsub_rn((float)log10((double)centre[b]), log_min), __fsub_rn(log_max, log_min));
-    const float osc_vol = __fmul_rn(depth[b], 0.5f);
-    const float fb = feedback[b];
-    const float wet_g = mix[b], dry_g = __fsub_rn(1.0f, mix[b]);
+    const PsClip k = ps_clip(sr, ext ? 0.0f : rate[b], depth[b], centre[b], feedback[b], mix[b]);
 
     const int n_groups = (total + 3) >> 2;                       // cut-off updates = groups of 4 samples from sample 0
     const int gpc = (n_groups + PS_P - 1) / PS_P;                // groups per chunk
     const int g0 = p * gpc, g1 = min(g0 + gpc, n_groups);        // this lane's groups [g0, g1) (empty beyond the clip)
 
     const bool use_ws = STASH || (gws != nullptr && (long long)n_groups <= gws_stride);
-    // one cut-off update (oracle_ref.c:orc_phaser; sin / pow / tan in fp64 and rounded once = the host libm's float results)
-    auto cutoff = [&](float ph) {
-        const float osc = (float)sin((double)__fsub_rn(ph, pi_f));
-        float lfo = __fadd_rn(__fmul_rn(osc, osc_vol), norm_centre);
-        lfo = lfo < 0.0f ? 0.0f : (lfo > 1.0f ? 1.0f : lfo);
-        const float fc = (float)pow(10.0, (double)__fadd_rn(__fmul_rn(lfo, __fsub_rn(log_max, log_min)), log_min));
-        const float gg = (float)tan(3.14159265358979323846 * (double)fc / sr);
-        return __fdiv_rn(gg, __fadd_rn(1.0f, gg));
-    };
-    // the same update from a given osc, which also hands out the lfo before its clamp (STASH only)
-    auto coef = [&](float osc, float &pre) {
-        pre = __fadd_rn(__fmul_rn(osc, osc_vol), norm_centre);
-        const float lfo = pre < 0.0f ? 0.0f : (pre > 1.0f ? 1.0f : pre);
-        const float fc = (float)pow(10.0, (double)__fadd_rn(__fmul_rn(lfo, __fsub_rn(log_max, log_min)), log_min));
-        const float gg = (float)tan(3.14159265358979323846 * (double)fc / sr);
-        return __fdiv_rn(gg, __fadd_rn(1.0f, gg));
-    };
-
-#define PS_STAGE(S)                                   \
-    v = __fmul_rn(G, __fsub_rn(out, S));             \
-    yk = __fadd_rn(v, S);                            \
-    S = __fadd_rn(v, yk);                            \
-    out = __fsub_rn(__fmul_rn(2.0f, yk), out);
 
     // ---- A: the chunk's affine map, the cut-offs on the way
     float S[8][7];
@@ -272,7 +211,7 @@ __global__ __launch_bounds__(PS_P) void phaser_scan_kernel(const float *__restri
     for (int r = 0; r < 8; ++r)
 #pragma unroll
         for (int c = 0; c < 7; ++c) S[r][c] = r == c ? 1.0f : 0.0f;
-    float phase = ext ? 0.0f : ps_phase_after(min(g0, n_groups), inc, two_pi);
+    float phase = ext ? 0.0f : ps_phase_after(min(g0, n_groups), k.inc);
     for (int g = g0; g < g1; ++g) {
         float xv[4];
 #pragma unroll
@@ -280,28 +219,19 @@ __global__ __launch_bounds__(PS_P) void phaser_scan_kernel(const float *__restri
             const int n = 4 * g + j;
             xv[j] = probe ? 0.25f : (n < total ? xb[n] : 0.0f);
         }
-        float G;
+        float pre;
+        const float osc = ext ? __fsub_rn(1.0f, __fmul_rn(2.0f, g < n_mod ? mb[g] : 0.5f)) : ps_osc(phase);
+        const float G = ps_cutoff(k, osc, pre);
         if constexpr (STASH) {
-            float pre;
-            const float osc = ext ? __fsub_rn(1.0f, __fmul_rn(2.0f, g < n_mod ? mb[g] : 0.5f))
-                                  : (float)sin((double)__fsub_rn(phase, pi_f));
-            G = coef(osc, pre);
-            st[sg + g] = pre;
-            st[2 * sg + g] = osc;
-        } else {
-            G = cutoff(phase);
+            st.pre()[g] = pre;
+            st.osc()[g] = osc;
         }
-        phase = ps_step(phase, inc, two_pi);
+        phase = ps_step(phase, k.inc);
         if (use_ws) gw[g] = G;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
 #pragma unroll
-            for (int r = 0; r < 8; ++r) {
-                const float in = r == 7 ? xv[j] : 0.0f;
-                float out = __fsub_rn(in, S[r][6]), v, yk;
-                PS_STAGE(S[r][0]) PS_STAGE(S[r][1]) PS_STAGE(S[r][2]) PS_STAGE(S[r][3]) PS_STAGE(S[r][4]) PS_STAGE(S[r][5])
-                S[r][6] = __fmul_rn(out, fb);
-            }
+            for (int r = 0; r < 8; ++r) (void)ps_sample(G, k.fb, r == 7 ? xv[j] : 0.0f, S[r]);
         }
     }
     {
@@ -334,21 +264,22 @@ __global__ __launch_bounds__(PS_P) void phaser_scan_kernel(const float *__restri
     }
     __syncthreads();
     if constexpr (STASH) {                                       // the chunk maps, as they lie in LDS
-        float *sm = st + 4 * (size_t)sg;
-        for (int i = p; i < PS_P * PS_MV; i += PS_P) sm[i] = mv[i];
+        for (int i = p; i < PS_P * PS_MV; i += PS_P) st.maps()[i] = mv[i];
     }
 
     // ---- C: the chunk from its true start state, JUCE's operation order, output window
     {
-        float s0 = zs[p * 8 + 0], s1 = zs[p * 8 + 1], s2 = zs[p * 8 + 2], s3 = zs[p * 8 + 3], s4 = zs[p * 8 + 4],
-              s5 = zs[p * 8 + 5], last = zs[p * 8 + 6];
-        float phase_c = use_ws ? 0.0f : ps_phase_after(min(g0, n_groups), inc, two_pi);
+        float z[7];
+#pragma unroll
+        for (int c = 0; c < 7; ++c) z[c] = zs[p * 8 + c];
+        float phase_c = use_ws ? 0.0f : ps_phase_after(min(g0, n_groups), k.inc);
         for (int g = g0; g < g1; ++g) {
             float G;
             if (use_ws) G = gw[g];
             else {                                               // workspace too small for this clip: evaluate the cut-off again
-                G = cutoff(phase_c);
-                phase_c = ps_step(phase_c, inc, two_pi);
+                float pre_unused;
+                G = ps_cutoff(k, ps_osc(phase_c), pre_unused);
+                phase_c = ps_step(phase_c, k.inc);
             }
             float xv[4];
 #pragma unroll
@@ -359,20 +290,17 @@ __global__ __launch_bounds__(PS_P) void phaser_scan_kernel(const float *__restri
             int passed = 0;
             if constexpr (STASH) {
                 if (((g - g0) & (PS_SUB - 1)) == 0) {
-                    float4 *ck = reinterpret_cast<float4 *>(st + 4 * (size_t)sg + PS_P * PS_MV) +
-                                 2 * ((size_t)p * ((gpc + PS_SUB - 1) / PS_SUB) + ((g - g0) / PS_SUB));
-                    ck[0] = make_float4(s0, s1, s2, s3);
-                    ck[1] = make_float4(s4, s5, last, 0.0f);
+                    float4 *ck = st.ckpt(p, gpc, (g - g0) / PS_SUB);
+                    ck[0] = make_float4(z[0], z[1], z[2], z[3]);
+                    ck[1] = make_float4(z[4], z[5], z[6], 0.0f);
                 }
             }
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const int n = 4 * g + j;
                 const float in = xv[j];
-                float out = __fsub_rn(in, last), v, yk;
-                PS_STAGE(s0) PS_STAGE(s1) PS_STAGE(s2) PS_STAGE(s3) PS_STAGE(s4) PS_STAGE(s5)
-                last = __fmul_rn(out, fb);
-                float m = __fadd_rn(__fmul_rn(out, wet_g), __fmul_rn(in, dry_g));
+                const float out = ps_sample(G, k.fb, in, z);
+                float m = __fadd_rn(__fmul_rn(out, k.wet_g), __fmul_rn(in, k.dry_g));
                 if constexpr (STASH) passed |= (m >= -1.0f && m <= 1.0f) ? 1 << j : 0;
                 m = m < -1.0f ? -1.0f : (m > 1.0f ? 1.0f : m);
                 if (n >= lead && n < total && (!probe || g + 1 == g1)) {
@@ -380,10 +308,9 @@ __global__ __launch_bounds__(PS_P) void phaser_scan_kernel(const float *__restri
                     if (db) db[n - lead] = in;
                 }
             }
-            if constexpr (STASH) reinterpret_cast<int *>(st)[3 * (size_t)sg + g] = passed;
+            if constexpr (STASH) st.pass()[g] = passed;
         }
     }
-#undef PS_STAGE
 }
 
 // x: source audio, row b at x + b*x_stride, at least lead[b] + N samples; rate, depth, centre,
@@ -408,16 +335,11 @@ static int phaser_fwd_launch(const float *x, int64_t x_stride, const float *rate
     if (exact_order) {
         const dim3 grid((unsigned)((items + PH_WPB - 1) / PH_WPB)), block(64 * PH_WPB);
         hipLaunchKernelGGL(phaser_kernel, grid, block, 0, (hipStream_t)stream, x, (long long)x_stride, rate, depth, centre,
-                           feedback, mix, lead, rows, (int)items, (int)N, (float)sr, sr, y, (long long)y_stride, dry_out);
+                           feedback, mix, lead, rows, (int)items, (int)N, sr, y, (long long)y_stride, dry_out);
     } else {
         const size_t lds = PS_LDS_FLOATS * sizeof(float);
-        static bool attr_set[64] = {};                       // per device: one process may drive several GPUs
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        if (dev < 0 || dev >= 64 || !attr_set[dev]) {
-            (void)hipFuncSetAttribute((const void *)phaser_scan_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (dev >= 0 && dev < 64) attr_set[dev] = true;
-        }
+        static MxLdsLatch latch = {};
+        if (mx_set_dyn_lds(latch, (const void *)phaser_scan_kernel<false>, lds) != MX_OK) return MX_ERR_LAUNCH;
         hipLaunchKernelGGL(phaser_scan_kernel<false>, dim3((unsigned)items), dim3(PS_P), lds, (hipStream_t)stream, x, (long long)x_stride,
                            rate, depth, centre, feedback, mix, lead, rows, (int)items, (int)N, sr, y, (long long)y_stride,
                            dry_out, workspace, (long long)workspace_stride, probe, (const float *)nullptr, 0ll, 0,
@@ -496,12 +418,7 @@ __global__ __launch_bounds__(PS_P) void phaser_cascade_probe_kernel(int steps, f
         for (int r = 0; r < 8; ++r) {
             float o = __fsub_rn(r == 7 ? in : 0.0f, last[r]);
 #pragma unroll
-            for (int k = 0; k < 6; ++k) {
-                const float v = __fmul_rn(G, __fsub_rn(o, s[r][k]));
-                const float yk = __fadd_rn(v, s[r][k]);
-                s[r][k] = __fadd_rn(v, yk);
-                o = __fsub_rn(__fmul_rn(2.0f, yk), o);
-            }
+            for (int k = 0; k < 6; ++k) (void)ps_stage(G, s[r][k], o);
             last[r] = __fmul_rn(o, fb);
         }
         in = -in;

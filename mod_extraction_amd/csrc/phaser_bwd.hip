@@ -71,25 +71,20 @@ __global__ __launch_bounds__(PS_P) void phaser_bwd_kernel(
     const float *dyb = dy + (size_t)b * dy_stride;
     float *dxb = dx ? dx + (size_t)b * dx_stride : nullptr;
     float *dmb = dmod ? dmod + (size_t)b * dmod_stride : nullptr;
-    const float *st = stash + (size_t)b * stash_stride;
-    const float *stG = st, *stPre = st + sg, *stOsc = st + 2 * (size_t)sg;
-    const int *stPass = reinterpret_cast<const int *>(st) + 3 * (size_t)sg;
-    const float *stM = st + 4 * (size_t)sg;
-    const float4 *stCk = reinterpret_cast<const float4 *>(stM + PS_P * PS_MV);
+    const PsStash<const float> st = {stash + (size_t)b * stash_stride, sg};
 
-    const float fb = feedback[b];
-    const float wet_g = mix[b], dry_g = __fsub_rn(1.0f, mix[b]);
+    const PsClip k = ps_clip(sr, 0.0f, depth[b], centre[b], feedback[b], mix[b]);   // (no rate: the phase is not needed)
+    const float fb = k.fb, wet_g = k.wet_g;
     const int gpc = (n_groups + PS_P - 1) / PS_P;                // the forward's chunking
-    const int spc = (gpc + PS_SUB - 1) / PS_SUB;
     const int g0 = min(p * gpc, n_groups), g1 = min(g0 + gpc, n_groups);
 
     // the forward's chunk maps -> LDS (M only: slots 49..55 of a chunk take w below)
     for (int i = p; i < PS_P * PS_MV; i += PS_P)
-        if (i % PS_MV < 49) mv[i] = stM[i];
+        if (i % PS_MV < 49) mv[i] = st.maps()[i];
 
     // the masked dy of the four samples of group g
     auto load_gm = [&](int g, float (&gm)[4]) {
-        const int pass = stPass[g];
+        const int pass = st.pass()[g];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int n = 4 * g + j;
@@ -101,7 +96,7 @@ __global__ __launch_bounds__(PS_P) void phaser_bwd_kernel(
     {
         float L[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, unused = 0.0f;
         for (int g = g1 - 1; g >= g0; --g) {
-            const float G = stG[g];
+            const float G = st.G()[g];
             float gm[4];
             load_gm(g, gm);
 #pragma unroll
@@ -132,11 +127,8 @@ __global__ __launch_bounds__(PS_P) void phaser_bwd_kernel(
     __syncthreads();
 
     // ---- C': the chunk backwards from its true end adjoint
-    const float fmax_hz = (float)fmin(20000.0, 0.49 * sr);
-    const float log_min = (float)log10(20.0), log_max = (float)log10((double)fmax_hz);
-    const float span = __fsub_rn(log_max, log_min);
-    const double ln10_span = 2.302585092994045684 * (double)span;
-    const double pi_sr = 3.14159265358979323846 / sr;
+    const double ln10_span = 2.302585092994045684 * (double)k.span;
+    const double pi_sr = PS_PI / sr;
     const double depth_d = (double)depth[b];
     double a_dp = 0.0, a_ce = 0.0, a_fb = 0.0, a_mx = 0.0;
     {
@@ -146,8 +138,9 @@ __global__ __launch_bounds__(PS_P) void phaser_bwd_kernel(
         const int n_sub = (g1 - g0 + PS_SUB - 1) / PS_SUB;
         for (int sb = n_sub - 1; sb >= 0; --sb) {
             const int gs = g0 + sb * PS_SUB;
-            const float4 c0 = stCk[2 * ((size_t)p * spc + sb)], c1 = stCk[2 * ((size_t)p * spc + sb) + 1];
-            float s0 = c0.x, s1 = c0.y, s2 = c0.z, s3 = c0.w, s4 = c1.x, s5 = c1.y, last = c1.z;
+            const float4 *ck = st.ckpt(p, gpc, sb);
+            const float4 c0 = ck[0], c1 = ck[1];
+            float z[7] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z};
             float D[PB_S][6], O6[PB_S], GM[PB_S], Gs[PS_SUB];
             float mx32 = 0.0f;
             // the forward of the sub-block, JUCE's operation order (phaser.hip phase C)
@@ -155,7 +148,7 @@ __global__ __launch_bounds__(PS_P) void phaser_bwd_kernel(
             for (int u = 0; u < PS_SUB; ++u) {
                 const int g = gs + u;
                 const bool live = g < g1;
-                const float G = live ? stG[g] : 0.0f;
+                const float G = live ? st.G()[g] : 0.0f;
                 Gs[u] = G;
                 float gm[4] = {0.f, 0.f, 0.f, 0.f};
                 if (live) load_gm(g, gm);
@@ -163,16 +156,7 @@ __global__ __launch_bounds__(PS_P) void phaser_bwd_kernel(
                 for (int j = 0; j < 4; ++j) {
                     const int n = 4 * g + j, s = 4 * u + j;
                     const float in = (live && n < total) ? xb[n] : 0.0f;
-                    float out = __fsub_rn(in, last), v, yk;
-#define PB_STAGE(S, K)                                \
-    D[s][K] = __fsub_rn(out, S);                     \
-    v = __fmul_rn(G, D[s][K]);                       \
-    yk = __fadd_rn(v, S);                            \
-    S = __fadd_rn(v, yk);                            \
-    out = __fsub_rn(__fmul_rn(2.0f, yk), out);
-                    PB_STAGE(s0, 0) PB_STAGE(s1, 1) PB_STAGE(s2, 2) PB_STAGE(s3, 3) PB_STAGE(s4, 4) PB_STAGE(s5, 5)
-#undef PB_STAGE
-                    last = __fmul_rn(out, fb);
+                    const float out = ps_sample(G, fb, in, z, D[s]);
                     O6[s] = out;
                     GM[s] = gm[j];
                     mx32 = __builtin_fmaf(gm[j], out - in, mx32);
@@ -191,18 +175,18 @@ __global__ __launch_bounds__(PS_P) void phaser_bwd_kernel(
                         const int n = 4 * g + j, s = 4 * u + j;
                         fb32 = __builtin_fmaf(L[6], O6[s], fb32);
                         const float g_out = pb_adj_step<true>(L, G, GM[s], fb, wet_g, D[s], dG);
-                        if (dxb && n < total) dxb[n] = __builtin_fmaf(dry_g, GM[s], g_out);
+                        if (dxb && n < total) dxb[n] = __builtin_fmaf(k.dry_g, GM[s], g_out);
                     }
                     a_fb += (double)fb32;
                     // dG -> dlfo through G = g / (1 + g), g = tan(pi fc / sr), fc = 10^(lfo span + log_min), lfo = clip(pre)
-                    const float pre = stPre[g];
+                    const float pre = st.pre()[g];
                     double dlfo = 0.0;
                     if (pre >= 0.0f && pre <= 1.0f) {
                         const double Gd = (double)G, omG = 1.0 - Gd, gg = Gd / omG;
-                        const double fc = pow(10.0, (double)__fadd_rn(__fmul_rn(pre, span), log_min));
+                        const double fc = pow(10.0, (double)__fadd_rn(__fmul_rn(pre, k.span), k.log_min));
                         dlfo = (double)dG * omG * omG * pi_sr * (1.0 + gg * gg) * fc * ln10_span;
                     }
-                    a_dp += dlfo * 0.5 * (double)stOsc[g];
+                    a_dp += dlfo * 0.5 * (double)st.osc()[g];
                     a_ce += dlfo;
                     if (dmb && g < n_mod) dmb[g] = (float)(-dlfo * depth_d);
                 }

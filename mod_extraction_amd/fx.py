@@ -32,18 +32,20 @@ def apply_tremolo(x: T, mod_sig: T, mix: Param = 1.0) -> T:
     return ((1.0 - mix) * x) + (mix * mod_sig * x)
 
 
-def _check_param(param: Param, bs: int, can_be_one: bool = True) -> None:
-    """fx.py:46-70: all parameters >= 0; feedback < 1 strictly, the others <= 1."""
+def _check_range(param: Param, bs: int, lo: float, hi: float, lo_open: bool = False, hi_open: bool = False) -> None:
+    """The range check of every effect parameter: a (bs,) tensor or a float inside [lo, hi] (open ends where said)."""
     if isinstance(param, T):
         assert param.shape == (bs,)
-        lo, hi = float(param.min()), float(param.max())
+        a, b = float(param.min()), float(param.max())
     else:
-        lo = hi = float(param)
-    assert lo >= 0
-    if can_be_one:
-        assert hi <= 1.0
-    else:
-        assert hi < 1.0
+        a = b = float(param)
+    assert a > lo if lo_open else a >= lo
+    assert b < hi if hi_open else b <= hi
+
+
+def _check_param(param: Param, bs: int, can_be_one: bool = True) -> None:
+    """fx.py:46-70: all parameters >= 0; feedback < 1 strictly, the others <= 1."""
+    _check_range(param, bs, 0.0, 1.0, hi_open=not can_be_one)
 
 
 def derive_clip_constants(bs: int, device: torch.device, max_min_delay_samples: int,
@@ -82,6 +84,16 @@ def _rows_view(t: T) -> Tuple[int, int]:
     return t.data_ptr(), t.stride(0)
 
 
+def _rows_arg(rows: Optional[T]) -> Tuple[Optional[int], int]:
+    """The (rows, n_rows) argument pair of every launch: an optional list of clip indices to process."""
+    return _hip.ptr(rows), 0 if rows is None else rows.numel()
+
+
+def _per_row(v: T, n_ch: int) -> T:
+    """A (bs,) per-clip vector repeated for the n_ch rows of each clip: a clip's channels share its parameters."""
+    return (v.repeat_interleave(n_ch) if n_ch > 1 else v).contiguous()
+
+
 def flanger_forward(x: T, mod_sig: T, consts: Dict[str, T], max_delay: T, max_delay_max: int,
                     rows: Optional[T] = None, out: Optional[T] = None, mod_up: Optional[T] = None,
                     dbg_prev: Optional[T] = None, dbg_frac: Optional[T] = None) -> T:
@@ -89,13 +101,11 @@ def flanger_forward(x: T, mod_sig: T, consts: Dict[str, T], max_delay: T, max_de
     channel of a (B,2,N) tensor); mod_sig (B,n_mod) fp32; max_delay (B,) int32."""
     B, N = x.shape
     y = out if out is not None else torch.empty_like(x)
-    xp, xs = _rows_view(x)
-    yp, ys = _rows_view(y)
-    _hip.call("mx_flanger_fwd", xp, xs, _hip.ptr(mod_sig), mod_sig.size(-1),
+    _hip.call("mx_flanger_fwd", *_rows_view(x), _hip.ptr(mod_sig), mod_sig.size(-1),
               _hip.ptr(consts["lfo_scale"]), _hip.ptr(consts["min_delay"]), _hip.ptr(consts["feedback"]),
               _hip.ptr(consts["depth"]), _hip.ptr(consts["mix"]), _hip.ptr(consts["one_minus_mix"]),
-              _hip.ptr(max_delay), int(max_delay_max), _hip.ptr(rows), 0 if rows is None else rows.numel(),
-              B, N, yp, ys, _hip.ptr(mod_up), _hip.ptr(dbg_prev), _hip.ptr(dbg_frac), _hip.stream())
+              _hip.ptr(max_delay), int(max_delay_max), *_rows_arg(rows),
+              B, N, *_rows_view(y), _hip.ptr(mod_up), _hip.ptr(dbg_prev), _hip.ptr(dbg_frac), _hip.stream())
     return y
 
 
@@ -108,13 +118,11 @@ def flanger_forward_stash(x: T, mod_sig: T, consts: Dict[str, T], max_delay: T, 
     assert mod_sig.shape == (B, N)
     y = out if out is not None else torch.empty_like(x)
     st = stash if stash is not None else torch.empty((B, N), device=x.device, dtype=torch.float32)
-    xp, xs = _rows_view(x)
-    yp, ys = _rows_view(y)
-    _hip.call("mx_flanger_fwd_stash", xp, xs, _hip.ptr(mod_sig), N,
+    _hip.call("mx_flanger_fwd_stash", *_rows_view(x), _hip.ptr(mod_sig), N,
               _hip.ptr(consts["lfo_scale"]), _hip.ptr(consts["min_delay"]), _hip.ptr(consts["feedback"]),
               _hip.ptr(consts["depth"]), _hip.ptr(consts["mix"]), _hip.ptr(consts["one_minus_mix"]),
-              _hip.ptr(max_delay), int(max_delay_max), _hip.ptr(rows), 0 if rows is None else rows.numel(),
-              B, N, yp, ys, _hip.ptr(st), _hip.stream())
+              _hip.ptr(max_delay), int(max_delay_max), *_rows_arg(rows),
+              B, N, *_rows_view(y), _hip.ptr(st), _hip.stream())
     return y, st
 
 
@@ -138,14 +146,12 @@ def flanger_backward(dy: T, x: T, mod_sig: T, stash: T, consts: Dict[str, T], ma
         dmod = torch.empty((B, N), device=dev, dtype=torch.float32)
     dxp, dxs = _rows_view(dx) if need_dx else (None, 0)
     dmp, dms = _rows_view(dmod) if need_dmod else (None, 0)
-    dyp, dys = _rows_view(dy)
-    xp, xs = _rows_view(x)
     grads = {k: torch.zeros((B,), device=dev, dtype=torch.float64) for k in params}
     ws = torch.empty((B, N), device=dev, dtype=torch.float32)
-    _hip.call("mx_flanger_bwd", dyp, dys, xp, xs, _hip.ptr(mod_sig), _hip.ptr(stash),
+    _hip.call("mx_flanger_bwd", *_rows_view(dy), *_rows_view(x), _hip.ptr(mod_sig), _hip.ptr(stash),
               _hip.ptr(consts["lfo_scale"]), _hip.ptr(consts["min_delay"]), _hip.ptr(consts["feedback"]),
               _hip.ptr(consts["depth"]), _hip.ptr(consts["mix"]), _hip.ptr(consts["one_minus_mix"]),
-              _hip.ptr(max_delay), int(max_delay_max), _hip.ptr(rows), 0 if rows is None else rows.numel(), B, N,
+              _hip.ptr(max_delay), int(max_delay_max), *_rows_arg(rows), B, N,
               _hip.ptr(ws), dxp, dxs, dmp, dms, *[_hip.ptr(grads.get(k)) for k in PARAM_GRADS], _hip.stream())
     return (dx if need_dx else None), (dmod if need_dmod else None), grads
 
@@ -159,8 +165,7 @@ class _FlangerFunction(torch.autograd.Function):
         rows = x.size(0)
         consts = {"lfo_scale": lfo_scale, "min_delay": min_delay, "feedback": feedback, "depth": depth, "mix": mix,
                   "one_minus_mix": one_minus_mix}
-        consts = {k: (v.detach().repeat_interleave(n_ch) if n_ch > 1 else v.detach()).contiguous()
-                  for k, v in consts.items()}
+        consts = {k: _per_row(v.detach(), n_ch) for k, v in consts.items()}
         md = torch.full((rows,), max_delay_samples, device=x.device, dtype=torch.int32)
         y, stash = flanger_forward_stash(x.detach(), mod_sig.detach(), consts, md, max_delay_samples)
         ctx.save_for_backward(x, mod_sig, stash)
@@ -201,16 +206,12 @@ class MonoFlangerChorusModule(nn.Module):
     def check_param(self, param: Param, bs: int, out_n_dim: int = 2, can_be_one: bool = True) -> Param:
         """fx.py:46-70: range check of one effect parameter ((bs,) tensor or float in [0, 1], or [0, 1) when it may not be
         one) and its broadcast view; ``forward`` applies the same checks inside ``derive_clip_constants``."""
-        if isinstance(param, T):
-            assert param.shape == (bs,)
-            assert param.min() >= 0
-            assert param.max() <= 1.0 if can_be_one else param.max() < 1.0
-            if out_n_dim not in (2, 3):
-                raise ValueError
-            return param.view((-1,) + (1,) * (out_n_dim - 1))
-        assert param >= 0
-        assert param <= 1.0 if can_be_one else param < 1.0
-        return param
+        _check_param(param, bs, can_be_one)
+        if not isinstance(param, T):
+            return param
+        if out_n_dim not in (2, 3):
+            raise ValueError
+        return param.view((-1,) + (1,) * (out_n_dim - 1))
 
     def apply_effect(self, x: T, mod_sig: T, feedback: Param, min_delay_width: Param, width: Param, depth: Param,
                      mix: Param) -> T:
@@ -224,12 +225,15 @@ class MonoFlangerChorusModule(nn.Module):
             return self._apply_effect_grad(x, mod_sig, *params)
         return self.forward(x, mod_sig, feedback, min_delay_width, width, depth, mix)
 
-    def _apply_effect_grad(self, x: T, mod_sig: T, feedback: Param, min_delay_width: Param, width: Param, depth: Param,
-                           mix: Param) -> T:
+    def _prepare(self, x: T, mod_sig: T, feedback: Param, min_delay_width: Param, width: Param, depth: Param,
+                 mix: Param, full_rate: bool):
+        """The checks, the per-clip constants and the rows both paths launch on.  n_ch > 1 (fx.py:81-85,104-115): every
+        channel owns a delay line = one kernel row per (clip, channel); a clip's channels share its parameters (the (bs,)
+        constants are returned as they are); mod_sig (bs, n) / (bs, 1, n) is shared by the channels."""
         assert x.ndim == 3
         bs, n_ch, n = x.shape
         assert n_ch == self.n_ch
-        assert mod_sig.size(0) == bs and mod_sig.size(-1) == n
+        assert mod_sig.size(0) == bs and (not full_rate or mod_sig.size(-1) == n)
         if mod_sig.ndim == 3:
             assert mod_sig.size(1) in (1, n_ch)
         consts = derive_clip_constants(bs, x.device, self.max_min_delay_samples, self.max_lfo_delay_samples,
@@ -239,35 +243,26 @@ class MonoFlangerChorusModule(nn.Module):
         if xr.stride(-1) != 1:
             xr = xr.contiguous()
         if mod_sig.ndim == 2 or mod_sig.size(1) == 1:               # fx.py:84-85: shared by the channels
-            mod_sig = mod_sig.reshape(bs, 1, n).expand(-1, n_ch, -1)
-        mr = mod_sig.reshape(rows, n).float().contiguous()
+            mod_sig = mod_sig.reshape(bs, 1, -1).expand(-1, n_ch, -1)
+        mr = mod_sig.reshape(rows, -1).float().contiguous()
+        return xr, mr, consts, (bs, n_ch, n)
+
+    def _apply_effect_grad(self, x: T, mod_sig: T, feedback: Param, min_delay_width: Param, width: Param, depth: Param,
+                           mix: Param) -> T:
+        xr, mr, consts, shape = self._prepare(x, mod_sig, feedback, min_delay_width, width, depth, mix, full_rate=True)
         y = _FlangerFunction.apply(xr, mr, consts["lfo_scale"], consts["min_delay"], consts["feedback"], consts["depth"],
-                                   consts["mix"], consts["one_minus_mix"], n_ch, self.max_delay_samples)
-        return y.view(bs, n_ch, n)
+                                   consts["mix"], consts["one_minus_mix"], self.n_ch, self.max_delay_samples)
+        return y.view(shape)
 
     def forward(self, x: T, mod_sig: T, feedback: Param = 0.0, min_delay_width: Param = 1.0,
                 width: Param = 1.0, depth: Param = 1.0, mix: Param = 1.0) -> T:
-        assert x.ndim == 3
-        bs, n_ch, n = x.shape
-        assert n_ch == self.n_ch
-        assert mod_sig.size(0) == bs
-        if mod_sig.ndim == 3:
-            assert mod_sig.size(1) in (1, n_ch)
         with torch.no_grad():
-            consts = derive_clip_constants(bs, x.device, self.max_min_delay_samples,
-                                           self.max_lfo_delay_samples, feedback, min_delay_width,
-                                           width, depth, mix)
-            # n_ch > 1 (fx.py:81-85,104-115): every channel owns a delay line = one kernel row per (clip, channel); a clip's
-            # channels share its parameters; mod_sig (bs, n) / (bs, 1, n) is shared by the channels
-            rows = bs * n_ch
-            if n_ch > 1:
-                consts = {k: v.repeat_interleave(n_ch) for k, v in consts.items()}
-                mod_sig = mod_sig.view(bs, 1, -1).expand(-1, n_ch, -1) if mod_sig.ndim == 2 or mod_sig.size(1) == 1 else mod_sig
-            md = torch.full((rows,), self.max_delay_samples, device=x.device, dtype=torch.int32)
-            xc = x.reshape(rows, n).contiguous().float()
-            mc = mod_sig.reshape(rows, -1).contiguous().float()
-            y = flanger_forward(xc, mc, consts, md, self.max_delay_samples)
-        return y.view(bs, n_ch, n)
+            xr, mr, consts, shape = self._prepare(x, mod_sig, feedback, min_delay_width, width, depth, mix,
+                                                  full_rate=False)
+            consts = {k: _per_row(v, self.n_ch) for k, v in consts.items()}
+            md = torch.full((xr.size(0),), self.max_delay_samples, device=x.device, dtype=torch.int32)
+            y = flanger_forward(xr, mr, consts, md, self.max_delay_samples)
+        return y.view(shape)
 
 
 def phaser_forward(src: T, params: Dict[str, T], lead: Optional[T], sr: float, n_samples: int,
@@ -293,7 +288,7 @@ def phaser_forward(src: T, params: Dict[str, T], lead: Optional[T], sr: float, n
     ws = None if exact_order else torch.empty((n_items, ws_stride), device=src.device, dtype=torch.float32)
     _hip.call("mx_phaser_fwd", sp, ss, _hip.ptr(params["rate_hz"]), _hip.ptr(params["depth"]),
               _hip.ptr(params["centre_frequency_hz"]), _hip.ptr(params["feedback"]), _hip.ptr(params["mix"]),
-              _hip.ptr(lead), _hip.ptr(rows), 0 if rows is None else rows.numel(), B, n_samples, float(sr),
+              _hip.ptr(lead), *_rows_arg(rows), B, n_samples, float(sr),
               1 if exact_order else 0, yp, ys, dp, _hip.ptr(ws), ws_stride, _hip.stream())
     return y
 
@@ -336,9 +331,8 @@ def phaser_forward_stash(src: T, params: Dict[str, T], lead: Optional[T], sr: fl
         assert mod.ndim == 2 and mod.size(0) == B and mod.dtype == torch.float32
     _hip.call("mx_phaser_fwd_stash", sp, ss, W, _hip.ptr(mod), 0 if mod is None else mod.size(1),
               _hip.ptr(params.get("rate_hz")), _hip.ptr(params["depth"]), _hip.ptr(params["centre_frequency_hz"]),
-              _hip.ptr(params["feedback"]), _hip.ptr(params["mix"]), _hip.ptr(lead), _hip.ptr(rows),
-              0 if rows is None else rows.numel(), B, n_samples, float(sr), yp, ys, dp, _hip.ptr(st), sg, row,
-              _hip.stream())
+              _hip.ptr(params["feedback"]), _hip.ptr(params["mix"]), _hip.ptr(lead), *_rows_arg(rows),
+              B, n_samples, float(sr), yp, ys, dp, _hip.ptr(st), sg, row, _hip.stream())
     return y, st
 
 
@@ -367,14 +361,12 @@ def phaser_backward(dy: T, src: T, stash: T, params: Dict[str, T], lead: Optiona
     dmp, dms = _rows_view(dmod) if need_dmod else (None, 0)
     assert not need_dx or dx.size(1) == W
     assert not need_dmod or dmod.size(1) >= n_mod                 # every group of the longest possible clip
-    dyp, dys = _rows_view(dy)
-    sp, ss = _rows_view(src)
     sg, row = phaser_stash_shape(W)
     assert stash.shape == (B, row)
     grads = {k: torch.zeros((B,), device=dev, dtype=torch.float64) for k in params_wanted}
-    _hip.call("mx_phaser_bwd", dyp, dys, sp, ss, W, _hip.ptr(stash), sg, row, _hip.ptr(params["depth"]),
+    _hip.call("mx_phaser_bwd", *_rows_view(dy), *_rows_view(src), W, _hip.ptr(stash), sg, row, _hip.ptr(params["depth"]),
               _hip.ptr(params["centre_frequency_hz"]), _hip.ptr(params["feedback"]), _hip.ptr(params["mix"]),
-              _hip.ptr(lead), _hip.ptr(rows), 0 if rows is None else rows.numel(), B, n_samples, float(sr), dxp, dxs,
+              _hip.ptr(lead), *_rows_arg(rows), B, n_samples, float(sr), dxp, dxs,
               dmp, dms, dmod.size(1) if need_dmod else 0, *[_hip.ptr(grads.get(k)) for k in PHASER_PARAM_GRADS],
               _hip.stream())
     return (dx if need_dx else None), (dmod if need_dmod else None), grads
@@ -387,8 +379,7 @@ class _PhaserFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, mod, rate, depth, centre, feedback, mix, lead, n_ch, sr, n):
         def rows_of(v):
-            v = v.detach().float()
-            return (v.repeat_interleave(n_ch) if n_ch > 1 else v).contiguous()
+            return _per_row(v.detach().float(), n_ch)
 
         params = {"depth": rows_of(depth), "centre_frequency_hz": rows_of(centre), "feedback": rows_of(feedback),
                   "mix": rows_of(mix)}
@@ -412,17 +403,6 @@ class _PhaserFunction(torch.autograd.Function):
         for k in PHASER_PARAM_GRADS:
             out.append(g[k].view(-1, ctx.n_ch).sum(1).float() if k in g else None)
         return tuple(out) + (None, None, None, None)
-
-
-def _check_phaser_param(param: Param, bs: int, lo: float, hi: float, lo_open: bool = False, hi_open: bool = False) -> None:
-    """Range check in the manner of ``_check_param``: a (bs,) tensor or a float inside [lo, hi] (open ends where said)."""
-    if isinstance(param, T):
-        assert param.shape == (bs,)
-        a, b = float(param.min()), float(param.max())
-    else:
-        a = b = float(param)
-    assert a > lo if lo_open else a >= lo
-    assert b < hi if hi_open else b <= hi
 
 
 class PhaserModule(nn.Module):
@@ -456,10 +436,10 @@ class PhaserModule(nn.Module):
         assert x.ndim == 3
         bs, n_ch, W = x.shape
         assert (mod_sig is None) != (rate_hz is None), "exactly one of mod_sig and rate_hz"
-        _check_phaser_param(depth, bs, 0.0, 1.0)
-        _check_phaser_param(mix, bs, 0.0, 1.0)
-        _check_phaser_param(feedback, bs, -1.0, 1.0, lo_open=True, hi_open=True)
-        _check_phaser_param(centre_frequency_hz, bs, 0.0, float("inf"), lo_open=True)
+        _check_range(depth, bs, 0.0, 1.0)
+        _check_range(mix, bs, 0.0, 1.0)
+        _check_range(feedback, bs, -1.0, 1.0, lo_open=True, hi_open=True)
+        _check_range(centre_frequency_hz, bs, 0.0, float("inf"), lo_open=True)
         if isinstance(rate_hz, T) and rate_hz.requires_grad:
             raise ValueError("PhaserModule has no gradient with respect to rate_hz: pass the LFO as mod_sig instead")
         dev = x.device
@@ -469,7 +449,7 @@ class PhaserModule(nn.Module):
         elif isinstance(lead, T):
             assert lead.shape == (bs,) and not lead.is_floating_point() and int(lead.min()) >= 0
             n = W - int(lead.max())
-            lead_rows = lead.to(device=dev, dtype=torch.int32).repeat_interleave(n_ch).contiguous()
+            lead_rows = _per_row(lead.to(device=dev, dtype=torch.int32), n_ch)
         else:
             assert 0 <= int(lead) < W
             n = W - int(lead)
@@ -517,8 +497,7 @@ class PhaserModule(nn.Module):
         with torch.no_grad():
             xr, mr, ps, lead_rows, n, (bs, n_ch) = self._prepare(x, mod_sig, rate_hz, depth, centre_frequency_hz, feedback,
                                                                  mix, lead)
-            rows_of = lambda v: (v.float().repeat_interleave(n_ch) if n_ch > 1 else v.float()).contiguous()
-            p = {k: rows_of(v) for k, v in zip(("rate_hz", "depth", "centre_frequency_hz", "feedback", "mix"), ps)
+            p = {k: _per_row(v.float(), n_ch) for k, v in zip(("rate_hz", "depth", "centre_frequency_hz", "feedback", "mix"), ps)
                  if v is not None}
             if mr is None:
                 y = phaser_forward(xr, p, lead_rows, self.sr, n)
