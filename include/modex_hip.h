@@ -92,8 +92,10 @@ int mx_flanger_fwd_probe(const float *x, int64_t x_stride, const float *mod, int
                    float *y, int64_t y_stride, float *mod_up, int64_t *dbg_prev, float *dbg_frac, void *stream);
 
 /* Forward of the flanger adjoint -- fx.py:72-119: mx_flanger_fwd (y bit-identical) that also writes the interpolated tap
- * v[n] of fx.py:113 of every sample to stash (B,N), dense rows (row b at stash + b*N).  mod must be full rate: n_mod != N
- * returns MX_ERR_UNSUPPORTED.  Other arguments, limits and the rows subset as mx_flanger_fwd. */
+ * v[n] of fx.py:113 of every sample to stash (B,N), dense rows (row b at stash + b*N).  mod (B,n_mod) as in mx_flanger_fwd:
+ * full rate (adjoint: mx_flanger_bwd) or any 1 <= n_mod < N, resampled in-kernel (adjoint: mx_flanger_bwd_lr); n_mod > N
+ * returns MX_ERR_ARG.  Other arguments, limits (the LDS budget includes the n_mod floats of a resampled row) and the rows
+ * subset as mx_flanger_fwd. */
 int mx_flanger_fwd_stash(const float *x, int64_t x_stride, const float *mod, int64_t n_mod, const float *lfo_scale,
                          const float *min_delay, const float *feedback, const float *depth,
                          const float *mix, const float *one_minus_mix, const int32_t *max_delay,
@@ -114,6 +116,22 @@ int mx_flanger_bwd(const float *dy, int64_t dy_stride, const float *x, int64_t x
                    float *ws, float *dx, int64_t dx_stride, float *dmod, int64_t dmod_stride,
                    double *d_lfo_scale, double *d_min_delay, double *d_feedback, double *d_depth,
                    double *d_mix, void *stream);
+/* mx_flanger_bwd for the LFO row the data path renders from -- fx.py:72-119 behind the align_corners=True resampling of
+ * mod_extraction/util.py:15-29 (linear_interpolate_last_dim, as data_modules.py:455 applies it to the n_samples // 100
+ * label before fx.py sees it).  mod (B,n_mod), 1 <= n_mod <= N, is the row mx_flanger_fwd_stash was given; every sample's
+ * LFO value is recomputed with the forward's own taps and rounding, so slots and fractions are the forward's.  dmod
+ * (B,n_mod), row stride dmod_stride >= n_mod: the transpose of that resampling applied to the per-sample gradient (each
+ * rounded to fp32 once, in ws), one fp64 gather per low-rate point over its contiguous range of samples in a fixed order,
+ * rounded once -- no atomics, no second (B,N) buffer.  d_lfo_scale uses the resampled values.  n_mod == N is
+ * mx_flanger_bwd.  The LDS of the recurrence holds max_delay_max + n_mod floats beside the ring: above FL_MAX_M (34784)
+ * it returns MX_ERR_UNSUPPORTED.  Everything else as mx_flanger_bwd. */
+int mx_flanger_bwd_lr(const float *dy, int64_t dy_stride, const float *x, int64_t x_stride, const float *mod,
+                      int64_t n_mod, const float *stash, const float *lfo_scale, const float *min_delay,
+                      const float *feedback, const float *depth, const float *mix, const float *one_minus_mix,
+                      const int32_t *max_delay, int32_t max_delay_max, const int32_t *rows, int64_t n_rows,
+                      int64_t B, int64_t N, float *ws, float *dx, int64_t dx_stride, float *dmod,
+                      int64_t dmod_stride, double *d_lfo_scale, double *d_min_delay, double *d_feedback,
+                      double *d_depth, double *d_mix, void *stream);
 
 /* Measurement aid (bench.py): `steps` dependent LDS round trips of the flanger lock-step's shape (two ds_read_b32 of the
  * slot the previous step wrote, the five fp32 operations of fx.py:113-115, one ds_write_b32) on one wavefront, nothing

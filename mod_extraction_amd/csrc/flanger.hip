@@ -86,8 +86,7 @@ __global__ __launch_bounds__(FL_THREADS) void flanger_kernel(
             const bool valid = n < N;
             float m;
             if (resample) {
-                InterpTap t = interp_tap(mod_scale, valid ? n : 0, n_mod);
-                m = interp_combine(t, lfo[t.i0], lfo[t.i1]);
+                m = fl_lfo(lfo, mod_scale, valid ? n : 0, n_mod);
                 if (mod_up && valid) mod_up[(size_t)b * N + n] = m;
             } else {
                 m = mr;
@@ -282,15 +281,15 @@ MX_EXPORT int mx_flanger_fwd_probe(const float *x, int64_t x_stride, const float
 }
 
 // Forward of the adjoint (flanger_bwd.hip): mx_flanger_fwd plus the tap v[n] of every sample in stash (B,N), dense rows.
-// The LFO must be full rate (n_mod == N): the adjoint does not differentiate the in-kernel resampling.
+// The LFO is full rate (n_mod == N, adjoint mx_flanger_bwd) or any shorter row resampled in-kernel as in mx_flanger_fwd
+// (adjoint mx_flanger_bwd_lr, which differentiates the resampling).
 MX_EXPORT int mx_flanger_fwd_stash(const float *x, int64_t x_stride, const float *mod, int64_t n_mod, const float *lfo_scale,
                                    const float *min_delay, const float *feedback, const float *depth,
                                    const float *mix, const float *one_minus_mix, const int32_t *max_delay,
                                    int32_t max_delay_max, const int32_t *rows, int64_t n_rows, int64_t B,
                                    int64_t N, float *y, int64_t y_stride, float *stash, void *stream)
 {
-    if (!stash) return MX_ERR_ARG;
-    if (n_mod != N) return MX_ERR_UNSUPPORTED;
+    if (!stash || n_mod > N) return MX_ERR_ARG;
     return flanger_fwd_launch<true>(x, x_stride, mod, n_mod, lfo_scale, min_delay, feedback, depth, mix, one_minus_mix, max_delay,
                                     max_delay_max, rows, n_rows, B, N, y, y_stride, nullptr, nullptr, nullptr, stream, 0, stash);
 }

@@ -40,6 +40,15 @@ __device__ __forceinline__ void fl_slots(int w, float m, float ls, float md, int
     frac = __fsub_rn(r, fl);                                            // fx.py:101
 }
 
+// The LFO value of sample n from a row of n_mod < N points (util.py:15-29, align_corners=True; scale =
+// interp_scale_host(n_mod, N)): the taps of interp_tap and their combination, one definition for the forward's producers
+// and for both adjoint kernels, so that the m -- and with it the slots, fractions and runs -- of a sample agree bit for bit.
+__device__ __forceinline__ float fl_lfo(const float *row, float scale, int n, int n_mod)
+{
+    const InterpTap t = interp_tap(scale, n, n_mod);
+    return interp_combine(t, row[t.i0], row[t.i1]);
+}
+
 // distance back from the write at slot w to the last write of slot s (slot w itself is "M samples ago")
 __device__ __forceinline__ int fl_dist(int w, int s, int M)
 {

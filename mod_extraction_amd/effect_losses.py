@@ -1,6 +1,6 @@
 """Effect-model losses of mod_extraction/losses.py:14-67 (ESR, DC) and nn.L1Loss on HIP tensors:
 one ``mx_effect_loss_sums`` launch gives the per-clip sums all three are built from."""
-from typing import Dict
+from typing import Dict, Optional
 
 import torch
 from torch import Tensor as T, nn
@@ -26,11 +26,13 @@ def effect_loss_terms(y_hat: T, y: T, eps: float = 1e-8) -> Dict[str, T]:
 GRAD_NAMES = ("l1", "mse", "esr", "dc", "mrstft", "log_mel_l1")      # losses whose d/dy_hat the TBPTT step can back-propagate
 
 
-def effect_loss_grad(y_hat: T, y: T, weights: Dict[str, float], eps: float = 1e-8, mrstft=None, logmel=None) -> T:
+def effect_loss_grad(y_hat: T, y: T, weights: Dict[str, float], eps: float = 1e-8, mrstft=None, logmel=None,
+                     values: Optional[Dict[str, T]] = None) -> T:
     """d (sum_k weights[k] * loss_k(y_hat, y)) / d y_hat as a (B, T) tensor -- the backward half of
     ``calc_and_log_losses`` (lightning.py:33-62,380-382) for the effect model's output chunk.  ``mrstft``: a
     ``MultiResolutionSTFTLoss`` module to reuse (window / twiddle tables); ``logmel``: a ``losses.LogMelLoss`` module to
-    reuse (window, twiddle, filter bank and band tables on the device)."""
+    reuse (window, twiddle, filter bank and band tables on the device).  ``values``: a dict that receives the WEIGHTED
+    values (device scalars) the value-and-gradient kernels of mrstft / log_mel_l1 produce alongside their gradients."""
     assert y_hat.shape == y.shape and y_hat.ndim == 3 and y_hat.size(1) == 1
     a, t = y_hat.detach()[:, 0, :], y.detach()[:, 0, :]
     assert a.stride(1) == 1 and t.stride(1) == 1
@@ -43,12 +45,16 @@ def effect_loss_grad(y_hat: T, y: T, weights: Dict[str, float], eps: float = 1e-
     if "mrstft" in w:
         from .mrstft import MultiResolutionSTFTLoss, mrstft_value_and_grad
         mod = mrstft if mrstft is not None else MultiResolutionSTFTLoss()
-        _, dy = mrstft_value_and_grad(mod, a, t, scale=w["mrstft"])
+        value, dy = mrstft_value_and_grad(mod, a, t, scale=w["mrstft"])
+        if values is not None:
+            values["mrstft"] = value
         acc = 1
     if "log_mel_l1" in w:
         from .losses import LogMelLoss, logmel_l1_value_and_grad
         mod = logmel if logmel is not None else LogMelLoss()
-        _, dy = logmel_l1_value_and_grad(mod, a, t, scale=w["log_mel_l1"], dx=dy, accumulate=bool(acc))
+        value, dy = logmel_l1_value_and_grad(mod, a, t, scale=w["log_mel_l1"], dx=dy, accumulate=bool(acc))
+        if values is not None:
+            values["log_mel_l1"] = value
         acc = 1
     if dy is None:
         dy = torch.empty((B, Tn), device=a.device, dtype=torch.float32)

@@ -1,8 +1,8 @@
 """Host mirror of mod_extraction/fx.py: same class, constructor and forward signature
 (fx.py:25-44,121-130); the per-sample delay-line recurrence runs in the ``mx_flanger_fwd`` HIP
 kernel (one wavefront per clip, delay line in LDS) instead of 88 200 python iterations.
-``apply_effect`` is differentiable (``mx_flanger_fwd_stash`` + ``mx_flanger_bwd``) when grad mode is on and an input
-requires grad.  ``PhaserModule`` is the same for the phaser (``mx_phaser_fwd_stash`` + ``mx_phaser_bwd``), with the LFO
+``apply_effect`` is differentiable (``mx_flanger_fwd_stash`` + ``mx_flanger_bwd`` / ``mx_flanger_bwd_lr``) when grad mode
+is on and an input requires grad; mod_sig may be full rate or the low-rate row the kernel resamples itself.  ``PhaserModule`` is the same for the phaser (``mx_phaser_fwd_stash`` + ``mx_phaser_bwd``), with the LFO
 either JUCE's built-in oscillator or an external signal.
 """
 from typing import Dict, Optional, Tuple, Union
@@ -113,12 +113,12 @@ def flanger_forward_stash(x: T, mod_sig: T, consts: Dict[str, T], max_delay: T, 
                           rows: Optional[T] = None, out: Optional[T] = None,
                           stash: Optional[T] = None) -> Tuple[T, T]:
     """Launch mx_flanger_fwd_stash: ``flanger_forward`` (same y, bit for bit) that also returns the tap v[n] of fx.py:113 of
-    every sample, (B,N) dense, for ``flanger_backward``.  mod_sig must be full rate (B,N)."""
+    every sample, (B,N) dense, for ``flanger_backward``.  mod_sig (B,n_mod), n_mod == N or shorter (resampled in-kernel)."""
     B, N = x.shape
-    assert mod_sig.shape == (B, N)
+    assert mod_sig.ndim == 2 and mod_sig.size(0) == B and 1 <= mod_sig.size(1) <= N
     y = out if out is not None else torch.empty_like(x)
     st = stash if stash is not None else torch.empty((B, N), device=x.device, dtype=torch.float32)
-    _hip.call("mx_flanger_fwd_stash", *_rows_view(x), _hip.ptr(mod_sig), N,
+    _hip.call("mx_flanger_fwd_stash", *_rows_view(x), _hip.ptr(mod_sig), mod_sig.size(1),
               _hip.ptr(consts["lfo_scale"]), _hip.ptr(consts["min_delay"]), _hip.ptr(consts["feedback"]),
               _hip.ptr(consts["depth"]), _hip.ptr(consts["mix"]), _hip.ptr(consts["one_minus_mix"]),
               _hip.ptr(max_delay), int(max_delay_max), *_rows_arg(rows),
@@ -127,28 +127,35 @@ def flanger_forward_stash(x: T, mod_sig: T, consts: Dict[str, T], max_delay: T, 
 
 
 PARAM_GRADS = ("lfo_scale", "min_delay", "feedback", "depth", "mix")
+FLANGER_MAX_DELAY_SAMPLES = 34784      # csrc/flanger_common.h FL_MAX_M: delay line + a resampled LFO row, in LDS
 
 
 def flanger_backward(dy: T, x: T, mod_sig: T, stash: T, consts: Dict[str, T], max_delay: T, max_delay_max: int,
                      rows: Optional[T] = None, need_dx: bool = True, need_dmod: bool = True,
                      params: Tuple[str, ...] = PARAM_GRADS, dx: Optional[T] = None,
                      dmod: Optional[T] = None) -> Tuple[Optional[T], Optional[T], Dict[str, T]]:
-    """Launch mx_flanger_bwd: the adjoint of fx.py:72-119 (the gradient the DESIGN K-table row defines).
-    dy, x: (B,N) views with contiguous rows; mod_sig, stash (B,N) dense.  Returns dx, dmod (B,N) (None unless asked for)
-    and the per-clip fp64 gradients of the constants named in ``params`` (d mix includes the one_minus_mix path)."""
+    """Launch mx_flanger_bwd (mod_sig at full rate) or mx_flanger_bwd_lr (a shorter mod_sig, as the stash forward was
+    given): the adjoint of fx.py:72-119 (the gradient the DESIGN K-table row defines).
+    dy, x: (B,N) views with contiguous rows; stash (B,N) and mod_sig (B,n_mod) dense.  Returns dx (B,N), dmod (B,n_mod)
+    (None unless asked for) and the per-clip fp64 gradients of the constants named in ``params`` (d mix includes the
+    one_minus_mix path)."""
     B, N = x.shape
     dev = x.device
+    n_mod = mod_sig.size(1)
+    assert mod_sig.ndim == 2 and mod_sig.size(0) == B and 1 <= n_mod <= N
     if dy.stride(-1) != 1 or dy.stride(0) < N:            # e.g. the expanded ones of y.sum().backward()
         dy = dy.contiguous()
     if need_dx and dx is None:
         dx = torch.empty((B, N), device=dev, dtype=torch.float32)
     if need_dmod and dmod is None:
-        dmod = torch.empty((B, N), device=dev, dtype=torch.float32)
+        dmod = torch.empty((B, n_mod), device=dev, dtype=torch.float32)
+    assert not need_dmod or dmod.size(1) == n_mod
     dxp, dxs = _rows_view(dx) if need_dx else (None, 0)
     dmp, dms = _rows_view(dmod) if need_dmod else (None, 0)
     grads = {k: torch.zeros((B,), device=dev, dtype=torch.float64) for k in params}
     ws = torch.empty((B, N), device=dev, dtype=torch.float32)
-    _hip.call("mx_flanger_bwd", *_rows_view(dy), *_rows_view(x), _hip.ptr(mod_sig), _hip.ptr(stash),
+    entry = ("mx_flanger_bwd", ()) if n_mod == N else ("mx_flanger_bwd_lr", (n_mod,))
+    _hip.call(entry[0], *_rows_view(dy), *_rows_view(x), _hip.ptr(mod_sig), *entry[1], _hip.ptr(stash),
               _hip.ptr(consts["lfo_scale"]), _hip.ptr(consts["min_delay"]), _hip.ptr(consts["feedback"]),
               _hip.ptr(consts["depth"]), _hip.ptr(consts["mix"]), _hip.ptr(consts["one_minus_mix"]),
               _hip.ptr(max_delay), int(max_delay_max), *_rows_arg(rows), B, N,
@@ -217,8 +224,9 @@ class MonoFlangerChorusModule(nn.Module):
                      mix: Param) -> T:
         """fx.py:72-119 (the per-sample loop) = one kernel launch here; ``forward`` is this under no_grad, as in the
         reference.  With grad mode on and x, mod_sig or a tensor parameter requiring grad, the output carries a grad_fn
-        (``mx_flanger_fwd_stash`` forward, ``mx_flanger_bwd`` backward; y is the same, bit for bit).  mod_sig must then be
-        full rate; python-float parameters get no gradient."""
+        (``mx_flanger_fwd_stash`` forward, ``mx_flanger_bwd`` backward; y is the same, bit for bit).  mod_sig is full rate
+        or any shorter row, which the kernel resamples as ``forward`` does (``mx_flanger_bwd_lr`` backward): its gradient has
+        mod_sig's own shape.  Python-float parameters get no gradient."""
         params = (feedback, min_delay_width, width, depth, mix)
         if torch.is_grad_enabled() and (x.requires_grad or mod_sig.requires_grad or
                                         any(isinstance(p, T) and p.requires_grad for p in params)):
@@ -226,14 +234,14 @@ class MonoFlangerChorusModule(nn.Module):
         return self.forward(x, mod_sig, feedback, min_delay_width, width, depth, mix)
 
     def _prepare(self, x: T, mod_sig: T, feedback: Param, min_delay_width: Param, width: Param, depth: Param,
-                 mix: Param, full_rate: bool):
+                 mix: Param):
         """The checks, the per-clip constants and the rows both paths launch on.  n_ch > 1 (fx.py:81-85,104-115): every
         channel owns a delay line = one kernel row per (clip, channel); a clip's channels share its parameters (the (bs,)
         constants are returned as they are); mod_sig (bs, n) / (bs, 1, n) is shared by the channels."""
         assert x.ndim == 3
         bs, n_ch, n = x.shape
         assert n_ch == self.n_ch
-        assert mod_sig.size(0) == bs and (not full_rate or mod_sig.size(-1) == n)
+        assert mod_sig.size(0) == bs
         if mod_sig.ndim == 3:
             assert mod_sig.size(1) in (1, n_ch)
         consts = derive_clip_constants(bs, x.device, self.max_min_delay_samples, self.max_lfo_delay_samples,
@@ -249,7 +257,7 @@ class MonoFlangerChorusModule(nn.Module):
 
     def _apply_effect_grad(self, x: T, mod_sig: T, feedback: Param, min_delay_width: Param, width: Param, depth: Param,
                            mix: Param) -> T:
-        xr, mr, consts, shape = self._prepare(x, mod_sig, feedback, min_delay_width, width, depth, mix, full_rate=True)
+        xr, mr, consts, shape = self._prepare(x, mod_sig, feedback, min_delay_width, width, depth, mix)
         y = _FlangerFunction.apply(xr, mr, consts["lfo_scale"], consts["min_delay"], consts["feedback"], consts["depth"],
                                    consts["mix"], consts["one_minus_mix"], self.n_ch, self.max_delay_samples)
         return y.view(shape)
@@ -257,8 +265,7 @@ class MonoFlangerChorusModule(nn.Module):
     def forward(self, x: T, mod_sig: T, feedback: Param = 0.0, min_delay_width: Param = 1.0,
                 width: Param = 1.0, depth: Param = 1.0, mix: Param = 1.0) -> T:
         with torch.no_grad():
-            xr, mr, consts, shape = self._prepare(x, mod_sig, feedback, min_delay_width, width, depth, mix,
-                                                  full_rate=False)
+            xr, mr, consts, shape = self._prepare(x, mod_sig, feedback, min_delay_width, width, depth, mix)
             consts = {k: _per_row(v, self.n_ch) for k, v in consts.items()}
             md = torch.full((xr.size(0),), self.max_delay_samples, device=x.device, dtype=torch.int32)
             y = flanger_forward(xr, mr, consts, md, self.max_delay_samples)

@@ -160,6 +160,234 @@ class LFOExtraction(BaseLightingModule):
             return step(batch, is_training=False)
 
 
+class _FlangerAudioLossFn(torch.autograd.Function):
+    """loss = sum_k w_k loss_k(flanger(dry, mod_sig_hat), wet) as ONE autograd node.  Its forward runs the stash forward
+    (``mx_flanger_fwd_stash`` on the low-rate LFO), the value-and-gradient kernels of the weighted losses
+    (``effect_loss_grad``) and the flanger adjoint (``mx_flanger_bwd_lr``) at once and keeps only d loss / d mod_sig_hat
+    (B, n_frames): the (B, N) stash, d loss / d wet_hat and the adjoint's workspace do not outlive the call.  Returns
+    (loss, wet_hat (B, N)); ``terms`` receives the unweighted value of every weighted loss."""
+
+    @staticmethod
+    def forward(ctx, mod_sig_hat, step, dry, wet, consts, terms):
+        from . import fx
+        from .effect_losses import effect_loss_grad, effect_loss_terms
+        mod = mod_sig_hat.detach().float().contiguous()
+        md, M = step._max_delay_rows(dry.size(0), dry.device), step.max_delay_samples
+        wet_hat, stash = fx.flanger_forward_stash(dry, mod, consts, md, M)
+        a, t = wet_hat.unsqueeze(1), wet.unsqueeze(1)
+        weighted: Dict[str, T] = {}
+        dy = effect_loss_grad(a, t, step.audio_loss_dict, values=weighted, **step._grad_modules())
+        _, dmod, _ = fx.flanger_backward(dy, dry, mod, stash, consts, md, M, need_dx=False, params=())
+        w = {k: v for k, v in step.audio_loss_dict.items() if v > 0}
+        terms.update({k: v / w[k] for k, v in weighted.items()})
+        if any(k in w for k in ("l1", "mse", "esr", "dc")):
+            terms.update({k: v for k, v in effect_loss_terms(a, t).items() if k in w})
+        loss = None
+        for k, wk in w.items():
+            loss = wk * terms[k] if loss is None else loss + wk * terms[k]
+        ctx.save_for_backward(dmod)
+        ctx.mark_non_differentiable(wet_hat)
+        return loss, wet_hat
+
+    @staticmethod
+    def backward(ctx, g, _g_wet_hat):
+        (dmod,) = ctx.saved_tensors
+        return dmod * g, None, None, None, None, None
+
+
+class LFOExtractionThroughEffect(BaseLightingModule):
+    """Trains the LFO extractor on dry / wet pairs WITHOUT an LFO label: the extractor's LFO drives the differentiable
+    flanger / chorus on ``dry`` and an audio-domain loss compares the result with ``wet``.  The reference has no such step
+    (its lightning.py:65-199 trains against the ground-truth LFO only; its flanger, fx.py:72-119, has no usable autograd).
+
+    Same batch 4-tuple ``(dry, wet, mod_sig, fx_params)`` and metric naming as ``LFOExtraction``; ``training_step`` returns a
+    loss with a grad graph, so ``trainer.Trainer`` drives it unchanged.
+    * ``max_min_delay_ms`` / ``max_lfo_delay_ms``: ONE flanger or chorus geometry per module, as in
+      ``fx.MonoFlangerChorusModule`` (batches that mix geometries are out of scope; so are phaser rows, whose render needs
+      lead-in samples the batch does not carry).
+    * ``fx_params`` carries the per-clip ``feedback``, ``min_delay_width``, ``width``, ``depth``, ``mix`` as (B,) tensors
+      (``check_fx_params``: range-check them on every step, which costs host synchronisations).
+    * ``audio_loss_dict``: names from ``effect_losses.GRAD_NAMES``; zero-weight names are only logged.
+    * ``loss_dict`` (optional, default none): an LFO-domain term (lightning.py:33-62) added to the loss when the batch carries
+      ``mod_sig``; it is logged as ``{prefix}/lfo_{name}``.
+    The LFO enters the flanger at the extractor's own rate (n_frames points, resampled in-kernel exactly as the data path
+    resamples its n_samples // 100 label), so a re-render from the label the batch was rendered with is bit-identical to
+    ``wet`` and every loss is exactly 0 there.
+
+    ``model_smooth_n_frames`` > 1 applies the moving average (with its transpose in the backward) and centre-crops dry and
+    wet by the rule of ``TBPTTLFOEffectModeling._prepare_all_rows``.  One limit of that crop: the re-render starts from an
+    EMPTY delay line at the first cropped sample, whereas the recorded wet had the samples before the crop in its line, so
+    the first ``max_delay_samples`` samples of ``wet_hat`` differ from ``wet`` even for the true LFO.  The default is
+    therefore no smoothing.  ``should_stretch`` is not wired in (the corner stretch has a backward, but not on this path)."""
+    default_audio_loss_dict = {"mrstft": 1.0}
+
+    def __init__(self,
+                 model: nn.Module,
+                 sr: float = 44100,
+                 use_dry: bool = True,
+                 model_smooth_n_frames: int = 0,
+                 max_min_delay_ms: float = 1.0,
+                 max_lfo_delay_ms: float = 10.0,
+                 audio_loss_dict: Optional[Dict[str, float]] = None,
+                 loss_dict: Optional[Dict[str, float]] = None,
+                 should_stretch: bool = False,
+                 check_fx_params: bool = False) -> None:
+        super().__init__({} if loss_dict is None else loss_dict)
+        from . import fx
+        from .effect_losses import GRAD_NAMES
+        if should_stretch:
+            raise NotImplementedError("should_stretch is not supported when training through the rendered effect")
+        audio_loss_dict = dict(self.default_audio_loss_dict if audio_loss_dict is None else audio_loss_dict)
+        for name, w in audio_loss_dict.items():
+            if w > 0 and name not in GRAD_NAMES:
+                raise NotImplementedError(f"audio loss '{name}' has no gradient kernel (supported: {GRAD_NAMES})")
+        if not any(w > 0 for w in audio_loss_dict.values()):
+            raise ValueError("audio_loss_dict needs at least one loss with a weight above 0")
+        if max_min_delay_ms < 0 or max_lfo_delay_ms < 0:
+            raise ValueError("max_min_delay_ms and max_lfo_delay_ms must not be negative")
+        self.max_min_delay_samples = fx.delay_samples(max_min_delay_ms, sr)
+        self.max_lfo_delay_samples = fx.delay_samples(max_lfo_delay_ms, sr)
+        self.max_delay_samples = self.max_min_delay_samples + self.max_lfo_delay_samples
+        if not 2 <= self.max_delay_samples <= fx.FLANGER_MAX_DELAY_SAMPLES:
+            raise ValueError(f"delay line of {self.max_delay_samples} samples: the flanger kernels keep it in LDS and support "
+                             f"2 .. {fx.FLANGER_MAX_DELAY_SAMPLES} samples (LFO row included)")
+        self.model = model
+        self.sr, self.use_dry = sr, use_dry
+        self.model_smooth_n_frames = model_smooth_n_frames
+        self.max_min_delay_ms, self.max_lfo_delay_ms = max_min_delay_ms, max_lfo_delay_ms
+        self.check_fx_params = check_fx_params
+        self.audio_loss_dict = audio_loss_dict
+        # the base class holds the LFO-domain term; loss_dict names every metric this step logs (trainer.metric_names)
+        self.lfo_loss_dict = self.loss_dict
+        self.loss_dict = dict(audio_loss_dict, **{f"lfo_{k}": w for k, w in self.lfo_loss_dict.items()})
+        self._extra_losses = {}
+        self._md = None
+
+    center_crop_mod_sig = staticmethod(LFOExtraction.center_crop_mod_sig)
+
+    def _loss_module(self, name: str):
+        """One module per loss name for the lifetime of the step (device tables are built once)."""
+        mod = self._extra_losses.get(name)
+        if mod is None:
+            mod = self._extra_losses[name] = L.get_loss_func_by_name(name)
+        return mod
+
+    def _grad_modules(self):
+        return {"mrstft": self._loss_module("mrstft") if "mrstft" in self.audio_loss_dict else None,
+                "logmel": self._loss_module("log_mel_l1") if "log_mel_l1" in self.audio_loss_dict else None}
+
+    def _max_delay_rows(self, bs: int, device) -> T:
+        if self._md is None or self._md.size(0) != bs or self._md.device != device:
+            self._md = torch.full((bs,), self.max_delay_samples, device=device, dtype=torch.int32)
+        return self._md
+
+    def clip_constants(self, fx_params, bs: int, device) -> Dict[str, T]:
+        from . import fx
+        return fx.derive_clip_constants(bs, device, self.max_min_delay_samples, self.max_lfo_delay_samples,
+                                        fx_params["feedback"], fx_params["min_delay_width"], fx_params["width"],
+                                        fx_params["depth"], fx_params["mix"], check=self.check_fx_params)
+
+    @staticmethod
+    def _rows(audio: T) -> T:
+        assert audio.ndim == 3 and audio.size(1) == 1, "mono clips (B, 1, N)"
+        return audio[:, 0, :]
+
+    def render(self, dry: T, mod_sig: T, fx_params) -> T:
+        """wet_hat (B, 1, N) = the flanger of ``dry`` (B, 1, N) driven by ``mod_sig`` (B, n_mod) at its own rate, with the
+        per-clip constants of ``fx_params``; no graph (``mx_flanger_fwd``, the data path's launch)."""
+        from . import fx
+        rows = self._rows(dry)
+        with torch.no_grad():
+            consts = self.clip_constants(fx_params, rows.size(0), rows.device)
+            y = fx.flanger_forward(rows, mod_sig.detach().float().contiguous(), consts,
+                                   self._max_delay_rows(rows.size(0), rows.device), self.max_delay_samples)
+        return y.unsqueeze(1)
+
+    def audio_loss(self, mod_sig_hat: T, dry: T, wet: T, fx_params, prefix: Optional[str] = None):
+        """(loss, wet_hat (B, 1, N)) for an LFO (B, n_frames); with grad mode on and an LFO that requires grad the loss
+        carries the graph of ``_FlangerAudioLossFn``, otherwise nothing is stashed and no backward kernel runs.  ``prefix``:
+        log every audio term under it."""
+        from .effect_losses import effect_loss_terms
+        dry_r, wet_r = self._rows(dry), self._rows(wet)
+        terms: Dict[str, T] = {}
+        if torch.is_grad_enabled() and mod_sig_hat.requires_grad:
+            with torch.no_grad():
+                consts = self.clip_constants(fx_params, dry_r.size(0), dry_r.device)
+            loss, wet_hat = _FlangerAudioLossFn.apply(mod_sig_hat, self, dry_r, wet_r, consts, terms)
+            wet_hat = wet_hat.unsqueeze(1)
+        else:
+            wet_hat, loss = self.render(dry, mod_sig_hat, fx_params), None
+        if prefix is not None or loss is None:
+            with torch.no_grad():
+                missing = [k for k in self.audio_loss_dict if k not in terms]
+                if any(k in ("l1", "mse", "esr", "dc") for k in missing):
+                    terms.update({k: v for k, v in effect_loss_terms(wet_hat, wet).items() if k in missing})
+                for k in missing:
+                    if k not in terms:
+                        terms[k] = self._loss_module(k)(wet_hat, wet)
+            if loss is None:
+                for k, w in self.audio_loss_dict.items():
+                    if w > 0:
+                        loss = w * terms[k] if loss is None else loss + w * terms[k]
+            if prefix is not None:
+                for k in self.audio_loss_dict:
+                    self.log(f"{prefix}/{k}", terms[k])
+        return loss, wet_hat
+
+    def _lfo_term(self, mod_sig_hat: T, mod_sig: T, prefix: str) -> Optional[T]:
+        """lightning.py:33-62 on the LFO itself (the optional supervised term)."""
+        if self._fused_lfo:
+            loss, terms = L.lfo_loss(mod_sig_hat, mod_sig, self.lfo_loss_dict)
+        else:
+            terms = {name: f(mod_sig_hat, mod_sig) for name, f in zip(self.lfo_loss_dict, self.loss_funcs)}
+            loss = None
+            for name, w in self.lfo_loss_dict.items():
+                if w > 0:
+                    loss = w * terms[name] if loss is None else loss + w * terms[name]
+        for name in self.lfo_loss_dict:
+            self.log(f"{prefix}/lfo_{name}", terms[name])
+        return loss
+
+    def common_step(self, batch, is_training: bool):
+        prefix = "train" if is_training else "val"
+        dry, wet, mod_sig, fx_params = batch
+        assert dry is not None and fx_params is not None, "the re-render needs the dry clip and the effect parameters"
+        mod_sig_hat, _ = self.model(stack_dry_wet(dry, wet) if self.use_dry else wet)
+        mod_sig_hat = mod_sig_hat.squeeze(1)
+        if mod_sig is not None:
+            mod_sig = linear_interpolate_last_dim(mod_sig, mod_sig_hat.size(-1), align_corners=True)
+        if self.model_smooth_n_frames > 1:
+            n_frames_in = mod_sig_hat.size(-1)
+            if mod_sig_hat.requires_grad and torch.is_grad_enabled():
+                mod_sig_hat = smoothen_with_grad(mod_sig_hat, self.model_smooth_n_frames)
+            else:
+                mod_sig_hat = smoothen(mod_sig_hat, self.model_smooth_n_frames)
+            n_frames = mod_sig_hat.size(-1)
+            if mod_sig is not None:
+                mod_sig = self.center_crop_mod_sig(mod_sig, n_frames)
+            n_samples = int((n_frames / n_frames_in) * dry.size(-1))            # TBPTTLFOEffectModeling._prepare_all_rows
+            dry = self.center_crop_mod_sig(dry, n_samples).contiguous()
+            wet = self.center_crop_mod_sig(wet, n_samples).contiguous()
+        loss, wet_hat = self.audio_loss(mod_sig_hat, dry, wet, fx_params, prefix)
+        if self.lfo_loss_dict and mod_sig is not None:
+            lfo_term = self._lfo_term(mod_sig_hat, mod_sig.contiguous(), prefix)
+            if lfo_term is not None:
+                loss = loss + lfo_term
+        self.log(f"{prefix}/loss", loss)
+        data_dict = {"dry": dry.detach(), "wet": wet.detach(), "wet_hat": wet_hat.detach(),
+                     "mod_sig_hat": mod_sig_hat.detach()}
+        if mod_sig is not None:
+            data_dict["mod_sig"] = mod_sig.detach()
+        return loss, data_dict, fx_params
+
+    def training_step(self, batch, batch_idx: int = 0) -> T:
+        return self.common_step(batch, is_training=True)[0]
+
+    def validation_step(self, batch, batch_idx: int = 0):
+        with torch.no_grad():
+            return self.common_step(batch, is_training=False)
+
+
 def _channel_rows(t: T) -> T:
     """(B, C, T) -> (B C, 1, T): the effect-model losses reduce over clips AND channels alike (losses.py:33-38,61-66: a mean over
     (batch, channel) of per-row ratios; nn.L1Loss: a mean over everything)."""
