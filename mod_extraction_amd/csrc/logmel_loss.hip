@@ -6,26 +6,20 @@
 // Gradient, torch's conventions (sgn(0) = 0; the clamp passes where M >= eps):
 //   dM[m] = c sgn(la - lb) [M_a >= eps] / M_a  with c = scale / count,   dP[k] = sum_m fb[k, m] dM[m],   dL/dX[k] = 2 dP[k] X[k],
 // then window, overlap-add by hop and the fold of the reflect padding.  c is known up front, so the time-domain gradient is
-// complete once a frame's bins are: the scheme of mrstft.hip's one-pass kernel with a single gradient component.
-//   lm_onepass : a STREAM (64 lanes; 32 for N = 512) walks a RUN of F consecutive frames of one clip, two frames at a time.  Per
-//                frame: one forward transform of the prediction frame and one of the target frame (real input each: a packed
+// complete once a frame's bins are: the pipeline of ola_ring.h (runs, frame pairs, ring, tails, fold) with a single gradient
+// component.
+//   lm_onepass : per frame: one forward transform of the prediction frame and one of the target frame (real input each: a packed
 //                x + i y transform leaves the rounding of the louder frame on both spectra, and the log-domain gradient of a
 //                weak band amplifies it) -> both powers P_a, P_b into the stream's exchange buffer -> the lanes take the mel
 //                bands over their non-zero bin ranges (band_lo / band_hi, coefficients packed in LDS) -> |la - lb| into the
 //                partial and dM into LDS -> each lane gathers dP of its bins over the (at most two, for a triangular bank)
-//                bands that contain them -> gradient spectrum.  The pair's two gradient spectra are completed to Hermitian
-//                ones and go through ONE inverse transform as G~_a + i G~_b; the windowed frames are overlap-added in a
-//                stream-private LDS ring and leave for memory `hop` positions at a time; the ring's last N - hop positions
-//                leave as the run's TAIL.  Nothing per bin is written to memory.  Without dx: no dM, no inverse transform, no ring.
+//                bands that contain them -> gradient spectrum -> the pair's inverse transform and the ring.  Without dx: no
+//                dM, no inverse transform, no ring.
 //   finish     : value = scale * (sum of the fp64 per-workgroup partials, fixed order) / count
-//   fold       : dx[n] (+)= the padded positions that map to n: run sums + the tails of the (<= 2) earlier runs -- a gather,
-//                deterministic, no atomics.
+//   fold       : dx[n] (+)= the gradient at the padded positions that map to n
 // Exact zeros: bit-identical (or negated) prediction and target frames go through the same arithmetic, so la == lb and the
 // frame contributes 0 to the value and the gradient; an all-zero frame has power 0 exactly.
-#include "wave_fft.h"
-#include "spectral_pair.h"
-
-#define LM_RUN_MIN 32    // frames per run (at least ceil(N / hop): a position then lies in at most two earlier runs' tails)
+#include "ola_ring.h"
 
 template <int N> struct LM {
     static constexpr int L = WF<N>::L, E = WF<N>::E, NB = WF<N>::NB, FW = WF<N>::FW;
@@ -35,10 +29,10 @@ template <int N> struct LM {
     static constexpr int NK = N / 2 + 1;                       // bins of the one-sided spectrum
 };
 
-// Dynamic LDS, in this order (each part a multiple of 8 bytes, rings first: a ring slot's byte address is
-// (position bytes & (4 N - 1)) | ring base):  rings (STREAMS x N floats) | twiddles (N cf) | exchange buffers (STREAMS x LEN cf) |
-// reduction (WAVES doubles) | dM (STREAMS x n_mels floats) | packed coefficients (coef_cap floats) | boff (n_mels + 1 ints) |
-// band_lo (n_mels ints) | band range of every bin: lo, hi (2 x NK ints)
+// Dynamic LDS, in this order (each part a multiple of 8 bytes; rings first: ola_ring.h):  rings (STREAMS x N floats) |
+// twiddles (N cf) | exchange buffers (STREAMS x LEN cf) | reduction (WAVES doubles) | dM (STREAMS x n_mels floats) |
+// packed coefficients (coef_cap floats) | boff (n_mels + 1 ints) | band_lo (n_mels ints) | band range of every bin: lo, hi
+// (2 x NK ints)
 __host__ __device__ __forceinline__ size_t lm_align8(size_t v) { return (v + 7) & ~(size_t)7; }
 template <int N> static size_t lm_lds_bytes(int n_mels, int coef_cap)
 {
@@ -52,7 +46,7 @@ template <int N, bool GRAD>
 __global__ __launch_bounds__(LM<N>::WAVES * 64) void lm_onepass_kernel(
     const float *__restrict__ x, long long xs, const float *__restrict__ y, long long ys, const float *__restrict__ win,
     const float2 *__restrict__ tw, const float *__restrict__ fb, const int *__restrict__ band_lo, const int *__restrict__ band_hi,
-    int n_mels, int coef_cap, int T, int hop, int n_frames, int F, int n_runs, float eps, float c, double *__restrict__ part,
+    int n_mels, int coef_cap, int T, int hop, OlaRuns rg, float eps, float c, double *__restrict__ part,
     float *__restrict__ mainp, float *__restrict__ tails)
 {
     using K = LM<N>;
@@ -78,16 +72,14 @@ __global__ __launch_bounds__(LM<N>::WAVES * 64) void lm_onepass_kernel(
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane / L, a_ = lane % L;
     const int b = blockIdx.y, sidx = wave * FW + g;
+    const int n_frames = rg.n_frames, F = rg.F;
     const float *xb = x + (size_t)b * xs, *yb = y + (size_t)b * ys;
     cf *buf = xbuf + (size_t)sidx * WF<N>::LEN;
     float *pw = reinterpret_cast<float *>(buf);                   // P_a[k] at k, P_b[k] at NK + k (2 NK <= 2 LEN floats)
     float *dm = dm_all + (size_t)sidx * n_mels;
 
     // ---- per workgroup: twiddles, band tables (ranges clamped to the spectrum), packed coefficients, the band range of every bin
-    for (int m = tid; m < N; m += NT) {
-        const float2 w = tw[m];
-        tw_s[m] = {w.x, w.y};
-    }
+    stage_twiddles<N, 1, NT>(tw_s, tw);
     for (int k = tid; k < NK; k += NT) { kbl[k] = n_mels; kbh[k] = 0; }
     if (GRAD)
         for (int j = a_; j < N; j += L) rings[(size_t)sidx * N + j] = 0.0f;
@@ -144,23 +136,16 @@ __global__ __launch_bounds__(LM<N>::WAVES * 64) void lm_onepass_kernel(
     fft_lane_setup<N, 1>(fl, buf, tw_s, tw, a_);
     const int run = blockIdx.x * STREAMS + sidx;
     const int f_begin = run * F, f_end = min(f_begin + F, n_frames);          // (an idle stream: f_begin >= f_end)
-    const int tail_len = N > hop ? N - hop : 0;
     float wv[E];                                                              // the lane's window values: positions a + L m
 #pragma unroll
     for (int m = 0; m < E; ++m) wv[m] = win[a_ + L * m];
-    double s_l = 0.0;
+    double s_l[1] = {0.0};
     int base = 0;                                                             // ring slot of the current frame's position 0
     const unsigned ring_b = (unsigned)sidx * 4u * N;
     float *mb = GRAD ? mainp + (size_t)b * n_frames * hop : nullptr;
 
-    cf raw[NB][4];
-    auto fetch = [&](int f, int a) {
-        const int fl_ = f < f_end ? f : (n_frames - 1);                        // dead slots transform a valid frame and contribute nothing
-        const bool inter_lane = fl_ * hop - N / 2 >= 0 && fl_ * hop + N / 2 <= T;
-        if (__ballot(!inter_lane) == 0ull) fetch_frame<N, true>(raw, xb, yb, fl_, hop, T, a);
-        else fetch_frame<N, false>(raw, xb, yb, fl_, hop, T, a);
-    };
-    fetch(f_begin, a_);
+    cf raw[NB][4];                                                            // the next frame's unwindowed samples
+    prefetch_frame<N>(raw, xb, yb, f_begin, f_end, n_frames, hop, T, a_);
     for (int fp = 0; fp < F; fp += 2) {
         int a = a_;
         asm volatile("" : "+v"(a));                                           // see mr_onepass_kernel
@@ -168,7 +153,7 @@ __global__ __launch_bounds__(LM<N>::WAVES * 64) void lm_onepass_kernel(
         if (__ballot(f0 < f_end) == 0ull) break;                               // every stream of the wavefront is done
         const bool live0 = f0 < f_end, live1 = f1 < f_end;
         cf ga[NBIN];                                                           // G~ of frame f0 at the lane's bins
-        float nya = 0.0f;                                                      // ... and at the Nyquist bin (real; lane 0)
+        float nya = 0.0f, nyb = 0.0f;                                          // ... and of both frames at the Nyquist bin (real; lane 0)
         cf R[NB][4], Z[E];
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
@@ -185,8 +170,8 @@ __global__ __launch_bounds__(LM<N>::WAVES * 64) void lm_onepass_kernel(
                 for (int bq = 0; bq < NB; ++bq)
 #pragma unroll
                     for (int cq = 0; cq < 4; ++cq)
-                        R[bq][cq] = cf{(sg ? raw[bq][cq].y : raw[bq][cq].x) * wv[bq + (N / 4 / L) * cq], 0.0f};
-                if (sg) fetch(u ? f0 + 2 : f1, a);                             // the next frame, in flight during this transform
+                        R[bq][cq] = cf{(sg ? raw[bq][cq].y : raw[bq][cq].x) * wv[m_of_in<N>(bq, cq)], 0.0f};
+                if (sg) prefetch_frame<N>(raw, xb, yb, u ? f0 + 2 : f1, f_end, n_frames, hop, T, a);     // in flight during this transform
                 wave_fft<N, false>(R, Z, fl);
 #pragma unroll
                 for (int i = 0; i < E; ++i) buf[pos_final<N>(i, a)] = Z[i];
@@ -238,7 +223,7 @@ __global__ __launch_bounds__(LM<N>::WAVES * 64) void lm_onepass_kernel(
                     dm[m] = (live && ma >= eps) ? sg / ma : 0.0f;
                 }
             }
-            if (live) s_l += (double)(0.69314718055994531f * fsum);
+            if (live) s_l[0] += (double)(0.69314718055994531f * fsum);
             if (GRAD) {
                 __builtin_amdgcn_wave_barrier();
                 // dP of the lane's bins over the bands that contain them; G~[k] = dP X (= G / 2, the Hermitian completion's
@@ -255,84 +240,27 @@ __global__ __launch_bounds__(LM<N>::WAVES * 64) void lm_onepass_kernel(
                     const bool dc = (j == 0) && (a == 0);
                     const float dp = dpk(k);
                     const cf gk = Xs[j] * (dc ? 2.0f * dp : dp);
-                    if (u == 0) {
-                        ga[j] = gk;
-                    } else {
-                        // H = G~_a + i G~_b at position k (lower half) and its mirror image conj G~_a + i conj G~_b at N - k
-                        const cf p = ga[j];
-                        R[j % NB][j / NB] = dc ? cf{p.x, gk.x} : add_pi(p, gk);
-                        buf[N - k] = mirror_h(p, gk);                          // (k = 0 lands in the pad: never read)
-                    }
+                    if (u == 0) ga[j] = gk;
+                    else place_pair<N>(R, buf, j, a, pair_h(dc, ga[j], gk), mirror_h(ga[j], gk));
                 }
                 if (a == 0) {
                     const float nv = 2.0f * dpk(N / 2) * xny;
                     if (u == 0) nya = nv;
-                    else buf[N / 2] = {nya, nv};
+                    else nyb = nv;
                 }
             }
             __builtin_amdgcn_wave_barrier();
         }
         if (GRAD) {
-#pragma unroll
-            for (int bq = 0; bq < NB; ++bq)
-#pragma unroll
-                for (int cq = 2; cq < 4; ++cq) R[bq][cq] = buf[a + L * bq + (N / 4) * cq];
-            __builtin_amdgcn_wave_barrier();
+            pair_finish<N>(R, buf, a, nya, nyb);
             wave_fft<N, true>(R, Z, fl);
             asm volatile("" : "+v"(a));
-            // the pair's windowed gradient frames (real part: f0 at ring position base, imaginary part: f1 at base + hop) ->
-            // ring (read - add - write); after each frame its first `hop` positions are final within the run and leave
-            cf Zw[E];
-#pragma unroll
-            for (int i = 0; i < E; ++i) Zw[i] = Z[i] * wv[pos_final<N>(i, 0) / L];
-#pragma unroll
-            for (int u = 0; u < 2; ++u) {
-                const int f = f0 + u;
-                const bool live = u ? live1 : live0;
-                const unsigned tb = (unsigned)(((u ? base + hop : base) + a) * 4);
-                if (live) {
-                    float old[E];
-#pragma unroll
-                    for (int i = 0; i < E; ++i)
-                        old[i] = *reinterpret_cast<const float *>(lm_smem + (((tb + 4u * (unsigned)pos_final<N>(i, 0)) & (4u * N - 1u)) | ring_b));
-#pragma unroll
-                    for (int i = 0; i < E; ++i)
-                        *reinterpret_cast<float *>(lm_smem + (((tb + 4u * (unsigned)pos_final<N>(i, 0)) & (4u * N - 1u)) | ring_b)) =
-                            old[i] + (u ? Zw[i].y : Zw[i].x);
-                }
-                __builtin_amdgcn_wave_barrier();
-                if (live) {
-                    float *o = mb + (size_t)f * hop;
-                    for (int j = a; j < hop; j += L) {
-                        float v = 0.0f;
-                        if (j < N) {
-                            float *slot = reinterpret_cast<float *>(lm_smem + (((tb + 4u * (unsigned)(j - a)) & (4u * N - 1u)) | ring_b));
-                            v = *slot;
-                            *slot = 0.0f;
-                        }
-                        o[j] = v;
-                    }
-                }
-                __builtin_amdgcn_wave_barrier();
-            }
+            ring_add_and_flush<N>(lm_smem, ring_b, mb, Z, wv, f0, live0, live1, a, base, hop);
             base = (base + 2 * hop) & (N - 1);
         }
     }
-    // the run's tail: positions [f_end * hop, f_end * hop + N - hop) as far as this run's frames reach them
-    if (GRAD && f_begin < f_end) {
-        const int bs = ((f_end - f_begin) * hop) & (N - 1);
-        const float *ring = rings + (size_t)sidx * N;
-        float *t = tails + ((size_t)b * n_runs + run) * tail_len;
-        for (int j = a_; j < tail_len; j += L) t[j] = ring[(bs + j) & (N - 1)];
-    }
-    s_l = wave_sum_f64(s_l);
-    if (lane == 0) red[wave] = s_l;
-    __syncthreads();
-    if (tid == 0) {
-        double acc = 0.0;
-        for (int w = 0; w < K::WAVES; ++w) acc += red[w];
-        part[(size_t)b * gridDim.x + blockIdx.x] = acc;
-    }
+    if (GRAD && f_begin < f_end) ring_write_tail<N, 1>(rings + (size_t)sidx * N, tails, rg, b, run, f_end - f_begin, hop, a_);
+    block_partials<1, K::WAVES>(s_l, red, b, part);
 }
 
 // partial sums -> value = scale * mean |la - lb|
@@ -348,44 +276,19 @@ __global__ __launch_bounds__(256) void lm_finish_kernel(const double *__restrict
     if (threadIdx.x == 0) value[0] = (float)(((red[0] + red[1]) + (red[2] + red[3])) * scale_over_count);
 }
 
-// the gradient at padded position p of clip b: the run sums plus the tails of the runs that end before p and reach it
-__device__ __forceinline__ float lm_fold_pos(const float *__restrict__ mainp, const float *__restrict__ tails, int b, int p, int hop,
-                                             int n_frames, int F, int n_runs, int tail_len)
+__global__ __launch_bounds__(256) void lm_fold_kernel(OlaGrad r, int T, int accumulate, float *__restrict__ dx, long long ds)
 {
-    const int flushed = n_frames * hop;
-    float g = 0.0f;
-    if (p < flushed) g += mainp[(size_t)b * flushed + p];
-    if (tail_len == 0) return g;
-    int rho = p / (F * hop);
-    if (rho > n_runs - 1) rho = n_runs - 1;
-    for (int q = rho; q >= 0 && q >= rho - 2; --q) {
-        const int fe = min((q + 1) * F, n_frames);
-        const int j = p - fe * hop;
-        if (j >= 0 && j < tail_len) g += tails[((size_t)b * n_runs + q) * tail_len + j];
-    }
-    return g;
-}
-
-__global__ __launch_bounds__(256) void lm_fold_kernel(const float *__restrict__ mainp, const float *__restrict__ tails, int N, int hop,
-                                                      int n_frames, int F, int n_runs, int tail_len, int T, int accumulate,
-                                                      float *__restrict__ dx, long long ds)
-{
-    const int b = blockIdx.y;
+    const int b = blockIdx.y, B = gridDim.y;
     const int n = blockIdx.x * 256 + threadIdx.x;
     if (n >= T) return;
-    // padded positions that map to sample n: the direct one and up to two reflected ones
-    float acc = lm_fold_pos(mainp, tails, b, n + N / 2, hop, n_frames, F, n_runs, tail_len);
-    if (n >= 1 && n <= N / 2) acc += lm_fold_pos(mainp, tails, b, N / 2 - n, hop, n_frames, F, n_runs, tail_len);
-    if (n <= T - 2 && n >= T - 1 - N / 2) acc += lm_fold_pos(mainp, tails, b, N / 2 + 2 * (T - 1) - n, hop, n_frames, F, n_runs, tail_len);
+    float acc = 0.0f;
+    for_padded_positions(n, r.N, T, [&](int p) {
+        float g[1] = {0.0f};
+        fold_pos<1>(r, B, b, p, g);
+        acc += g[0];
+    });
     float *o = dx + (size_t)b * ds + n;
     *o = accumulate ? *o + acc : acc;
-}
-
-static int lm_run_frames(int N, int hop)
-{
-    int F = (N + hop - 1) / hop;
-    if (F < LM_RUN_MIN) F = LM_RUN_MIN;
-    return (F + 1) & ~1;
 }
 
 template <int N>
@@ -394,29 +297,28 @@ static int lm_run(const float *x, long long xs, const float *y, long long ys, co
                   double *part, float *scratch, float *value, float *dx, long long ds, hipStream_t st)
 {
     using K = LM<N>;
-    const int n_frames = 1 + T / hop;
-    const int F = lm_run_frames(N, hop), n_runs = (n_frames + F - 1) / F, tail_len = N > hop ? N - hop : 0;
-    const int groups = (n_runs + K::STREAMS - 1) / K::STREAMS;
+    const OlaRuns rg = ola_runs(N, hop, T);
+    const int groups = (rg.n_runs + K::STREAMS - 1) / K::STREAMS;
     const int coef_cap = 2 * K::NK + 2 * n_mels;                  // triangular filters: every bin lies in <= 2 bands
     const size_t lds = lm_lds_bytes<N>(n_mels, coef_cap);
     const size_t lds_cap = 160 * 1024 - 64;                       // (the kernel's static LDS: the scan's wave sums)
     if (lds > lds_cap) return MX_ERR_UNSUPPORTED;
-    const long long count = (long long)B * n_mels * n_frames;
+    const long long count = (long long)B * n_mels * rg.n_frames;
     const float c = (float)((double)scale / (double)count);
-    float *mainp = scratch, *tails = dx ? scratch + (size_t)B * n_frames * hop : nullptr;
+    float *mainp = scratch, *tails = dx ? scratch + ola_main_floats(B, rg, hop) : nullptr;
     static MxLdsLatch latch[2];
     const void *fn = dx ? (const void *)lm_onepass_kernel<N, true> : (const void *)lm_onepass_kernel<N, false>;
     if (lds > 64 * 1024 && mx_set_dyn_lds(latch[dx ? 1 : 0], fn, lds_cap) != MX_OK) return MX_ERR_LAUNCH;
     if (dx)
         hipLaunchKernelGGL((lm_onepass_kernel<N, true>), dim3(groups, B), dim3(K::WAVES * 64), lds, st, x, xs, y, ys, win, tw, fb,
-                           band_lo, band_hi, n_mels, coef_cap, T, hop, n_frames, F, n_runs, eps, c, part, mainp, tails);
+                           band_lo, band_hi, n_mels, coef_cap, T, hop, rg, eps, c, part, mainp, tails);
     else
         hipLaunchKernelGGL((lm_onepass_kernel<N, false>), dim3(groups, B), dim3(K::WAVES * 64), lds, st, x, xs, y, ys, win, tw, fb,
-                           band_lo, band_hi, n_mels, coef_cap, T, hop, n_frames, F, n_runs, eps, c, part, nullptr, nullptr);
+                           band_lo, band_hi, n_mels, coef_cap, T, hop, rg, eps, c, part, nullptr, nullptr);
     hipLaunchKernelGGL(lm_finish_kernel, dim3(1), dim3(256), 0, st, part, groups * B, (double)scale / (double)count, value);
     if (dx)
-        hipLaunchKernelGGL(lm_fold_kernel, dim3((unsigned)((T + 255) / 256), (unsigned)B), dim3(256), 0, st, mainp, tails, N, hop,
-                           n_frames, F, n_runs, tail_len, T, accumulate, dx, ds);
+        hipLaunchKernelGGL(lm_fold_kernel, dim3((unsigned)((T + 255) / 256), (unsigned)B), dim3(256), 0, st,
+                           OlaGrad{mainp, tails, N, hop, rg}, T, accumulate, dx, ds);
     return mx_launch_status();
 }
 

@@ -11,6 +11,7 @@ import torch
 from torch import Tensor as T, nn
 
 from . import _hip
+from .mrstft import RUN_MIN, ola_scratch_floats, run_geometry
 
 _LFO_TERMS = ("l1", "fdl1", "sdl1", "mse")
 
@@ -90,11 +91,7 @@ class MSELoss(_SingleTerm):
 def logmel_scratch_floats(B: int, Tn: int, n_fft: int, hop: int) -> int:
     """Workspace floats of ``mx_logmel_l1_loss`` for the gradient (include/modex_hip.h): per clip frames * hop run sums plus
     one tail of n_fft - hop positions per run of F frames."""
-    frames = 1 + Tn // hop
-    run = max(32, -(-n_fft // hop))
-    run += run & 1
-    runs = -(-frames // run)
-    return B * (frames * hop + runs * max(n_fft - hop, 0))
+    return ola_scratch_floats(1, B, Tn, n_fft, hop)
 
 
 def logmel_l1_value_and_grad(mod: "LogMelLoss", a: T, t: T, need_grad: bool = True, scale: float = 1.0,
@@ -112,8 +109,8 @@ def logmel_l1_value_and_grad(mod: "LogMelLoss", a: T, t: T, need_grad: bool = Tr
     dev = a.device
     if sp.mel_scale.fb.device != dev:
         sp.to(dev)
-    frames = 1 + Tn // hop
-    part = torch.empty(B * -(-frames // 32), device=dev, dtype=torch.float64)
+    # one partial per workgroup, a workgroup takes at least one run: at most ceil(frames / RUN_MIN) per clip
+    part = torch.empty(B * -(-run_geometry(Tn, n_fft, hop)[0] // RUN_MIN), device=dev, dtype=torch.float64)
     value = torch.empty((), device=dev, dtype=torch.float32)
     if need_grad:
         if dx is None:

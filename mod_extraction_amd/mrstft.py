@@ -21,13 +21,28 @@ def _windows(fft_sizes: Sequence[int], win_lengths: Sequence[int], device) -> T:
     return w.to(device)
 
 
-def scratch_floats(B: int, Tn: int, n_fft: int, hop: int) -> int:
-    """Workspace floats of one resolution for the gradient (mirrors mr_ws_floats in csrc/mrstft.hip)."""
+# The one-pass gradient pipeline of the spectral losses (MR-STFT: 2 components, log-mel L1: 1).  csrc/ola_ring.h holds the
+# single definition (OLA_RUN_MIN, ola_runs, ola_ws_floats); this restates it for the workspaces Python allocates.
+RUN_MIN = 32
+
+
+def run_geometry(Tn: int, n_fft: int, hop: int) -> Tuple[int, int, int, int]:
+    """(frames, frames per run, runs, tail length) of a Tn-sample clip."""
     frames = 1 + Tn // hop
-    run = max(32, -(-n_fft // hop))
+    run = max(RUN_MIN, -(-n_fft // hop))
     run += run & 1
-    runs = -(-frames // run)
-    return 2 * B * (frames * hop + runs * max(n_fft - hop, 0))
+    return frames, run, -(-frames // run), max(n_fft - hop, 0)
+
+
+def ola_scratch_floats(components: int, B: int, Tn: int, n_fft: int, hop: int) -> int:
+    """Workspace floats for ``components`` time-domain gradient components: per clip frames * hop run sums plus one tail per run."""
+    frames, _, runs, tail = run_geometry(Tn, n_fft, hop)
+    return components * B * (frames * hop + runs * tail)
+
+
+def scratch_floats(B: int, Tn: int, n_fft: int, hop: int) -> int:
+    """Workspace floats of one resolution for the gradient."""
+    return ola_scratch_floats(2, B, Tn, n_fft, hop)
 
 
 def mrstft_value_and_grad(mod: "MultiResolutionSTFTLoss", a: T, t: T, need_grad: bool = True, scale: float = 1.0):

@@ -44,7 +44,7 @@ def run(B=256, T=176400):
     part = torch.empty(3 * B * max(-(-f // 8) for f in frames), device=dev, dtype=torch.float64)
     coef = torch.empty(n_res, device=dev)
     terms = torch.empty(2 * n_res + 1, device=dev)
-    # (generous: variants built with a smaller MR_RUN_MIN keep more run tails than the shipped formula)
+    # (generous: variants built with a smaller OLA_RUN_MIN keep more run tails than the shipped formula)
     scratch = torch.empty(3 * sum(mrstft.scratch_floats(B, T, n, h) for n, h in zip(mod.fft_sizes, mod.hop_sizes)), device=dev)
     dx = torch.empty((B, T), device=dev)
     ffts = (ctypes.c_int32 * n_res)(*mod.fft_sizes)
