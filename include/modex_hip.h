@@ -139,6 +139,29 @@ int mx_flanger_bwd_lr(const float *dy, int64_t dy_stride, const float *x, int64_
  * out: 1 float.  No reference counterpart. */
 int mx_lds_roundtrip_probe(int64_t steps, float *out, void *stream);
 
+/* ---- K2c: tremolo -- mod_extraction/fx.py:13-22 (apply_tremolo), one row per (clip, channel):
+ *   y[n] = ((1 - mix) * x[n]) + ((mix * m[n]) * x[n]), every operation rounded to fp32 where the reference's torch ops round.
+ * x: row b at x + b*x_stride (N samples); y likewise with y_stride.  mod (B,n_mod) dense fp32, 1 <= n_mod <= N: m = mod[n]
+ * for n_mod == N, otherwise the row is resampled in-kernel with the align_corners=True rule of util.py:15-29 (the taps and
+ * rounding of mx_interp_linear and of mx_flanger_fwd's in-kernel LFO), so the result is bit-identical to resampling first.
+ * mix, one_minus_mix (B,) fp32 (both: a python-float mix rounds 1 - mix in double before fp32); rows/n_rows: optional list of
+ * rows to process, the others are not touched.  Rows whose pointers are 16-byte aligned move float4s, others single floats.
+ * N >= 2^30 returns MX_ERR_UNSUPPORTED. */
+int mx_tremolo_fwd(const float *x, int64_t x_stride, const float *mod, int64_t n_mod, const float *mix,
+                   const float *one_minus_mix, const int32_t *rows, int64_t n_rows, int64_t B, int64_t N,
+                   float *y, int64_t y_stride, void *stream);
+/* Adjoint of fx.py:13-22 behind the resampling of util.py:15-29; m is recomputed exactly as in mx_tremolo_fwd (no stash).
+ * dy, x: views as above; mod, n_mod, mix, one_minus_mix, rows as the forward was given.  Optional outputs (NULL = skip):
+ *   dx    row b at dx + b*dx_stride: dy * (one_minus_mix + mix * m), fp32;
+ *   dmod  (B,n_mod) fp32 dense: mix * sum_n w_k(n) dy[n] x[n] with the fp32 tap weights w_k(n) of the resampling, products
+ *         and sums in fp64 over the contiguous range of samples with a tap on point k, in a fixed order, rounded once
+ *         (n_mod == N: mix * dy * x); no atomics, no workspace: two calls are bit-identical;
+ *   dmix  (B,) fp64: sum_n dy x (m - 1), the one_minus_mix path included (the convention of mx_flanger_bwd's d_mix). */
+int mx_tremolo_bwd(const float *dy, int64_t dy_stride, const float *x, int64_t x_stride, const float *mod,
+                   int64_t n_mod, const float *mix, const float *one_minus_mix, const int32_t *rows,
+                   int64_t n_rows, int64_t B, int64_t N, float *dx, int64_t dx_stride, float *dmod, double *dmix,
+                   void *stream);
+
 /* ---- K3: phaser -- call site mod_extraction/datasets.py:455-482 (pedalboard==0.7.3 Phaser = JUCE
  * dsp::Phaser<float>: 6 first-order TPT all-pass stages + feedback, sine LFO at sr/4 on a log
  * frequency axis, linear dry/wet mix), then clip to [-1,1] (datasets.py:472).  Third-party

@@ -6,6 +6,8 @@ rendering moved onto the device:
 * flanger / chorus  -> ``mx_flanger_fwd`` (the reference runs fx.py on the CPU in
   ``on_before_batch_transfer`` or pre-renders to disk)
 * phaser            -> ``mx_phaser_fwd`` (the reference calls pedalboard in DataLoader workers)
+* tremolo           -> ``mx_tremolo_fwd`` on the n_samples // 100 label, resampled in-kernel (the reference's
+  ``TremoloDataset``, datasets.py:485-501, hands fx.py:16 an LFO of the wrong length and cannot run as written)
 * LFO labels        -> ``mx_lfo_synth``
 
 Audio comes from recorded files when the configured directories exist (``datasets.FileChunkSource``: the
@@ -35,6 +37,7 @@ FLANGER_FX = {"max_min_delay_ms": 1.0, "max_lfo_delay_ms": 10.0, "feedback": (0.
 CHORUS_FX = dict(FLANGER_FX, max_min_delay_ms=30.0, min_delay_width=(0.367, 1.0))   # configs/data/gen_idmt_ch.yml:34-51
 PHASER_FX = {"rate_hz": (0.5, 3.0), "depth": (0.2, 1.0), "centre_frequency_hz": (70.0, 18000.0),
              "feedback": (0.0, 0.7), "mix": (0.2, 1.0)}        # configs/train_lfo_phaser.yml:33-48
+TREMOLO_FX = {"mix": (0.0, 1.0)}
 MOD_SIG = {"rate_hz": (0.5, 3.0), "phase": (0.0, 2 * math.pi), "shapes": LFO_SHAPES, "exp": 1.0}
 
 
@@ -61,21 +64,25 @@ class SyntheticFxBatcher:
     """Builds one training batch entirely on the device.
 
     ``kinds`` lists the effect of each slot of the interleave, clip ``i`` gets ``kinds[i % len(kinds)]``
-    (datasets.py:79-83): "flanger", "chorus" (fx.py with 1 ms / 30 ms base delay) or "phaser".
+    (datasets.py:79-83): "flanger", "chorus" (fx.py with 1 ms / 30 ms base delay), "phaser", "tremolo"
+    (fx.py:13-22) or "dry" (no effect).
     Host RNG: ``torch`` global generator and numpy global RNG (scipy ``loguniform``), as in the
     reference.  ``rng_order="batch"`` (default) draws each parameter once per batch (one vectorised call);
     ``rng_order="reference"`` consumes the host RNG streams in the reference's own order -- per item
     rate / phase / shape (datasets.py:367-372) resp. rate, depth, centre, feedback, mix, crop offset for a phaser
-    item (datasets.py:429-431,460-465,444), then the five (B,) effect draws of
+    item (datasets.py:429-431,460-465,444) resp. rate / phase / shape / mix for a tremolo item (datasets.py:367-372,492-495), then the five (B,) effect draws of
     ``FlangerCPUDataModule.on_before_batch_transfer`` (data_modules.py:421-445) -- so a seeded run reproduces the
-    reference's parameter stream value for value (tests/test_param_stream.py, golden from the real ``util``).
+    reference's parameter stream value for value (tests/test_param_stream.py, golden from the real ``util``).  In "batch"
+    order the tremolo mix is one more vectorised draw after the phaser's, made only when the batch has a tremolo slot, so
+    the streams of batches without one do not move.
     """
 
     def __init__(self, batch_size: int, n_samples: int, sr: float, kinds: Sequence[str], device: torch.device,
                  flanger_fx: Optional[Dict] = None, chorus_fx: Optional[Dict] = None,
                  phaser_fx: Optional[Dict] = None, mod_sig: Optional[Dict] = None, audio_seed: int = 43,
                  peak_db: float = -1.0, fixed_lead: Optional[int] = None, overlap: bool = False,
-                 chunk_source: Optional[Any] = None, rng_order: str = "batch") -> None:
+                 chunk_source: Optional[Any] = None, rng_order: str = "batch",
+                 tremolo_fx: Optional[Dict] = None) -> None:
         assert rng_order in ("batch", "reference")
         self.rng_order = rng_order
         self.B, self.N, self.sr, self.device = batch_size, n_samples, float(sr), device
@@ -84,6 +91,7 @@ class SyntheticFxBatcher:
         self.fl = _fx_from_config(flanger_fx, FLANGER_FX)
         self.ch = _fx_from_config(chorus_fx, CHORUS_FX)
         self.ph = _fx_from_config(phaser_fx, PHASER_FX)
+        self.tr = _fx_from_config(tremolo_fx, TREMOLO_FX)
         self.ms = dict(MOD_SIG)
         if mod_sig:
             for k, v in mod_sig.items():
@@ -92,13 +100,15 @@ class SyntheticFxBatcher:
         self.lfo_sr = self.sr // 100
         # "dry": no effect -- the wet slot carries the untouched chunk and the LFO is a label only (datasets.py:365-398 as
         # RandomAudioChunkAndModSigDataModule uses it, data_modules.py:331-371)
-        self.kind_id = torch.tensor([{"flanger": 0, "chorus": 1, "phaser": 2, "dry": 3}[k] for k in self.kinds])
+        self.kind_id = torch.tensor([{"flanger": 0, "chorus": 1, "phaser": 2, "dry": 3, "tremolo": 4}[k] for k in self.kinds])
         self.rows_fx = torch.nonzero(self.kind_id < 2).view(-1).to(torch.int32).to(device)
         self.rows_ph = torch.nonzero(self.kind_id == 2).view(-1).to(torch.int32).to(device)
+        self.rows_tr = torch.nonzero(self.kind_id == 4).view(-1).to(torch.int32).to(device)
         self._is_ph_dev = (self.kind_id == 2).to(device)
         self.has_ph = bool((self.kind_id == 2).any())
         self.has_fx = bool((self.kind_id < 2).any())
         self.has_dry = bool((self.kind_id == 3).any())
+        self.has_tr = bool((self.kind_id == 4).any())
         self.fixed_lead = fixed_lead
         # phaser: the reference renders n + sr/rate samples and crops (datasets.py:428-449)
         self.max_lead = int(self.sr / self.ph["rate_hz"][0] + 0.5) if self.has_ph else 0
@@ -160,6 +170,7 @@ class SyntheticFxBatcher:
         ph = {k: torch.zeros(B, dtype=torch.float64) for k in ("depth", "centre", "feedback", "mix")}
         lead = torch.zeros(B, dtype=torch.int64)
         rate_n = torch.zeros(B, dtype=torch.int64)
+        tr_mix = torch.zeros(B, dtype=torch.float64)
         for i, kind in enumerate(self.kinds):
             if kind == "phaser":
                 rate[i] = util.sample_log_uniform(*self.ph["rate_hz"])                      # datasets.py:429-432
@@ -175,6 +186,8 @@ class SyntheticFxBatcher:
                 rate[i] = util.sample_log_uniform(*self.ms["rate_hz"])                      # datasets.py:367-372
                 phase[i] = util.sample_uniform(*self.ms["phase"])
                 shapes.append(util.choice(list(self.ms["shapes"])))
+                if kind == "tremolo":
+                    tr_mix[i] = util.sample_uniform(*self.tr["mix"])                        # datasets.py:492-495
         is_ph = self.kind_id == 2
         p: Dict[str, Any] = {}
         for name in ("feedback", "min_delay_width", "width", "depth", "mix"):               # data_modules.py:421-445
@@ -186,6 +199,8 @@ class SyntheticFxBatcher:
             p["mix"] = torch.where(is_ph, ph["mix"].float(), p["mix"])
             centre = torch.where(is_ph, ph["centre"].float(), centre)
             p["proc_extra"] = rate_n
+        if self.has_tr:
+            p["mix"] = torch.where(self.kind_id == 4, tr_mix.float(), p["mix"])
         p.update(rate_hz=rate.float(), phase=phase.float(), shape=shapes, exp=torch.full((B,), float(self.ms["exp"])),
                  centre_frequency_hz=centre, lead=lead.to(torch.int32))
         return p
@@ -228,6 +243,8 @@ class SyntheticFxBatcher:
                 lead = torch.full((B,), int(self.fixed_lead), dtype=torch.int64)
             lead = torch.where(is_ph, lead, torch.zeros_like(lead)).to(torch.int32)
             p["proc_extra"] = torch.where(is_ph, rate_n, torch.zeros_like(rate_n))   # the reference renders n + sr/rate
+        if self.has_tr:                                                           # datasets.py:492-495; the last draw of a batch
+            p["mix"] = torch.where(self.kind_id == 4, self._uniform(*self.tr["mix"]), p["mix"])
         p.update(rate_hz=rate, phase=phase, shape=shapes, exp=torch.full((B,), float(self.ms["exp"])),
                  centre_frequency_hz=centre, lead=lead)
         return p
@@ -288,6 +305,10 @@ class SyntheticFxBatcher:
             fx.flanger_forward(dry, mod, consts, self.max_delay, self.max_delay_max, rows=self.rows_fx, out=wet)
         if self.has_ph:
             fx.phaser_forward(self._src_cur, d, d["lead"], self.sr, N, rows=self.rows_ph, out=wet, dry_out=dry)
+        if self.has_tr:
+            # datasets.py:497 on the 882-point label: the kernel resamples it as util.py:15-29 would (the reference asserts there)
+            consts = {"mix": d["mix"], "one_minus_mix": (1.0 - d["mix"]).contiguous()}
+            fx.tremolo_forward(dry, mod, consts, rows=self.rows_tr, out=wet)
         fx_params = dict(d)
         fx_params["shape"] = p["shape"]
         return self.audio[:, 0:1, :], self.audio[:, 1:2, :], mod, fx_params
@@ -393,7 +414,8 @@ class _SyntheticDataModule:
     def setup(self, device: torch.device, rank: int = 0, seed: int = 43) -> None:
         fl = self.fx_config.get("flanger")
         common = dict(flanger_fx=fl, chorus_fx=fl if "chorus" in self.kinds and fl else None,
-                      phaser_fx=self.fx_config.get("pedalboard_phaser"), mod_sig=self.fx_config.get("mod_sig"),
+                      phaser_fx=self.fx_config.get("pedalboard_phaser"), tremolo_fx=self.fx_config.get("tremolo"),
+                      mod_sig=self.fx_config.get("mod_sig"),
                       audio_seed=seed + rank, rng_order=self.rng_order)
         self._batcher = SyntheticFxBatcher(self.batch_size, self.n_samples, self.sr, self.kinds, device,
                                            chunk_source=self._chunk_source("train"), overlap=self.overlap, **common)
@@ -449,6 +471,13 @@ class FlangerCPUDataModule(_SyntheticDataModule):
 class PedalboardPhaserDataModule(_SyntheticDataModule):
     """data_modules.py:259-328."""
     kinds = ("phaser",)
+
+
+class TremoloDataModule(_SyntheticDataModule):
+    """The batch form of datasets.py:485-501 (``TremoloDataset``): wet = fx.py:13-22 on the dry chunk, driven by the
+    n_samples // 100 label resampled to the audio rate, mix from ``fx_config["tremolo"]["mix"]``.  The reference has no data
+    module of its own for it; the per-item dataset stays out of this package, as for the phaser."""
+    kinds = ("tremolo",)
 
 
 class RandomAudioChunkAndModSigDataModule(_SyntheticDataModule):

@@ -22,13 +22,23 @@ def delay_samples(ms: float, sr: float) -> int:
 
 
 def apply_tremolo(x: T, mod_sig: T, mix: Param = 1.0) -> T:
-    """fx.py:13-22 (a single fused elementwise expression; torch-on-HIP plumbing, not a kernel)."""
+    """fx.py:13-22.  An fp32 HIP x with nothing requiring grad goes through ``mx_tremolo_fwd`` (bit-identical to the
+    expression below); everything else -- host tensors, other dtypes, a graph to record -- keeps the torch expression, so
+    torch autograd through this function is what it was.  ``TremoloModule`` is the differentiable kernel path."""
     assert x.ndim == 3 and x.size(0) == mod_sig.size(0) and x.size(-1) == mod_sig.size(-1)
     if mod_sig.ndim == 2:
         mod_sig = mod_sig.unsqueeze(1).expand(-1, x.size(1), -1)
     if isinstance(mix, T):
         assert mix.size(0) == x.size(0)
     assert 0.0 <= mix <= 1.0                    # fx.py:21 (a tensor mix must therefore hold one element)
+    graph = torch.is_grad_enabled() and any(isinstance(t, T) and t.requires_grad for t in (x, mod_sig, mix))
+    if (x.is_cuda and x.dtype == torch.float32 and mod_sig.dtype == torch.float32 and mod_sig.device == x.device
+            and mod_sig.shape == x.shape and not graph and (not isinstance(mix, T) or mix.dtype == torch.float32)):
+        bs, n_ch, n = x.shape
+        consts = derive_tremolo_constants(bs, x.device, mix, check=False)
+        xr, mr = _channel_rows_of(x, mod_sig)
+        y = tremolo_forward(xr, mr, {k: _per_row(v, n_ch) for k, v in consts.items()})
+        return y.view(bs, n_ch, n)
     return ((1.0 - mix) * x) + (mix * mod_sig * x)
 
 
@@ -92,6 +102,66 @@ def _rows_arg(rows: Optional[T]) -> Tuple[Optional[int], int]:
 def _per_row(v: T, n_ch: int) -> T:
     """A (bs,) per-clip vector repeated for the n_ch rows of each clip: a clip's channels share its parameters."""
     return (v.repeat_interleave(n_ch) if n_ch > 1 else v).contiguous()
+
+
+def _channel_rows_of(x: T, mod_sig: T) -> Tuple[T, T]:
+    """x (bs, n_ch, n) and mod_sig (bs, n_mod) / (bs, 1 | n_ch, n_mod) as the kernels' rows: one row per (clip, channel),
+    (bs n_ch, n) with contiguous samples and (bs n_ch, n_mod) dense; a mod_sig without a channel axis (or with one of 1) is
+    shared by its clip's channels (fx.py:84-85)."""
+    bs, n_ch, n = x.shape
+    xr = x.reshape(bs * n_ch, n).float()
+    if xr.stride(-1) != 1:
+        xr = xr.contiguous()
+    if mod_sig.ndim == 2 or mod_sig.size(1) == 1:
+        mod_sig = mod_sig.reshape(bs, 1, -1).expand(-1, n_ch, -1)
+    return xr, mod_sig.reshape(bs * n_ch, -1).float().contiguous()
+
+
+def derive_tremolo_constants(bs: int, device: torch.device, mix: Param, check: bool = True) -> Dict[str, T]:
+    """The per-clip fp32 constants of fx.py:22 under the rounding rule of ``derive_clip_constants``: a tensor mix gives
+    1 - mix in fp32, a python float gives it in double, rounded to fp32 once."""
+    if check:
+        _check_param(mix, bs)
+    if isinstance(mix, T):
+        mix_v = mix.to(device=device, dtype=torch.float32).contiguous()
+        return {"mix": mix_v, "one_minus_mix": (1.0 - mix_v).contiguous()}
+    return {"mix": torch.full((bs,), float(mix), device=device, dtype=torch.float32),
+            "one_minus_mix": torch.full((bs,), 1.0 - float(mix), device=device, dtype=torch.float32)}
+
+
+def tremolo_forward(x: T, mod_sig: T, consts: Dict[str, T], rows: Optional[T] = None, out: Optional[T] = None) -> T:
+    """Launch mx_tremolo_fwd.  x, out: (B,N) fp32 views with contiguous rows (any row stride, e.g. one channel of a (B,2,N)
+    tensor); mod_sig (B,n_mod) fp32 dense, 1 <= n_mod <= N (a shorter row is resampled in-kernel); consts from
+    ``derive_tremolo_constants``; rows: optional int32 list of the rows to process (the others of ``out`` are untouched)."""
+    B, N = x.shape
+    assert mod_sig.ndim == 2 and mod_sig.size(0) == B and 1 <= mod_sig.size(1) <= N
+    y = out if out is not None else torch.empty_like(x)
+    assert y.shape == x.shape
+    _hip.call("mx_tremolo_fwd", *_rows_view(x), _hip.ptr(mod_sig), mod_sig.size(1), _hip.ptr(consts["mix"]),
+              _hip.ptr(consts["one_minus_mix"]), *_rows_arg(rows), B, N, *_rows_view(y), _hip.stream())
+    return y
+
+
+def tremolo_backward(dy: T, x: T, mod_sig: T, consts: Dict[str, T], rows: Optional[T] = None, need_dx: bool = True,
+                     need_dmod: bool = True, need_dmix: bool = True) -> Tuple[Optional[T], Optional[T], Optional[T]]:
+    """Launch mx_tremolo_bwd: the adjoint of fx.py:13-22 behind the in-kernel resampling.  dy, x: (B,N) views with
+    contiguous rows; mod_sig (B,n_mod) as the forward was given.  Returns dx (B,N) fp32, dmod (B,n_mod) fp32 and dmix (B,)
+    fp64 (the one_minus_mix path included), each None unless asked for; rows not listed in ``rows`` hold zeros."""
+    B, N = x.shape
+    dev = x.device
+    n_mod = mod_sig.size(1)
+    assert mod_sig.ndim == 2 and mod_sig.size(0) == B and 1 <= n_mod <= N and dy.shape == x.shape
+    if dy.stride(-1) != 1 or dy.stride(0) < N:            # e.g. the expanded ones of y.sum().backward()
+        dy = dy.contiguous()
+    new = torch.empty if rows is None else torch.zeros
+    dx = new((B, N), device=dev, dtype=torch.float32) if need_dx else None
+    dmod = new((B, n_mod), device=dev, dtype=torch.float32) if need_dmod else None
+    dmix = torch.zeros((B,), device=dev, dtype=torch.float64) if need_dmix else None
+    dxp, dxs = _rows_view(dx) if need_dx else (None, 0)
+    _hip.call("mx_tremolo_bwd", *_rows_view(dy), *_rows_view(x), _hip.ptr(mod_sig), n_mod, _hip.ptr(consts["mix"]),
+              _hip.ptr(consts["one_minus_mix"]), *_rows_arg(rows), B, N, dxp, dxs, _hip.ptr(dmod), _hip.ptr(dmix),
+              _hip.stream())
+    return dx, dmod, dmix
 
 
 def flanger_forward(x: T, mod_sig: T, consts: Dict[str, T], max_delay: T, max_delay_max: int,
@@ -246,13 +316,7 @@ class MonoFlangerChorusModule(nn.Module):
             assert mod_sig.size(1) in (1, n_ch)
         consts = derive_clip_constants(bs, x.device, self.max_min_delay_samples, self.max_lfo_delay_samples,
                                        feedback, min_delay_width, width, depth, mix)
-        rows = bs * n_ch
-        xr = x.reshape(rows, n).float()
-        if xr.stride(-1) != 1:
-            xr = xr.contiguous()
-        if mod_sig.ndim == 2 or mod_sig.size(1) == 1:               # fx.py:84-85: shared by the channels
-            mod_sig = mod_sig.reshape(bs, 1, -1).expand(-1, n_ch, -1)
-        mr = mod_sig.reshape(rows, -1).float().contiguous()
+        xr, mr = _channel_rows_of(x, mod_sig)                       # fx.py:84-85: mod_sig shared by the channels
         return xr, mr, consts, (bs, n_ch, n)
 
     def _apply_effect_grad(self, x: T, mod_sig: T, feedback: Param, min_delay_width: Param, width: Param, depth: Param,
@@ -511,3 +575,65 @@ class PhaserModule(nn.Module):
             else:
                 y, _ = phaser_forward_stash(xr, p, lead_rows, self.sr, n, mod=mr)
         return y.view(bs, n_ch, n)
+
+
+class _TremoloFunction(torch.autograd.Function):
+    """y = tremolo(x, mod, mix) over (clip, channel) rows; the (bs,) mix is shared by a clip's n_ch rows, so its gradient
+    is summed over the channels (in fp64) before it is rounded to fp32.  one_minus_mix gets no gradient of its own: d mix
+    includes that path."""
+
+    @staticmethod
+    def forward(ctx, x, mod_sig, mix, one_minus_mix, n_ch):
+        consts = {"mix": _per_row(mix.detach(), n_ch), "one_minus_mix": _per_row(one_minus_mix.detach(), n_ch)}
+        y = tremolo_forward(x.detach(), mod_sig.detach(), consts)
+        ctx.save_for_backward(x, mod_sig)
+        ctx.consts, ctx.n_ch = consts, n_ch
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        x, mod_sig = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        dx, dmod, dmix = tremolo_backward(dy, x, mod_sig, ctx.consts, need_dx=need[0], need_dmod=need[1], need_dmix=need[2])
+        if dmix is not None:
+            dmix = dmix.view(-1, ctx.n_ch).sum(1).float()
+        return dx, dmod, dmix, None, None
+
+
+class TremoloModule(nn.Module):
+    """The tremolo of fx.py:13-22 (``apply_tremolo``) as a module in the shape of ``PhaserModule``, on the
+    ``mx_tremolo_fwd`` / ``mx_tremolo_bwd`` kernels.
+
+    x (bs, n_ch, N): the channels are rows that share their clip's LFO and mix.  mod_sig (bs, n_mod) or
+    (bs, 1 | n_ch, n_mod) at any 1 <= n_mod <= N: a row shorter than N is resampled in-kernel exactly as
+    ``util.linear_interpolate_last_dim(mod_sig, N, align_corners=True)`` would, and its gradient has mod_sig's own shape.
+    mix: a python float or a (bs,) tensor in [0, 1] -- one value PER CLIP, which the reference's scalar assert (fx.py:21)
+    does not allow; a float or a one-element tensor reproduces ``apply_tremolo`` bit for bit.
+
+    ``forward`` runs under no_grad.  ``apply_effect`` carries a grad_fn when grad mode is on and x, mod_sig or a tensor mix
+    requires grad; the gradients of mod_sig and mix are summed over a clip's channels.  A python-float mix gets no
+    gradient.  The effect has no state, so there is no stash: the backward recomputes the LFO values."""
+
+    def _prepare(self, x: T, mod_sig: T, mix: Param):
+        assert x.ndim == 3
+        bs, n_ch, n = x.shape
+        assert mod_sig.size(0) == bs and mod_sig.ndim in (2, 3) and 1 <= mod_sig.size(-1) <= n
+        if mod_sig.ndim == 3:
+            assert mod_sig.size(1) in (1, n_ch)
+        consts = derive_tremolo_constants(bs, x.device, mix)
+        xr, mr = _channel_rows_of(x, mod_sig)
+        return xr, mr, consts, (bs, n_ch, n)
+
+    def apply_effect(self, x: T, mod_sig: T, mix: Param = 1.0) -> T:
+        if not (torch.is_grad_enabled() and (x.requires_grad or mod_sig.requires_grad or
+                                             (isinstance(mix, T) and mix.requires_grad))):
+            return self.forward(x, mod_sig, mix)
+        xr, mr, consts, shape = self._prepare(x, mod_sig, mix)
+        return _TremoloFunction.apply(xr, mr, consts["mix"], consts["one_minus_mix"], shape[1]).view(shape)
+
+    def forward(self, x: T, mod_sig: T, mix: Param = 1.0) -> T:
+        with torch.no_grad():
+            xr, mr, consts, shape = self._prepare(x, mod_sig, mix)
+            y = tremolo_forward(xr, mr, {k: _per_row(v, shape[1]) for k, v in consts.items()})
+        return y.view(shape)

@@ -160,34 +160,32 @@ class LFOExtraction(BaseLightingModule):
             return step(batch, is_training=False)
 
 
-class _FlangerAudioLossFn(torch.autograd.Function):
-    """loss = sum_k w_k loss_k(flanger(dry, mod_sig_hat), wet) as ONE autograd node.  Its forward runs the stash forward
-    (``mx_flanger_fwd_stash`` on the low-rate LFO), the value-and-gradient kernels of the weighted losses
-    (``effect_loss_grad``) and the flanger adjoint (``mx_flanger_bwd_lr``) at once and keeps only d loss / d mod_sig_hat
-    (B, n_frames): the (B, N) stash, d loss / d wet_hat and the adjoint's workspace do not outlive the call.  Returns
-    (loss, wet_hat (B, N)); ``terms`` receives the unweighted value of every weighted loss."""
+def _audio_loss_node(ctx, step, wet_hat, wet, terms, adjoint):
+    """What the audio-loss nodes of every effect share, after the effect's forward has rendered ``wet_hat`` (B, N): the
+    value-and-gradient kernels of the weighted losses (``effect_loss_grad``), the effect's ``adjoint(dy) -> dmod`` at once,
+    the unweighted terms and the weighted sum.  Only d loss / d mod_sig_hat (B, n_frames) is kept for the backward; d loss /
+    d wet_hat and whatever the adjoint closes over do not outlive the call."""
+    from .effect_losses import effect_loss_grad, effect_loss_terms
+    a, t = wet_hat.unsqueeze(1), wet.unsqueeze(1)
+    weighted: Dict[str, T] = {}
+    dy = effect_loss_grad(a, t, step.audio_loss_dict, values=weighted, **step._grad_modules())
+    dmod = adjoint(dy)
+    w = {k: v for k, v in step.audio_loss_dict.items() if v > 0}
+    terms.update({k: v / w[k] for k, v in weighted.items()})
+    if any(k in w for k in ("l1", "mse", "esr", "dc")):
+        terms.update({k: v for k, v in effect_loss_terms(a, t).items() if k in w})
+    loss = None
+    for k, wk in w.items():
+        loss = wk * terms[k] if loss is None else loss + wk * terms[k]
+    ctx.save_for_backward(dmod)
+    ctx.mark_non_differentiable(wet_hat)
+    return loss, wet_hat
 
-    @staticmethod
-    def forward(ctx, mod_sig_hat, step, dry, wet, consts, terms):
-        from . import fx
-        from .effect_losses import effect_loss_grad, effect_loss_terms
-        mod = mod_sig_hat.detach().float().contiguous()
-        md, M = step._max_delay_rows(dry.size(0), dry.device), step.max_delay_samples
-        wet_hat, stash = fx.flanger_forward_stash(dry, mod, consts, md, M)
-        a, t = wet_hat.unsqueeze(1), wet.unsqueeze(1)
-        weighted: Dict[str, T] = {}
-        dy = effect_loss_grad(a, t, step.audio_loss_dict, values=weighted, **step._grad_modules())
-        _, dmod, _ = fx.flanger_backward(dy, dry, mod, stash, consts, md, M, need_dx=False, params=())
-        w = {k: v for k, v in step.audio_loss_dict.items() if v > 0}
-        terms.update({k: v / w[k] for k, v in weighted.items()})
-        if any(k in w for k in ("l1", "mse", "esr", "dc")):
-            terms.update({k: v for k, v in effect_loss_terms(a, t).items() if k in w})
-        loss = None
-        for k, wk in w.items():
-            loss = wk * terms[k] if loss is None else loss + wk * terms[k]
-        ctx.save_for_backward(dmod)
-        ctx.mark_non_differentiable(wet_hat)
-        return loss, wet_hat
+
+class _EffectAudioLossFn(torch.autograd.Function):
+    """loss = sum_k w_k loss_k(effect(dry, mod_sig_hat), wet) as ONE autograd node: ``forward(ctx, mod_sig_hat, step, dry,
+    wet, consts, terms)`` returns (loss, wet_hat (B, N)) and fills ``terms`` with the unweighted value of every weighted
+    loss; the gradient was computed in the forward (``_audio_loss_node``), the backward scales it."""
 
     @staticmethod
     def backward(ctx, g, _g_wet_hat):
@@ -195,22 +193,52 @@ class _FlangerAudioLossFn(torch.autograd.Function):
         return dmod * g, None, None, None, None, None
 
 
+class _FlangerAudioLossFn(_EffectAudioLossFn):
+    """The flanger / chorus: the stash forward (``mx_flanger_fwd_stash`` on the low-rate LFO) and the adjoint
+    (``mx_flanger_bwd_lr``); the (B, N) stash and the adjoint's workspace do not outlive the call."""
+
+    @staticmethod
+    def forward(ctx, mod_sig_hat, step, dry, wet, consts, terms):
+        from . import fx
+        mod = mod_sig_hat.detach().float().contiguous()
+        md, M = step._max_delay_rows(dry.size(0), dry.device), step.max_delay_samples
+        wet_hat, stash = fx.flanger_forward_stash(dry, mod, consts, md, M)
+        return _audio_loss_node(ctx, step, wet_hat, wet, terms, lambda dy: fx.flanger_backward(
+            dy, dry, mod, stash, consts, md, M, need_dx=False, params=())[1])
+
+
+class _TremoloAudioLossFn(_EffectAudioLossFn):
+    """The tremolo: ``mx_tremolo_fwd`` on the low-rate LFO and ``mx_tremolo_bwd`` asked for dmod alone (no stash: the
+    effect has no state)."""
+
+    @staticmethod
+    def forward(ctx, mod_sig_hat, step, dry, wet, consts, terms):
+        from . import fx
+        mod = mod_sig_hat.detach().float().contiguous()
+        wet_hat = fx.tremolo_forward(dry, mod, consts)
+        return _audio_loss_node(ctx, step, wet_hat, wet, terms, lambda dy: fx.tremolo_backward(
+            dy, dry, mod, consts, need_dx=False, need_dmix=False)[1])
+
+
 class LFOExtractionThroughEffect(BaseLightingModule):
-    """Trains the LFO extractor on dry / wet pairs WITHOUT an LFO label: the extractor's LFO drives the differentiable
-    flanger / chorus on ``dry`` and an audio-domain loss compares the result with ``wet``.  The reference has no such step
+    """Trains the LFO extractor on dry / wet pairs WITHOUT an LFO label: the extractor's LFO drives a differentiable
+    effect -- ``effect="flanger"`` (flanger / chorus, the default) or ``effect="tremolo"`` -- on ``dry`` and an audio-domain
+    loss compares the result with ``wet``.  The reference has no such step
     (its lightning.py:65-199 trains against the ground-truth LFO only; its flanger, fx.py:72-119, has no usable autograd).
 
     Same batch 4-tuple ``(dry, wet, mod_sig, fx_params)`` and metric naming as ``LFOExtraction``; ``training_step`` returns a
     loss with a grad graph, so ``trainer.Trainer`` drives it unchanged.
     * ``max_min_delay_ms`` / ``max_lfo_delay_ms``: ONE flanger or chorus geometry per module, as in
       ``fx.MonoFlangerChorusModule`` (batches that mix geometries are out of scope; so are phaser rows, whose render needs
-      lead-in samples the batch does not carry).
-    * ``fx_params`` carries the per-clip ``feedback``, ``min_delay_width``, ``width``, ``depth``, ``mix`` as (B,) tensors
+      lead-in samples the batch does not carry).  ``effect="tremolo"`` ignores both and has no delay-line limit.
+    * ``effect``: ONE effect family per module; a batch that mixes effects is out of scope.
+    * ``fx_params`` carries the per-clip ``feedback``, ``min_delay_width``, ``width``, ``depth``, ``mix`` as (B,) tensors;
+      the tremolo needs only ``mix``
       (``check_fx_params``: range-check them on every step, which costs host synchronisations).
     * ``audio_loss_dict``: names from ``effect_losses.GRAD_NAMES``; zero-weight names are only logged.
     * ``loss_dict`` (optional, default none): an LFO-domain term (lightning.py:33-62) added to the loss when the batch carries
       ``mod_sig``; it is logged as ``{prefix}/lfo_{name}``.
-    The LFO enters the flanger at the extractor's own rate (n_frames points, resampled in-kernel exactly as the data path
+    The LFO enters the effect at the extractor's own rate (n_frames points, resampled in-kernel exactly as the data path
     resamples its n_samples // 100 label), so a re-render from the label the batch was rendered with is bit-identical to
     ``wet`` and every loss is exactly 0 there.
 
@@ -218,8 +246,10 @@ class LFOExtractionThroughEffect(BaseLightingModule):
     wet by the rule of ``TBPTTLFOEffectModeling._prepare_all_rows``.  One limit of that crop: the re-render starts from an
     EMPTY delay line at the first cropped sample, whereas the recorded wet had the samples before the crop in its line, so
     the first ``max_delay_samples`` samples of ``wet_hat`` differ from ``wet`` even for the true LFO.  The default is
-    therefore no smoothing.  ``should_stretch`` is not wired in (the corner stretch has a backward, but not on this path)."""
+    therefore no smoothing.  The tremolo has no state, so this caveat does not apply to it: the re-render of a cropped
+    clip does not depend on the samples before the crop.  ``should_stretch`` is not wired in (the corner stretch has a backward, but not on this path)."""
     default_audio_loss_dict = {"mrstft": 1.0}
+    _nodes = {"flanger": _FlangerAudioLossFn, "tremolo": _TremoloAudioLossFn}
 
     def __init__(self,
                  model: nn.Module,
@@ -231,24 +261,31 @@ class LFOExtractionThroughEffect(BaseLightingModule):
                  audio_loss_dict: Optional[Dict[str, float]] = None,
                  loss_dict: Optional[Dict[str, float]] = None,
                  should_stretch: bool = False,
-                 check_fx_params: bool = False) -> None:
+                 check_fx_params: bool = False,
+                 effect: str = "flanger") -> None:
         super().__init__({} if loss_dict is None else loss_dict)
         from . import fx
         from .effect_losses import GRAD_NAMES
         if should_stretch:
             raise NotImplementedError("should_stretch is not supported when training through the rendered effect")
+        if effect not in self._nodes:
+            raise ValueError(f"effect '{effect}': supported are {tuple(self._nodes)}")
+        self.effect = effect
         audio_loss_dict = dict(self.default_audio_loss_dict if audio_loss_dict is None else audio_loss_dict)
         for name, w in audio_loss_dict.items():
             if w > 0 and name not in GRAD_NAMES:
                 raise NotImplementedError(f"audio loss '{name}' has no gradient kernel (supported: {GRAD_NAMES})")
         if not any(w > 0 for w in audio_loss_dict.values()):
             raise ValueError("audio_loss_dict needs at least one loss with a weight above 0")
-        if max_min_delay_ms < 0 or max_lfo_delay_ms < 0:
-            raise ValueError("max_min_delay_ms and max_lfo_delay_ms must not be negative")
-        self.max_min_delay_samples = fx.delay_samples(max_min_delay_ms, sr)
-        self.max_lfo_delay_samples = fx.delay_samples(max_lfo_delay_ms, sr)
+        if effect == "flanger":
+            if max_min_delay_ms < 0 or max_lfo_delay_ms < 0:
+                raise ValueError("max_min_delay_ms and max_lfo_delay_ms must not be negative")
+            self.max_min_delay_samples = fx.delay_samples(max_min_delay_ms, sr)
+            self.max_lfo_delay_samples = fx.delay_samples(max_lfo_delay_ms, sr)
+        else:                                                       # no delay line: the arguments are ignored
+            self.max_min_delay_samples = self.max_lfo_delay_samples = 0
         self.max_delay_samples = self.max_min_delay_samples + self.max_lfo_delay_samples
-        if not 2 <= self.max_delay_samples <= fx.FLANGER_MAX_DELAY_SAMPLES:
+        if effect == "flanger" and not 2 <= self.max_delay_samples <= fx.FLANGER_MAX_DELAY_SAMPLES:
             raise ValueError(f"delay line of {self.max_delay_samples} samples: the flanger kernels keep it in LDS and support "
                              f"2 .. {fx.FLANGER_MAX_DELAY_SAMPLES} samples (LFO row included)")
         self.model = model
@@ -283,6 +320,8 @@ class LFOExtractionThroughEffect(BaseLightingModule):
 
     def clip_constants(self, fx_params, bs: int, device) -> Dict[str, T]:
         from . import fx
+        if self.effect == "tremolo":
+            return fx.derive_tremolo_constants(bs, device, fx_params["mix"], check=self.check_fx_params)
         return fx.derive_clip_constants(bs, device, self.max_min_delay_samples, self.max_lfo_delay_samples,
                                         fx_params["feedback"], fx_params["min_delay_width"], fx_params["width"],
                                         fx_params["depth"], fx_params["mix"], check=self.check_fx_params)
@@ -293,19 +332,23 @@ class LFOExtractionThroughEffect(BaseLightingModule):
         return audio[:, 0, :]
 
     def render(self, dry: T, mod_sig: T, fx_params) -> T:
-        """wet_hat (B, 1, N) = the flanger of ``dry`` (B, 1, N) driven by ``mod_sig`` (B, n_mod) at its own rate, with the
-        per-clip constants of ``fx_params``; no graph (``mx_flanger_fwd``, the data path's launch)."""
+        """wet_hat (B, 1, N) = the effect on ``dry`` (B, 1, N) driven by ``mod_sig`` (B, n_mod) at its own rate, with the
+        per-clip constants of ``fx_params``; no graph (``mx_flanger_fwd`` / ``mx_tremolo_fwd``, the data path's launches)."""
         from . import fx
         rows = self._rows(dry)
         with torch.no_grad():
             consts = self.clip_constants(fx_params, rows.size(0), rows.device)
-            y = fx.flanger_forward(rows, mod_sig.detach().float().contiguous(), consts,
-                                   self._max_delay_rows(rows.size(0), rows.device), self.max_delay_samples)
+            mod = mod_sig.detach().float().contiguous()
+            if self.effect == "tremolo":
+                y = fx.tremolo_forward(rows, mod, consts)
+            else:
+                y = fx.flanger_forward(rows, mod, consts, self._max_delay_rows(rows.size(0), rows.device),
+                                       self.max_delay_samples)
         return y.unsqueeze(1)
 
     def audio_loss(self, mod_sig_hat: T, dry: T, wet: T, fx_params, prefix: Optional[str] = None):
         """(loss, wet_hat (B, 1, N)) for an LFO (B, n_frames); with grad mode on and an LFO that requires grad the loss
-        carries the graph of ``_FlangerAudioLossFn``, otherwise nothing is stashed and no backward kernel runs.  ``prefix``:
+        carries the graph of the effect's ``_EffectAudioLossFn``, otherwise nothing is stashed and no backward kernel runs.  ``prefix``:
         log every audio term under it."""
         from .effect_losses import effect_loss_terms
         dry_r, wet_r = self._rows(dry), self._rows(wet)
@@ -313,7 +356,7 @@ class LFOExtractionThroughEffect(BaseLightingModule):
         if torch.is_grad_enabled() and mod_sig_hat.requires_grad:
             with torch.no_grad():
                 consts = self.clip_constants(fx_params, dry_r.size(0), dry_r.device)
-            loss, wet_hat = _FlangerAudioLossFn.apply(mod_sig_hat, self, dry_r, wet_r, consts, terms)
+            loss, wet_hat = self._nodes[self.effect].apply(mod_sig_hat, self, dry_r, wet_r, consts, terms)
             wet_hat = wet_hat.unsqueeze(1)
         else:
             wet_hat, loss = self.render(dry, mod_sig_hat, fx_params), None
