@@ -222,6 +222,24 @@ int mx_phaser_bwd(const float *dy, int64_t dy_stride, const float *x, int64_t x_
                   int64_t dx_stride, float *dmod, int64_t dmod_stride, int64_t n_mod, double *d_depth,
                   double *d_centre, double *d_feedback, double *d_mix, void *stream);
 
+/* ---- K3c: the phaser's external LFO at a low rate (the reference has no counterpart: its phaser is pedalboard's, with a
+ * built-in oscillator and no gradient).  The linear map from a row of n_mod points spanning the N samples of the clip
+ * window (align_corners=True, the resampling of util.py:15-29 as the flanger and tremolo kernels evaluate it) to the
+ * cut-off-update grid of mx_phaser_fwd_stash / mx_phaser_bwd, and its transpose.
+ * mx_phaser_mod_expand: mod_lr (B, n_mod) fp32 dense, 1 <= n_mod <= N; lead (B,) int32 or NULL (= 0); x_width (>= N): valid
+ * floats of a source row, as given to mx_phaser_fwd_stash.  mod_g: row b at mod_g + b*mod_g_stride, mod_g_stride >=
+ * ceil(x_width / 4); every one of the ceil(x_width / 4) groups is written: group g < ceil((lead[b] + N) / 4) gets the row
+ * resampled at clip sample clamp(4 g - lead[b], 0, N - 1) (held at its first value through the lead-in; n_mod == N: a plain
+ * read), the others 0.5. */
+int mx_phaser_mod_expand(const float *mod_lr, int64_t n_mod, const int32_t *lead, int64_t B, int64_t N, int64_t x_width,
+                         float *mod_g, int64_t mod_g_stride, void *stream);
+/* The exact transpose.  dmod_g: row b at dmod_g + b*dmod_g_stride, n_groups valid floats (>= ceil(N / 4)) as mx_phaser_bwd
+ * wrote them (its dmod, dmod_stride, n_mod); lead, N, n_mod as given to mx_phaser_mod_expand.  dmod_lr (B, n_mod) fp32 dense:
+ * every point is the fp64 sum, in a fixed order, of weight x dmod_g over the groups with a tap on it, rounded once (no
+ * atomics: deterministic). */
+int mx_phaser_dmod_gather(const float *dmod_g, int64_t dmod_g_stride, int64_t n_groups, const int32_t *lead, int64_t B,
+                          int64_t N, int64_t n_mod, float *dmod_lr, void *stream);
+
 /* ---- K4: log-mel front end -- mod_extraction/models.py:170-181,199-208
  * (torchaudio MelSpectrogram: n_fft in {512, 1024, 2048} -- every shipped config: 1024 --, hann, centre/reflect, power 2,
  * mel filter bank `fb`; other n_fft: MX_ERR_UNSUPPORTED)

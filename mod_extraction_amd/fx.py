@@ -3,7 +3,8 @@
 kernel (one wavefront per clip, delay line in LDS) instead of 88 200 python iterations.
 ``apply_effect`` is differentiable (``mx_flanger_fwd_stash`` + ``mx_flanger_bwd`` / ``mx_flanger_bwd_lr``) when grad mode
 is on and an input requires grad; mod_sig may be full rate or the low-rate row the kernel resamples itself.  ``PhaserModule`` is the same for the phaser (``mx_phaser_fwd_stash`` + ``mx_phaser_bwd``), with the LFO
-either JUCE's built-in oscillator or an external signal.
+either JUCE's built-in oscillator or an external signal, on the cut-off-update grid or (``mod_sig_low_rate``) at any lower rate
+(``mx_phaser_mod_expand`` / ``mx_phaser_dmod_gather``).
 """
 from typing import Dict, Optional, Tuple, Union
 
@@ -368,6 +369,26 @@ PHASER_PARAM_GRADS = ("depth", "centre_frequency_hz", "feedback", "mix")
 _PS_P, _PS_MV, _PS_SUB = 512, 57, 2                 # csrc/phaser_common.h
 
 
+def derive_phaser_params(bs: int, device: torch.device, depth: Param, centre_frequency_hz: Param, feedback: Param,
+                         mix: Param, check: bool = True) -> Dict[str, T]:
+    """The per-clip (bs,) fp32 parameter dict of the phaser launches (no ``rate_hz``: for an external LFO) from python
+    floats or (bs,) tensors; ``check``: ``PhaserModule``'s ranges (host synchronisations for tensors)."""
+    if check:
+        _check_range(depth, bs, 0.0, 1.0)
+        _check_range(mix, bs, 0.0, 1.0)
+        _check_range(feedback, bs, -1.0, 1.0, lo_open=True, hi_open=True)
+        _check_range(centre_frequency_hz, bs, 0.0, float("inf"), lo_open=True)
+
+    def vec(p: Param) -> T:
+        if isinstance(p, T):
+            assert p.shape == (bs,)
+            return p.to(device=device, dtype=torch.float32).contiguous()
+        return torch.full((bs,), float(p), device=device, dtype=torch.float32)
+
+    return {"depth": vec(depth), "centre_frequency_hz": vec(centre_frequency_hz), "feedback": vec(feedback),
+            "mix": vec(mix)}
+
+
 def phaser_stash_shape(width: int) -> Tuple[int, int]:
     """(stash_groups, floats per stash row) for source rows of ``width`` samples (csrc/phaser_common.h)."""
     sg = ((width + 3) // 4 + 3) // 4 * 4
@@ -443,6 +464,54 @@ def phaser_backward(dy: T, src: T, stash: T, params: Dict[str, T], lead: Optiona
     return (dx if need_dx else None), (dmod if need_dmod else None), grads
 
 
+def phaser_mod_expand(mod_lr: T, lead: Optional[T], n_samples: int, width: int, out: Optional[T] = None) -> T:
+    """Launch mx_phaser_mod_expand: a low-rate LFO (B, n_mod), 1 <= n_mod <= n_samples, spanning the n_samples of the clip
+    window, as the (B, ceil(width / 4)) row ``phaser_forward_stash`` takes as ``mod``: group g of row b reads the row
+    resampled (as ``flanger_forward`` / ``tremolo_forward`` resample theirs) at clip sample
+    clamp(4 g - lead[b], 0, n_samples - 1) -- the LFO is held at its first value through the lead-in; groups beyond
+    lead[b] + n_samples hold 0.5."""
+    B, n_mod = mod_lr.shape
+    assert mod_lr.dtype == torch.float32 and mod_lr.is_contiguous() and 1 <= n_mod <= n_samples <= width
+    ng = (width + 3) // 4
+    mod_g = out if out is not None else torch.empty((B, ng), device=mod_lr.device, dtype=torch.float32)
+    assert mod_g.size(0) == B and mod_g.size(1) >= ng
+    mp, ms = _rows_view(mod_g)
+    _hip.call("mx_phaser_mod_expand", _hip.ptr(mod_lr), n_mod, _hip.ptr(lead), B, n_samples, width, mp, ms, _hip.stream())
+    return mod_g
+
+
+def phaser_dmod_gather(dmod_g: T, lead: Optional[T], n_samples: int, n_mod: int) -> T:
+    """Launch mx_phaser_dmod_gather, the transpose of ``phaser_mod_expand``: dmod_g (B, >= ceil(n_samples / 4)) as
+    ``phaser_backward`` returns it -> (B, n_mod) fp32 (fp64 sums in a fixed order, rounded once; deterministic)."""
+    B = dmod_g.size(0)
+    assert 1 <= n_mod <= n_samples
+    dp, ds = _rows_view(dmod_g)
+    dmod_lr = torch.empty((B, n_mod), device=dmod_g.device, dtype=torch.float32)
+    _hip.call("mx_phaser_dmod_gather", dp, ds, dmod_g.size(1), _hip.ptr(lead), B, n_samples, n_mod, _hip.ptr(dmod_lr),
+              _hip.stream())
+    return dmod_lr
+
+
+def phaser_forward_stash_lr(src: T, params: Dict[str, T], lead: Optional[T], sr: float, n_samples: int,
+                            mod_lr: T) -> Tuple[T, T, T]:
+    """``phaser_forward_stash`` driven by a low-rate LFO: mod_lr (B, n_mod) fp32, any 1 <= n_mod <= n_samples, spanning the
+    n_samples OUTPUT samples (the lead-in holds its first value).  Two launches: ``phaser_mod_expand``, then the stash
+    forward on the expanded row.  Returns (y, stash, mod_g): mod_g (B, ceil(W / 4)) is the row the scan read."""
+    mod_g = phaser_mod_expand(mod_lr, lead, n_samples, src.size(1))
+    y, stash = phaser_forward_stash(src, params, lead, sr, n_samples, mod=mod_g)
+    return y, stash, mod_g
+
+
+def phaser_backward_lr(dy: T, src: T, stash: T, params: Dict[str, T], lead: Optional[T], sr: float, n_samples: int,
+                       n_mod: int, need_dx: bool = True,
+                       params_wanted: Tuple[str, ...] = PHASER_PARAM_GRADS) -> Tuple[Optional[T], T, Dict[str, T]]:
+    """The adjoint of ``phaser_forward_stash_lr``: ``phaser_backward`` (dmod at group rate), then ``phaser_dmod_gather``.
+    Returns (dx (B, W) or None, dmod_lr (B, n_mod), the per-clip fp64 parameter gradients named in ``params_wanted``)."""
+    dx, dmod_g, grads = phaser_backward(dy, src, stash, params, lead, sr, n_samples, need_dx=need_dx, need_dmod=True,
+                                        params_wanted=params_wanted)
+    return dx, phaser_dmod_gather(dmod_g, lead, n_samples, n_mod), grads
+
+
 class _PhaserFunction(torch.autograd.Function):
     """y = phaser(x, mod | rate, parameters) over (clip, channel) rows; the (bs,) parameters are shared by a clip's n_ch
     rows, so their gradients are summed over the channels (in fp64) before they are rounded to the parameters' dtype."""
@@ -476,6 +545,40 @@ class _PhaserFunction(torch.autograd.Function):
         return tuple(out) + (None, None, None, None)
 
 
+class _PhaserLowRateFunction(torch.autograd.Function):
+    """``_PhaserFunction`` with the LFO at a low rate: mod (rows, n_mod) spans the n output samples
+    (``phaser_forward_stash_lr`` / ``phaser_backward_lr``); the group-rate row does not outlive the forward."""
+
+    @staticmethod
+    def forward(ctx, x, mod, depth, centre, feedback, mix, lead, n_ch, sr, n):
+        def rows_of(v):
+            return _per_row(v.detach().float(), n_ch)
+
+        params = {"depth": rows_of(depth), "centre_frequency_hz": rows_of(centre), "feedback": rows_of(feedback),
+                  "mix": rows_of(mix)}
+        y, stash, _ = phaser_forward_stash_lr(x.detach(), params, lead, sr, n, mod.detach())
+        ctx.save_for_backward(x, stash)
+        ctx.params, ctx.lead, ctx.n_ch, ctx.sr, ctx.n, ctx.n_mod = params, lead, n_ch, sr, n, mod.size(1)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        x, stash = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        wanted = tuple(k for k, n in zip(PHASER_PARAM_GRADS, need[2:6]) if n)
+        if need[1]:
+            dx, dmod, g = phaser_backward_lr(dy, x, stash, ctx.params, ctx.lead, ctx.sr, ctx.n, ctx.n_mod, need_dx=need[0],
+                                             params_wanted=wanted)
+        else:
+            dx, dmod, g = phaser_backward(dy, x, stash, ctx.params, ctx.lead, ctx.sr, ctx.n, need_dx=need[0],
+                                          need_dmod=False, params_wanted=wanted)
+        out = [dx, dmod]
+        for k in PHASER_PARAM_GRADS:
+            out.append(g[k].view(-1, ctx.n_ch).sum(1).float() if k in g else None)
+        return tuple(out) + (None, None, None, None)
+
+
 class PhaserModule(nn.Module):
     """The phaser of the data pipeline (pedalboard.Phaser = JUCE dsp::Phaser semantics, ``phaser_forward``) as a module in
     the shape of ``MonoFlangerChorusModule``; the reference has no counterpart (its phaser is pedalboard's, on the CPU,
@@ -488,6 +591,10 @@ class PhaserModule(nn.Module):
     * mod_sig, values in [0, 1], in the convention of the reference's phaser ground truth
       ``make_mod_signal(.., pi / 2, "cos")`` = (1 + sin wt) / 2, so that JUCE's osc = 1 - 2 mod: (bs, ceil(width / 4)), one value per cut-off update, or full rate
       (bs, width), which is sampled at samples 0, 4, 8, ...; optionally with a channel axis of 1 or n_ch.
+      With ``mod_sig_low_rate=True`` it is instead (bs, n_mod) (or with a channel axis of 1 or n_ch) at any 1 <= n_mod <= n
+      and spans the n OUTPUT samples, resampled as the flanger and the tremolo resample theirs (align_corners=True,
+      ``mx_phaser_mod_expand``); through the lead-in the LFO holds its first value.  Gradients as on the default path, the
+      one of mod_sig at its own rate (``mx_phaser_dmod_gather``).
     depth, mix in [0, 1], feedback in (-1, 1) (JUCE's range), centre_frequency_hz > 0 (centres outside 20 Hz .. 20 kHz
     clamp): python floats or (bs,) tensors.
 
@@ -503,7 +610,7 @@ class PhaserModule(nn.Module):
         self.sr = sr
 
     def _prepare(self, x: T, mod_sig: Optional[T], rate_hz: Optional[Param], depth: Param, centre_frequency_hz: Param,
-                 feedback: Param, mix: Param, lead):
+                 feedback: Param, mix: Param, lead, low_rate: bool = False):
         assert x.ndim == 3
         bs, n_ch, W = x.shape
         assert (mod_sig is None) != (rate_hz is None), "exactly one of mod_sig and rate_hz"
@@ -537,7 +644,13 @@ class PhaserModule(nn.Module):
         if xr.stride(-1) != 1:
             xr = xr.contiguous()
         mr = None
-        if mod_sig is not None:
+        if low_rate:
+            assert mod_sig is not None, "mod_sig_low_rate needs a mod_sig"
+            assert mod_sig.size(0) == bs and mod_sig.ndim in (2, 3) and 1 <= mod_sig.size(-1) <= n
+            if mod_sig.ndim == 3:
+                assert mod_sig.size(1) in (1, n_ch)
+            mr = _channel_rows_of(x, mod_sig)[1]                      # a mod_sig without a channel axis: shared by the channels
+        elif mod_sig is not None:
             n_mod = (W + 3) // 4
             assert mod_sig.size(0) == bs and mod_sig.ndim in (2, 3)
             if mod_sig.ndim == 3:
@@ -552,26 +665,33 @@ class PhaserModule(nn.Module):
         return xr, mr, ps, lead_rows, n, (bs, n_ch)
 
     def apply_effect(self, x: T, mod_sig: Optional[T] = None, rate_hz: Optional[Param] = None, depth: Param = 1.0,
-                     centre_frequency_hz: Param = 1300.0, feedback: Param = 0.0, mix: Param = 1.0, lead=None) -> T:
+                     centre_frequency_hz: Param = 1300.0, feedback: Param = 0.0, mix: Param = 1.0, lead=None,
+                     mod_sig_low_rate: bool = False) -> T:
         params = (depth, centre_frequency_hz, feedback, mix)
         if not (torch.is_grad_enabled() and (x.requires_grad or (mod_sig is not None and mod_sig.requires_grad) or
                                              any(isinstance(p, T) and p.requires_grad for p in params))):
             if isinstance(rate_hz, T) and rate_hz.requires_grad and torch.is_grad_enabled():
                 raise ValueError("PhaserModule has no gradient with respect to rate_hz: pass the LFO as mod_sig instead")
-            return self.forward(x, mod_sig, rate_hz, depth, centre_frequency_hz, feedback, mix, lead)
-        xr, mr, ps, lead_rows, n, (bs, n_ch) = self._prepare(x, mod_sig, rate_hz, *params, lead)
-        y = _PhaserFunction.apply(xr, mr, *ps, lead_rows, n_ch, self.sr, n)
+            return self.forward(x, mod_sig, rate_hz, depth, centre_frequency_hz, feedback, mix, lead, mod_sig_low_rate)
+        xr, mr, ps, lead_rows, n, (bs, n_ch) = self._prepare(x, mod_sig, rate_hz, *params, lead, mod_sig_low_rate)
+        if mod_sig_low_rate:
+            y = _PhaserLowRateFunction.apply(xr, mr, *ps[1:], lead_rows, n_ch, self.sr, n)
+        else:
+            y = _PhaserFunction.apply(xr, mr, *ps, lead_rows, n_ch, self.sr, n)
         return y.view(bs, n_ch, n)
 
     def forward(self, x: T, mod_sig: Optional[T] = None, rate_hz: Optional[Param] = None, depth: Param = 1.0,
-                centre_frequency_hz: Param = 1300.0, feedback: Param = 0.0, mix: Param = 1.0, lead=None) -> T:
+                centre_frequency_hz: Param = 1300.0, feedback: Param = 0.0, mix: Param = 1.0, lead=None,
+                mod_sig_low_rate: bool = False) -> T:
         with torch.no_grad():
             xr, mr, ps, lead_rows, n, (bs, n_ch) = self._prepare(x, mod_sig, rate_hz, depth, centre_frequency_hz, feedback,
-                                                                 mix, lead)
+                                                                 mix, lead, mod_sig_low_rate)
             p = {k: _per_row(v.float(), n_ch) for k, v in zip(("rate_hz", "depth", "centre_frequency_hz", "feedback", "mix"), ps)
                  if v is not None}
             if mr is None:
                 y = phaser_forward(xr, p, lead_rows, self.sr, n)
+            elif mod_sig_low_rate:
+                y = phaser_forward_stash_lr(xr, p, lead_rows, self.sr, n, mr)[0]
             else:
                 y, _ = phaser_forward_stash(xr, p, lead_rows, self.sr, n, mod=mr)
         return y.view(bs, n_ch, n)

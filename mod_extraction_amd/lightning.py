@@ -220,26 +220,42 @@ class _TremoloAudioLossFn(_EffectAudioLossFn):
             dy, dry, mod, consts, need_dx=False, need_dmix=False)[1])
 
 
+class _PhaserAudioLossFn(_EffectAudioLossFn):
+    """The phaser: ``mx_phaser_mod_expand`` + ``mx_phaser_fwd_stash`` on the low-rate LFO (lead 0, empty filter state) and
+    ``mx_phaser_bwd`` + ``mx_phaser_dmod_gather`` asked for dmod alone; the stash and the two group-rate rows do not
+    outlive the call."""
+
+    @staticmethod
+    def forward(ctx, mod_sig_hat, step, dry, wet, consts, terms):
+        from . import fx
+        mod = mod_sig_hat.detach().float().contiguous()
+        n = dry.size(1)
+        wet_hat, stash, _ = fx.phaser_forward_stash_lr(dry, consts, None, step.sr, n, mod)
+        return _audio_loss_node(ctx, step, wet_hat, wet, terms, lambda dy: fx.phaser_backward_lr(
+            dy, dry, stash, consts, None, step.sr, n, mod.size(1), need_dx=False, params_wanted=())[1])
+
+
 class LFOExtractionThroughEffect(BaseLightingModule):
     """Trains the LFO extractor on dry / wet pairs WITHOUT an LFO label: the extractor's LFO drives a differentiable
-    effect -- ``effect="flanger"`` (flanger / chorus, the default) or ``effect="tremolo"`` -- on ``dry`` and an audio-domain
+    effect -- ``effect="flanger"`` (flanger / chorus, the default), ``effect="tremolo"`` or ``effect="phaser"`` -- on ``dry`` and an audio-domain
     loss compares the result with ``wet``.  The reference has no such step
     (its lightning.py:65-199 trains against the ground-truth LFO only; its flanger, fx.py:72-119, has no usable autograd).
 
     Same batch 4-tuple ``(dry, wet, mod_sig, fx_params)`` and metric naming as ``LFOExtraction``; ``training_step`` returns a
     loss with a grad graph, so ``trainer.Trainer`` drives it unchanged.
     * ``max_min_delay_ms`` / ``max_lfo_delay_ms``: ONE flanger or chorus geometry per module, as in
-      ``fx.MonoFlangerChorusModule`` (batches that mix geometries are out of scope; so are phaser rows, whose render needs
-      lead-in samples the batch does not carry).  ``effect="tremolo"`` ignores both and has no delay-line limit.
+      ``fx.MonoFlangerChorusModule`` (batches that mix geometries are out of scope).  ``effect="tremolo"`` and
+      ``effect="phaser"`` ignore both and have no delay-line limit.
     * ``effect``: ONE effect family per module; a batch that mixes effects is out of scope.
     * ``fx_params`` carries the per-clip ``feedback``, ``min_delay_width``, ``width``, ``depth``, ``mix`` as (B,) tensors;
-      the tremolo needs only ``mix``
+      the tremolo needs only ``mix``; the phaser needs ``depth``, ``centre_frequency_hz``, ``feedback``, ``mix`` (its
+      ``rate_hz`` and ``lead`` are ignored: the LFO is the extractor's)
       (``check_fx_params``: range-check them on every step, which costs host synchronisations).
     * ``audio_loss_dict``: names from ``effect_losses.GRAD_NAMES``; zero-weight names are only logged.
     * ``loss_dict`` (optional, default none): an LFO-domain term (lightning.py:33-62) added to the loss when the batch carries
       ``mod_sig``; it is logged as ``{prefix}/lfo_{name}``.
     The LFO enters the effect at the extractor's own rate (n_frames points, resampled in-kernel exactly as the data path
-    resamples its n_samples // 100 label), so a re-render from the label the batch was rendered with is bit-identical to
+    resamples its n_samples // 100 label), so for the flanger and the tremolo a re-render from the label the batch was rendered with is bit-identical to
     ``wet`` and every loss is exactly 0 there.
 
     ``model_smooth_n_frames`` > 1 applies the moving average (with its transpose in the backward) and centre-crops dry and
@@ -247,9 +263,19 @@ class LFOExtractionThroughEffect(BaseLightingModule):
     EMPTY delay line at the first cropped sample, whereas the recorded wet had the samples before the crop in its line, so
     the first ``max_delay_samples`` samples of ``wet_hat`` differ from ``wet`` even for the true LFO.  The default is
     therefore no smoothing.  The tremolo has no state, so this caveat does not apply to it: the re-render of a cropped
-    clip does not depend on the samples before the crop.  ``should_stretch`` is not wired in (the corner stretch has a backward, but not on this path)."""
+    clip does not depend on the samples before the crop.
+
+    ``effect="phaser"``, the lead-in rule: the step re-renders from ``dry`` ALONE, with lead 0 and empty filter state
+    (``mx_phaser_fwd_stash`` on the LFO expanded by ``mx_phaser_mod_expand``).  The batch's ``wet`` was rendered by JUCE's
+    oscillator after ``fx_params["lead"]`` warm-up samples, which the batch tuple does not carry -- in the reference and the
+    data path that lead exists to randomise the LFO's phase.  So at the true label the loss is small but NOT exactly 0, for
+    three reasons: the start transient of the six all-passes and the feedback path; a cut-off-update grid shifted by
+    ``lead % 4`` samples against the recorded one; and a label that is the sine linearly interpolated from
+    ``n_samples // 100`` points.  The same kind of caveat as the flanger's crop above.
+
+    ``should_stretch`` is not wired in (the corner stretch has a backward, but not on this path)."""
     default_audio_loss_dict = {"mrstft": 1.0}
-    _nodes = {"flanger": _FlangerAudioLossFn, "tremolo": _TremoloAudioLossFn}
+    _nodes = {"flanger": _FlangerAudioLossFn, "tremolo": _TremoloAudioLossFn, "phaser": _PhaserAudioLossFn}
 
     def __init__(self,
                  model: nn.Module,
@@ -322,6 +348,9 @@ class LFOExtractionThroughEffect(BaseLightingModule):
         from . import fx
         if self.effect == "tremolo":
             return fx.derive_tremolo_constants(bs, device, fx_params["mix"], check=self.check_fx_params)
+        if self.effect == "phaser":
+            return fx.derive_phaser_params(bs, device, fx_params["depth"], fx_params["centre_frequency_hz"],
+                                           fx_params["feedback"], fx_params["mix"], check=self.check_fx_params)
         return fx.derive_clip_constants(bs, device, self.max_min_delay_samples, self.max_lfo_delay_samples,
                                         fx_params["feedback"], fx_params["min_delay_width"], fx_params["width"],
                                         fx_params["depth"], fx_params["mix"], check=self.check_fx_params)
@@ -333,7 +362,8 @@ class LFOExtractionThroughEffect(BaseLightingModule):
 
     def render(self, dry: T, mod_sig: T, fx_params) -> T:
         """wet_hat (B, 1, N) = the effect on ``dry`` (B, 1, N) driven by ``mod_sig`` (B, n_mod) at its own rate, with the
-        per-clip constants of ``fx_params``; no graph (``mx_flanger_fwd`` / ``mx_tremolo_fwd``, the data path's launches)."""
+        per-clip constants of ``fx_params``; no graph (``mx_flanger_fwd`` / ``mx_tremolo_fwd``, the data path's launches; the
+        phaser: ``mx_phaser_mod_expand`` + ``mx_phaser_fwd_stash`` with lead 0, see the class docstring)."""
         from . import fx
         rows = self._rows(dry)
         with torch.no_grad():
@@ -341,6 +371,8 @@ class LFOExtractionThroughEffect(BaseLightingModule):
             mod = mod_sig.detach().float().contiguous()
             if self.effect == "tremolo":
                 y = fx.tremolo_forward(rows, mod, consts)
+            elif self.effect == "phaser":
+                y = fx.phaser_forward_stash_lr(rows, consts, None, self.sr, rows.size(1), mod)[0]
             else:
                 y = fx.flanger_forward(rows, mod, consts, self._max_delay_rows(rows.size(0), rows.device),
                                        self.max_delay_samples)

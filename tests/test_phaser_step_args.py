@@ -1,0 +1,52 @@
+"""CPU: the arguments of lightning.LFOExtractionThroughEffect(effect="phaser") (no device work: nothing is rendered)."""
+import pytest
+import torch
+
+
+def test_phaser_step_constructs_and_ignores_the_delay_arguments():
+    from mod_extraction_amd import lightning
+    step = lightning.LFOExtractionThroughEffect(torch.nn.Identity(), effect="phaser")
+    assert step.effect == "phaser" and step.max_delay_samples == 0
+    # the delay arguments are ignored: values the flanger refuses are accepted
+    lightning.LFOExtractionThroughEffect(torch.nn.Identity(), effect="phaser", max_min_delay_ms=-1.0, max_lfo_delay_ms=1e6)
+    with pytest.raises(ValueError):
+        lightning.LFOExtractionThroughEffect(torch.nn.Identity(), max_min_delay_ms=-1.0)
+
+
+def test_phaser_step_lists_its_metrics():
+    from mod_extraction_amd import lightning
+    step = lightning.LFOExtractionThroughEffect(torch.nn.Identity(), effect="phaser",
+                                                audio_loss_dict={"mrstft": 1.0, "log_mel_l1": 0.5, "esr": 0.0},
+                                                loss_dict={"l1": 1.0})
+    assert step.loss_dict == {"mrstft": 1.0, "log_mel_l1": 0.5, "esr": 0.0, "lfo_l1": 1.0}
+    assert lightning.LFOExtractionThroughEffect(torch.nn.Identity(), effect="phaser").loss_dict == {"mrstft": 1.0}
+
+
+def test_phaser_node_is_registered_and_unknown_effects_still_raise():
+    from mod_extraction_amd import lightning
+    assert set(lightning.LFOExtractionThroughEffect._nodes) == {"flanger", "tremolo", "phaser"}
+    assert issubclass(lightning._PhaserAudioLossFn, lightning._EffectAudioLossFn)
+    with pytest.raises(ValueError):
+        lightning.LFOExtractionThroughEffect(torch.nn.Identity(), effect="wah")
+
+
+def test_should_stretch_still_raises():
+    from mod_extraction_amd import lightning
+    with pytest.raises(NotImplementedError):
+        lightning.LFOExtractionThroughEffect(torch.nn.Identity(), effect="phaser", should_stretch=True)
+
+
+def test_phaser_params_come_from_fx_params_and_are_range_checked():
+    from mod_extraction_amd import fx
+    cpu = torch.device("cpu")
+    fxp = {"depth": torch.tensor([0.5, 1.0]), "centre_frequency_hz": torch.tensor([440.0, 1300.0]),
+           "feedback": torch.tensor([0.0, 0.7]), "mix": torch.tensor([0.2, 1.0])}
+    p = fx.derive_phaser_params(2, cpu, **fxp)
+    assert set(p) == {"depth", "centre_frequency_hz", "feedback", "mix"}                # no rate_hz: the LFO is external
+    assert all(v.dtype == torch.float32 and v.shape == (2,) and v.is_contiguous() for v in p.values())
+    assert torch.equal(p["feedback"], fxp["feedback"])
+    for bad in ({"feedback": torch.tensor([0.0, 1.0])}, {"depth": torch.tensor([0.5, 1.5])},
+                {"mix": torch.tensor([-0.1, 1.0])}, {"centre_frequency_hz": torch.tensor([0.0, 440.0])}):
+        with pytest.raises(AssertionError):
+            fx.derive_phaser_params(2, cpu, **dict(fxp, **bad))
+        fx.derive_phaser_params(2, cpu, **dict(fxp, **bad), check=False)               # check_fx_params=False: not looked at
