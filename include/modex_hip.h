@@ -239,6 +239,20 @@ int mx_phaser_mod_expand(const float *mod_lr, int64_t n_mod, const int32_t *lead
  * atomics: deterministic). */
 int mx_phaser_dmod_gather(const float *dmod_g, int64_t dmod_g_stride, int64_t n_groups, const int32_t *lead, int64_t B,
                           int64_t N, int64_t n_mod, float *dmod_lr, void *stream);
+/* The two maps on a LIST of rows (the reference has no counterpart): for the phaser clips of a batch that mixes effects, whose
+ * LFO rows and gradient rows lie among the other effects' in shared (B, .) buffers.  rows: n_rows int32 clip indices on the
+ * device, 1 <= n_rows <= B, in any order; the grid covers n_rows x tiles and a workgroup works on b = rows[blockIdx.x / tiles].
+ * Every buffer stays indexed by the full-batch row b (mod_lr + b*n_mod, lead[b], mod_g + b*mod_g_stride, dmod_g +
+ * b*dmod_g_stride, dmod_lr + b*n_mod); a row that is not listed is neither read nor written; a listed row holds the bits
+ * mx_phaser_mod_expand / mx_phaser_dmod_gather give it (same taps, same fp64 order, one cast; no atomics: deterministic).
+ * rows == NULL, n_rows < 1 or n_rows > B: MX_ERR_ARG; the other checks and the grid limits (MX_ERR_UNSUPPORTED) as above, all
+ * before any launch.  The indices themselves are device data and are NOT checked by the host: the kernels skip an index
+ * outside 0 .. B - 1. */
+int mx_phaser_mod_expand_rows(const float *mod_lr, int64_t n_mod, const int32_t *lead, const int32_t *rows, int64_t n_rows,
+                              int64_t B, int64_t N, int64_t x_width, float *mod_g, int64_t mod_g_stride, void *stream);
+int mx_phaser_dmod_gather_rows(const float *dmod_g, int64_t dmod_g_stride, int64_t n_groups, const int32_t *lead,
+                               const int32_t *rows, int64_t n_rows, int64_t B, int64_t N, int64_t n_mod, float *dmod_lr,
+                               void *stream);
 
 /* ---- K4: log-mel front end -- mod_extraction/models.py:170-181,199-208
  * (torchaudio MelSpectrogram: n_fft in {512, 1024, 2048} -- every shipped config: 1024 --, hann, centre/reflect, power 2,

@@ -48,6 +48,8 @@ SIGNATURES = {
                       _P, _I64, _I64, _P, _P, _P, _P, _P],
     "mx_phaser_mod_expand": [_P, _I64, _P, _I64, _I64, _I64, _P, _I64, _P],
     "mx_phaser_dmod_gather": [_P, _I64, _I64, _P, _I64, _I64, _I64, _P, _P],
+    "mx_phaser_mod_expand_rows": [_P, _I64, _P, _P, _I64, _I64, _I64, _I64, _P, _I64, _P],
+    "mx_phaser_dmod_gather_rows": [_P, _I64, _I64, _P, _P, _I64, _I64, _I64, _I64, _P, _P],
     "mx_logmel_fwd": [_P, _I64, _I64, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _F32, _I32, _I32,
                       _I32, _I32, _P, _P],
     "mx_conv_pack_weights": [_P, _I64, _I64, _I32, _P, _P],

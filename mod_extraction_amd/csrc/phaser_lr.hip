@@ -15,6 +15,12 @@
 //            group comes from an estimate that is corrected with the forward's own taps, as tremolo.hip pass 2 does.  The
 //            weights are interp_tap's fp32 taps, products and sums fp64 in a fixed order (per lane, then a butterfly),
 //            rounded to fp32 once.  No atomics, no (B, N) workspace: two runs are bit-identical.
+//
+// Both kernels take an optional row list (mx_phaser_mod_expand_rows / mx_phaser_dmod_gather_rows): the grid then covers
+// n_rows x tiles and a workgroup works on row b = rows[blockIdx.x / tiles] of the FULL batch -- every buffer stays indexed by
+// b, rows that are not listed are neither read nor written, and a listed row goes through the very same code as without a
+// list, so its result has the same bits.  That lets the phaser rows of a batch of mixed effects write into buffers they share
+// with the other effects' rows.
 #include "common.h"
 
 #define PL_THREADS 256
@@ -43,12 +49,13 @@ __device__ __forceinline__ int pl_groups(int lead, int N, int n_groups)
 }
 
 __global__ __launch_bounds__(PL_THREADS) void phaser_mod_expand_kernel(
-    const float *__restrict__ mod_lr, int n_mod, float scale, const int *__restrict__ lead, int N, int n_groups, int tiles,
-    float *__restrict__ mod_g, long long mod_g_stride)
+    const float *__restrict__ mod_lr, int n_mod, float scale, const int *__restrict__ lead, const int *__restrict__ rows,
+    int B, int N, int n_groups, int tiles, float *__restrict__ mod_g, long long mod_g_stride)
 {
-    const int b = (int)(blockIdx.x / (unsigned)tiles), tile = (int)(blockIdx.x % (unsigned)tiles);
+    const int item = (int)(blockIdx.x / (unsigned)tiles), tile = (int)(blockIdx.x % (unsigned)tiles);
+    const int b = rows ? rows[item] : item;
     const int g = tile * PL_THREADS + (int)threadIdx.x;
-    if (g >= n_groups) return;
+    if (g >= n_groups || (unsigned)b >= (unsigned)B) return;          // a listed index outside the batch: nothing is touched
     const int ld = lead ? lead[b] : 0;
     const float *row = mod_lr + (size_t)b * n_mod;
     float v = 0.5f;
@@ -65,13 +72,15 @@ __global__ __launch_bounds__(PL_THREADS) void phaser_mod_expand_kernel(
 }
 
 __global__ __launch_bounds__(PL_THREADS) void phaser_dmod_gather_kernel(
-    const float *__restrict__ dmod_g, long long dmod_g_stride, int n_groups, const int *__restrict__ lead, int N, int n_mod,
-    float scale, int tiles, float *__restrict__ dmod_lr)
+    const float *__restrict__ dmod_g, long long dmod_g_stride, int n_groups, const int *__restrict__ lead,
+    const int *__restrict__ rows, int B, int N, int n_mod, float scale, int tiles, float *__restrict__ dmod_lr)
 {
-    const int b = (int)(blockIdx.x / (unsigned)tiles), tile = (int)(blockIdx.x % (unsigned)tiles);
+    const int item = (int)(blockIdx.x / (unsigned)tiles), tile = (int)(blockIdx.x % (unsigned)tiles);
+    const int b = rows ? rows[item] : item;                           // the same for the whole workgroup
     const int lane = threadIdx.x & 63;
     const int k = tile * PL_WAVES + (int)(threadIdx.x >> 6);
-    if (k >= n_mod) return;                                           // whole waves leave: the butterfly below stays full
+    // whole waves leave (k is one per wave, b one per workgroup): the butterfly below stays full
+    if (k >= n_mod || (unsigned)b >= (unsigned)B) return;
     const int ld = lead ? lead[b] : 0;
     const int G = pl_groups(ld, N, n_groups);
     const float *gb = dmod_g + (size_t)b * dmod_g_stride;
@@ -98,6 +107,37 @@ __global__ __launch_bounds__(PL_THREADS) void phaser_dmod_gather_kernel(
 }
 
 // C ABI ---------------------------------------------------------------------------------------
+// rows: NULL (all B rows, grid B x tiles) or n_rows indices on the device (grid n_rows x tiles)
+static int pl_launch_expand(const float *mod_lr, int64_t n_mod, const int32_t *lead, const int32_t *rows, int64_t n_rows,
+                            int64_t B, int64_t N, int64_t x_width, float *mod_g, int64_t mod_g_stride, void *stream)
+{
+    if (!mod_lr || !mod_g || B <= 0 || N <= 0 || n_mod < 1 || n_mod > N || x_width < N) return MX_ERR_ARG;
+    if (x_width >= (1ll << 30)) return MX_ERR_UNSUPPORTED;
+    const int64_t n_groups = (x_width + 3) / 4;
+    if (mod_g_stride < n_groups) return MX_ERR_ARG;
+    const int64_t tiles = (n_groups + PL_THREADS - 1) / PL_THREADS, items = rows ? n_rows : B;
+    if (B >= (1ll << 31) || items * tiles >= (1ll << 31)) return MX_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(phaser_mod_expand_kernel, dim3((unsigned)(items * tiles)), dim3(PL_THREADS), 0, (hipStream_t)stream,
+                       mod_lr, (int)n_mod, interp_scale_host(n_mod, N), lead, rows, (int)B, (int)N, (int)n_groups,
+                       (int)tiles, mod_g, (long long)mod_g_stride);
+    return mx_launch_status();
+}
+
+static int pl_launch_gather(const float *dmod_g, int64_t dmod_g_stride, int64_t n_groups, const int32_t *lead,
+                            const int32_t *rows, int64_t n_rows, int64_t B, int64_t N, int64_t n_mod, float *dmod_lr,
+                            void *stream)
+{
+    if (!dmod_g || !dmod_lr || B <= 0 || N <= 0 || n_mod < 1 || n_mod > N) return MX_ERR_ARG;
+    if (n_groups < (N + 3) / 4 || dmod_g_stride < n_groups) return MX_ERR_ARG;
+    if (n_groups >= (1ll << 28)) return MX_ERR_UNSUPPORTED;
+    const int64_t tiles = (n_mod + PL_WAVES - 1) / PL_WAVES, items = rows ? n_rows : B;
+    if (B >= (1ll << 31) || items * tiles >= (1ll << 31)) return MX_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(phaser_dmod_gather_kernel, dim3((unsigned)(items * tiles)), dim3(PL_THREADS), 0, (hipStream_t)stream,
+                       dmod_g, (long long)dmod_g_stride, (int)n_groups, lead, rows, (int)B, (int)N, (int)n_mod,
+                       interp_scale_host(n_mod, N), (int)tiles, dmod_lr);
+    return mx_launch_status();
+}
+
 // mod_lr (B, n_mod) fp32 dense, 1 <= n_mod <= N, spanning the N samples of the clip window (align_corners=True); lead (B,)
 // int32 lead-in samples of every row, or NULL for 0; x_width: valid floats of a source row (>= N), as given to
 // mx_phaser_fwd_stash.  Output mod_g: row b at mod_g + b*mod_g_stride, ceil(x_width / 4) floats, ALL written (0.5 beyond the
@@ -105,16 +145,7 @@ __global__ __launch_bounds__(PL_THREADS) void phaser_dmod_gather_kernel(
 MX_EXPORT int mx_phaser_mod_expand(const float *mod_lr, int64_t n_mod, const int32_t *lead, int64_t B, int64_t N,
                                    int64_t x_width, float *mod_g, int64_t mod_g_stride, void *stream)
 {
-    if (!mod_lr || !mod_g || B <= 0 || N <= 0 || n_mod < 1 || n_mod > N || x_width < N) return MX_ERR_ARG;
-    if (x_width >= (1ll << 30)) return MX_ERR_UNSUPPORTED;
-    const int64_t n_groups = (x_width + 3) / 4;
-    if (mod_g_stride < n_groups) return MX_ERR_ARG;
-    const int64_t tiles = (n_groups + PL_THREADS - 1) / PL_THREADS;
-    if (B * tiles >= (1ll << 31)) return MX_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(phaser_mod_expand_kernel, dim3((unsigned)(B * tiles)), dim3(PL_THREADS), 0, (hipStream_t)stream,
-                       mod_lr, (int)n_mod, interp_scale_host(n_mod, N), lead, (int)N, (int)n_groups, (int)tiles, mod_g,
-                       (long long)mod_g_stride);
-    return mx_launch_status();
+    return pl_launch_expand(mod_lr, n_mod, lead, nullptr, 0, B, N, x_width, mod_g, mod_g_stride, stream);
 }
 
 // The transpose of mx_phaser_mod_expand.  dmod_g: row b at dmod_g + b*dmod_g_stride, n_groups valid floats as mx_phaser_bwd
@@ -123,13 +154,27 @@ MX_EXPORT int mx_phaser_mod_expand(const float *mod_lr, int64_t n_mod, const int
 MX_EXPORT int mx_phaser_dmod_gather(const float *dmod_g, int64_t dmod_g_stride, int64_t n_groups, const int32_t *lead,
                                     int64_t B, int64_t N, int64_t n_mod, float *dmod_lr, void *stream)
 {
-    if (!dmod_g || !dmod_lr || B <= 0 || N <= 0 || n_mod < 1 || n_mod > N) return MX_ERR_ARG;
-    if (n_groups < (N + 3) / 4 || dmod_g_stride < n_groups) return MX_ERR_ARG;
-    if (n_groups >= (1ll << 28)) return MX_ERR_UNSUPPORTED;
-    const int64_t tiles = (n_mod + PL_WAVES - 1) / PL_WAVES;
-    if (B * tiles >= (1ll << 31)) return MX_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(phaser_dmod_gather_kernel, dim3((unsigned)(B * tiles)), dim3(PL_THREADS), 0, (hipStream_t)stream,
-                       dmod_g, (long long)dmod_g_stride, (int)n_groups, lead, (int)N, (int)n_mod,
-                       interp_scale_host(n_mod, N), (int)tiles, dmod_lr);
-    return mx_launch_status();
+    return pl_launch_gather(dmod_g, dmod_g_stride, n_groups, lead, nullptr, 0, B, N, n_mod, dmod_lr, stream);
+}
+
+// mx_phaser_mod_expand on the n_rows rows listed in rows (device int32, 1 <= n_rows <= B; the indices themselves are device
+// data and are not checked here: one outside 0 .. B - 1 is skipped by the kernel).  mod_lr, lead and mod_g are the full
+// batch's: a listed row b reads mod_lr + b*n_mod and lead[b] and writes mod_g + b*mod_g_stride, with the bits of the un-listed
+// launch; the other rows are neither read nor written.
+MX_EXPORT int mx_phaser_mod_expand_rows(const float *mod_lr, int64_t n_mod, const int32_t *lead, const int32_t *rows,
+                                        int64_t n_rows, int64_t B, int64_t N, int64_t x_width, float *mod_g,
+                                        int64_t mod_g_stride, void *stream)
+{
+    if (!rows || n_rows < 1 || n_rows > B) return MX_ERR_ARG;
+    return pl_launch_expand(mod_lr, n_mod, lead, rows, n_rows, B, N, x_width, mod_g, mod_g_stride, stream);
+}
+
+// mx_phaser_dmod_gather on the listed rows, same contract: row b of dmod_lr (B, n_mod) is written for every listed b, the
+// others keep what they held (e.g. the gradient rows of the other effects of a mixed batch).
+MX_EXPORT int mx_phaser_dmod_gather_rows(const float *dmod_g, int64_t dmod_g_stride, int64_t n_groups, const int32_t *lead,
+                                         const int32_t *rows, int64_t n_rows, int64_t B, int64_t N, int64_t n_mod,
+                                         float *dmod_lr, void *stream)
+{
+    if (!rows || n_rows < 1 || n_rows > B) return MX_ERR_ARG;
+    return pl_launch_gather(dmod_g, dmod_g_stride, n_groups, lead, rows, n_rows, B, N, n_mod, dmod_lr, stream);
 }

@@ -144,10 +144,13 @@ def tremolo_forward(x: T, mod_sig: T, consts: Dict[str, T], rows: Optional[T] = 
 
 
 def tremolo_backward(dy: T, x: T, mod_sig: T, consts: Dict[str, T], rows: Optional[T] = None, need_dx: bool = True,
-                     need_dmod: bool = True, need_dmix: bool = True) -> Tuple[Optional[T], Optional[T], Optional[T]]:
+                     need_dmod: bool = True, need_dmix: bool = True,
+                     dmod: Optional[T] = None) -> Tuple[Optional[T], Optional[T], Optional[T]]:
     """Launch mx_tremolo_bwd: the adjoint of fx.py:13-22 behind the in-kernel resampling.  dy, x: (B,N) views with
     contiguous rows; mod_sig (B,n_mod) as the forward was given.  Returns dx (B,N) fp32, dmod (B,n_mod) fp32 and dmix (B,)
-    fp64 (the one_minus_mix path included), each None unless asked for; rows not listed in ``rows`` hold zeros."""
+    fp64 (the one_minus_mix path included), each None unless asked for; rows not listed in ``rows`` hold zeros.  dmod: an
+    optional (B,n_mod) dense output (e.g. a gradient shared with other effects) whose listed rows are written and whose
+    other rows are not touched."""
     B, N = x.shape
     dev = x.device
     n_mod = mod_sig.size(1)
@@ -156,7 +159,11 @@ def tremolo_backward(dy: T, x: T, mod_sig: T, consts: Dict[str, T], rows: Option
         dy = dy.contiguous()
     new = torch.empty if rows is None else torch.zeros
     dx = new((B, N), device=dev, dtype=torch.float32) if need_dx else None
-    dmod = new((B, n_mod), device=dev, dtype=torch.float32) if need_dmod else None
+    if not need_dmod:
+        dmod = None
+    elif dmod is None:
+        dmod = new((B, n_mod), device=dev, dtype=torch.float32)
+    assert dmod is None or (dmod.shape == (B, n_mod) and dmod.dtype == torch.float32)
     dmix = torch.zeros((B,), device=dev, dtype=torch.float64) if need_dmix else None
     dxp, dxs = _rows_view(dx) if need_dx else (None, 0)
     _hip.call("mx_tremolo_bwd", *_rows_view(dy), *_rows_view(x), _hip.ptr(mod_sig), n_mod, _hip.ptr(consts["mix"]),
@@ -464,52 +471,87 @@ def phaser_backward(dy: T, src: T, stash: T, params: Dict[str, T], lead: Optiona
     return (dx if need_dx else None), (dmod if need_dmod else None), grads
 
 
-def phaser_mod_expand(mod_lr: T, lead: Optional[T], n_samples: int, width: int, out: Optional[T] = None) -> T:
+def phaser_mod_expand(mod_lr: T, lead: Optional[T], n_samples: int, width: int, out: Optional[T] = None,
+                      rows: Optional[T] = None) -> T:
     """Launch mx_phaser_mod_expand: a low-rate LFO (B, n_mod), 1 <= n_mod <= n_samples, spanning the n_samples of the clip
     window, as the (B, ceil(width / 4)) row ``phaser_forward_stash`` takes as ``mod``: group g of row b reads the row
     resampled (as ``flanger_forward`` / ``tremolo_forward`` resample theirs) at clip sample
     clamp(4 g - lead[b], 0, n_samples - 1) -- the LFO is held at its first value through the lead-in; groups beyond
-    lead[b] + n_samples hold 0.5."""
+    lead[b] + n_samples hold 0.5.  rows: optional int32 list of the rows to process (mx_phaser_mod_expand_rows): the listed
+    rows get the same bits, the others of ``out`` are not touched (without ``out`` they are uninitialised); an empty list
+    launches nothing."""
     B, n_mod = mod_lr.shape
     assert mod_lr.dtype == torch.float32 and mod_lr.is_contiguous() and 1 <= n_mod <= n_samples <= width
     ng = (width + 3) // 4
     mod_g = out if out is not None else torch.empty((B, ng), device=mod_lr.device, dtype=torch.float32)
     assert mod_g.size(0) == B and mod_g.size(1) >= ng
     mp, ms = _rows_view(mod_g)
-    _hip.call("mx_phaser_mod_expand", _hip.ptr(mod_lr), n_mod, _hip.ptr(lead), B, n_samples, width, mp, ms, _hip.stream())
+    if rows is None:
+        _hip.call("mx_phaser_mod_expand", _hip.ptr(mod_lr), n_mod, _hip.ptr(lead), B, n_samples, width, mp, ms, _hip.stream())
+    elif rows.numel():
+        assert rows.dtype == torch.int32 and rows.numel() <= B
+        _hip.call("mx_phaser_mod_expand_rows", _hip.ptr(mod_lr), n_mod, _hip.ptr(lead), *_rows_arg(rows), B, n_samples, width,
+                  mp, ms, _hip.stream())
     return mod_g
 
 
-def phaser_dmod_gather(dmod_g: T, lead: Optional[T], n_samples: int, n_mod: int) -> T:
+def phaser_dmod_gather(dmod_g: T, lead: Optional[T], n_samples: int, n_mod: int, rows: Optional[T] = None,
+                       out: Optional[T] = None) -> T:
     """Launch mx_phaser_dmod_gather, the transpose of ``phaser_mod_expand``: dmod_g (B, >= ceil(n_samples / 4)) as
-    ``phaser_backward`` returns it -> (B, n_mod) fp32 (fp64 sums in a fixed order, rounded once; deterministic)."""
+    ``phaser_backward`` returns it -> (B, n_mod) fp32 (fp64 sums in a fixed order, rounded once; deterministic).  rows:
+    optional int32 list of the rows to process (mx_phaser_dmod_gather_rows): same bits on the listed rows, the others of
+    ``out`` (B, n_mod) dense -- e.g. a gradient shared with other effects -- are not touched (without ``out`` they are
+    uninitialised); an empty list launches nothing."""
     B = dmod_g.size(0)
     assert 1 <= n_mod <= n_samples
     dp, ds = _rows_view(dmod_g)
-    dmod_lr = torch.empty((B, n_mod), device=dmod_g.device, dtype=torch.float32)
-    _hip.call("mx_phaser_dmod_gather", dp, ds, dmod_g.size(1), _hip.ptr(lead), B, n_samples, n_mod, _hip.ptr(dmod_lr),
-              _hip.stream())
+    dmod_lr = out if out is not None else torch.empty((B, n_mod), device=dmod_g.device, dtype=torch.float32)
+    assert dmod_lr.shape == (B, n_mod) and dmod_lr.dtype == torch.float32
+    if rows is None:
+        _hip.call("mx_phaser_dmod_gather", dp, ds, dmod_g.size(1), _hip.ptr(lead), B, n_samples, n_mod, _hip.ptr(dmod_lr),
+                  _hip.stream())
+    elif rows.numel():
+        assert rows.dtype == torch.int32 and rows.numel() <= B
+        _hip.call("mx_phaser_dmod_gather_rows", dp, ds, dmod_g.size(1), _hip.ptr(lead), *_rows_arg(rows), B, n_samples, n_mod,
+                  _hip.ptr(dmod_lr), _hip.stream())
     return dmod_lr
 
 
 def phaser_forward_stash_lr(src: T, params: Dict[str, T], lead: Optional[T], sr: float, n_samples: int,
-                            mod_lr: T) -> Tuple[T, T, T]:
+                            mod_lr: T, rows: Optional[T] = None, out: Optional[T] = None,
+                            stash: Optional[T] = None) -> Tuple[T, T, T]:
     """``phaser_forward_stash`` driven by a low-rate LFO: mod_lr (B, n_mod) fp32, any 1 <= n_mod <= n_samples, spanning the
     n_samples OUTPUT samples (the lead-in holds its first value).  Two launches: ``phaser_mod_expand``, then the stash
-    forward on the expanded row.  Returns (y, stash, mod_g): mod_g (B, ceil(W / 4)) is the row the scan read."""
-    mod_g = phaser_mod_expand(mod_lr, lead, n_samples, src.size(1))
-    y, stash = phaser_forward_stash(src, params, lead, sr, n_samples, mod=mod_g)
+    forward on the expanded row.  Returns (y, stash, mod_g): mod_g (B, ceil(W / 4)) is the row the scan read.  rows:
+    optional int32 list of the rows to process, through both launches: the other rows of ``out`` (e.g. the wet_hat a batch
+    of mixed effects shares) are not touched, those of stash and mod_g are uninitialised; an empty list launches nothing."""
+    mod_g = phaser_mod_expand(mod_lr, lead, n_samples, src.size(1), rows=rows)
+    if rows is not None and rows.numel() == 0:
+        B = src.size(0)
+        y = out if out is not None else torch.empty((B, n_samples), device=src.device, dtype=torch.float32)
+        st = stash if stash is not None else torch.empty((B, phaser_stash_shape(src.size(1))[1]), device=src.device,
+                                                         dtype=torch.float32)
+        return y, st, mod_g
+    y, stash = phaser_forward_stash(src, params, lead, sr, n_samples, mod=mod_g, rows=rows, out=out, stash=stash)
     return y, stash, mod_g
 
 
 def phaser_backward_lr(dy: T, src: T, stash: T, params: Dict[str, T], lead: Optional[T], sr: float, n_samples: int,
-                       n_mod: int, need_dx: bool = True,
-                       params_wanted: Tuple[str, ...] = PHASER_PARAM_GRADS) -> Tuple[Optional[T], T, Dict[str, T]]:
+                       n_mod: int, need_dx: bool = True, params_wanted: Tuple[str, ...] = PHASER_PARAM_GRADS,
+                       rows: Optional[T] = None, dmod: Optional[T] = None) -> Tuple[Optional[T], T, Dict[str, T]]:
     """The adjoint of ``phaser_forward_stash_lr``: ``phaser_backward`` (dmod at group rate), then ``phaser_dmod_gather``.
-    Returns (dx (B, W) or None, dmod_lr (B, n_mod), the per-clip fp64 parameter gradients named in ``params_wanted``)."""
-    dx, dmod_g, grads = phaser_backward(dy, src, stash, params, lead, sr, n_samples, need_dx=need_dx, need_dmod=True,
-                                        params_wanted=params_wanted)
-    return dx, phaser_dmod_gather(dmod_g, lead, n_samples, n_mod), grads
+    Returns (dx (B, W) or None, dmod_lr (B, n_mod), the per-clip fp64 parameter gradients named in ``params_wanted``).
+    rows: the list the forward was given, through both launches; dmod: an optional (B, n_mod) dense output whose listed
+    rows are written and whose other rows are not touched (without it they are uninitialised, as are those of dx); an
+    empty list launches nothing."""
+    if rows is not None and rows.numel() == 0:
+        B, W = src.shape
+        dx = torch.empty((B, W), device=src.device, dtype=torch.float32) if need_dx else None
+        out = dmod if dmod is not None else torch.empty((B, n_mod), device=src.device, dtype=torch.float32)
+        return dx, out, {k: torch.zeros((B,), device=src.device, dtype=torch.float64) for k in params_wanted}
+    dx, dmod_g, grads = phaser_backward(dy, src, stash, params, lead, sr, n_samples, rows=rows, need_dx=need_dx,
+                                        need_dmod=True, params_wanted=params_wanted)
+    return dx, phaser_dmod_gather(dmod_g, lead, n_samples, n_mod, rows=rows, out=dmod), grads
 
 
 class _PhaserFunction(torch.autograd.Function):

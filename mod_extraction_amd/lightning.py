@@ -10,7 +10,7 @@ tensors (lightning.py:132-141) are dropped -- ``data_dict`` holds device tensors
 import logging
 import os
 from collections import defaultdict
-from typing import Dict, List, Optional
+from typing import Dict, List, Optional, Sequence, Tuple, Union
 
 import torch
 from torch import Tensor as T, nn
@@ -235,6 +235,34 @@ class _PhaserAudioLossFn(_EffectAudioLossFn):
             dy, dry, stash, consts, None, step.sr, n, mod.size(1), need_dx=False, params_wanted=())[1])
 
 
+class _MixedAudioLossFn(_EffectAudioLossFn):
+    """A batch that mixes effects: every family renders its rows into ONE wet_hat (B, N) through its row list
+    (``LFOExtractionThroughEffect._render_rows``) and its adjoint writes its rows of ONE zero-initialised (B, n_frames)
+    gradient (``_adjoint_rows``); dry rows are a copy of ``dry`` and keep a zero gradient.  The stashes (allocated for all B
+    rows) do not outlive the call."""
+
+    @staticmethod
+    def forward(ctx, mod_sig_hat, step, dry, wet, consts, terms):
+        mod = mod_sig_hat.detach().float().contiguous()
+        wet_hat, stashes = step._render_rows(dry, mod, consts, stash=True)
+        return _audio_loss_node(ctx, step, wet_hat, wet, terms,
+                                lambda dy: step._adjoint_rows(dy, dry, mod, consts, stashes))
+
+
+MIXED_KINDS = ("flanger", "chorus", "phaser", "tremolo", "dry")
+
+
+def mixed_row_lists(kinds: Sequence[str], bs: int) -> Dict[str, List[int]]:
+    """The rows of a batch of ``bs`` clips each launch family works on, by the batcher's rule (row i is of kind
+    ``kinds[i % len(kinds)]``, data_modules.SyntheticFxBatcher, datasets.py:79-83): "delay" = flanger and chorus (one
+    kernel, per-row geometry), "tremolo", "phaser", "dry".  A family without a row has an empty list."""
+    family = {"flanger": "delay", "chorus": "delay", "tremolo": "tremolo", "phaser": "phaser", "dry": "dry"}
+    out: Dict[str, List[int]] = {"delay": [], "tremolo": [], "phaser": [], "dry": []}
+    for i in range(bs):
+        out[family[kinds[i % len(kinds)]]].append(i)
+    return out
+
+
 class LFOExtractionThroughEffect(BaseLightingModule):
     """Trains the LFO extractor on dry / wet pairs WITHOUT an LFO label: the extractor's LFO drives a differentiable
     effect -- ``effect="flanger"`` (flanger / chorus, the default), ``effect="tremolo"`` or ``effect="phaser"`` -- on ``dry`` and an audio-domain
@@ -243,10 +271,19 @@ class LFOExtractionThroughEffect(BaseLightingModule):
 
     Same batch 4-tuple ``(dry, wet, mod_sig, fx_params)`` and metric naming as ``LFOExtraction``; ``training_step`` returns a
     loss with a grad graph, so ``trainer.Trainer`` drives it unchanged.
-    * ``max_min_delay_ms`` / ``max_lfo_delay_ms``: ONE flanger or chorus geometry per module, as in
-      ``fx.MonoFlangerChorusModule`` (batches that mix geometries are out of scope).  ``effect="tremolo"`` and
-      ``effect="phaser"`` ignore both and have no delay-line limit.
-    * ``effect``: ONE effect family per module; a batch that mixes effects is out of scope.
+    * ``max_min_delay_ms`` / ``max_lfo_delay_ms``: the flanger geometry (with a string ``effect``: ONE flanger or chorus
+      geometry per module, as in ``fx.MonoFlangerChorusModule``).  ``effect="tremolo"`` and ``effect="phaser"`` ignore both
+      and have no delay-line limit.  ``chorus_max_min_delay_ms`` / ``chorus_max_lfo_delay_ms`` (default
+      ``data_modules.CHORUS_FX``: 30 ms / 10 ms): the geometry of the "chorus" rows of a mixed batch.
+    * ``effect``: a string = ONE effect family per module, or a sequence of kinds out of "flanger", "chorus", "phaser",
+      "tremolo", "dry" = a batch that mixes them: row i is of kind ``effect[i % len(effect)]``, the batcher's own rule
+      (``data_modules.SyntheticFxBatcher``, datasets.py:79-83), so ``InterwovenDataModule`` batches and each DDP rank's
+      local batch line up with ``effect=("flanger", "chorus", "phaser")``.  Every family renders its rows into one shared
+      wet_hat and its adjoint writes its rows of one shared gradient through the kernels' row lists
+      (``_MixedAudioLossFn``); the per-row delay-line lengths and constants are formed with the batcher's own fp32
+      arithmetic.  "dry" rows are copied and get a zero gradient.  ``fx_params`` then carries what the kinds present need,
+      each as ONE (B,) tensor over all rows (the batcher's merged ``depth`` / ``feedback`` / ``mix``).  The caveats below
+      apply row by row.
     * ``fx_params`` carries the per-clip ``feedback``, ``min_delay_width``, ``width``, ``depth``, ``mix`` as (B,) tensors;
       the tremolo needs only ``mix``; the phaser needs ``depth``, ``centre_frequency_hz``, ``feedback``, ``mix`` (its
       ``rate_hz`` and ``lead`` are ignored: the LFO is the extractor's)
@@ -288,14 +325,24 @@ class LFOExtractionThroughEffect(BaseLightingModule):
                  loss_dict: Optional[Dict[str, float]] = None,
                  should_stretch: bool = False,
                  check_fx_params: bool = False,
-                 effect: str = "flanger") -> None:
+                 effect: Union[str, Sequence[str]] = "flanger",
+                 chorus_max_min_delay_ms: Optional[float] = None,
+                 chorus_max_lfo_delay_ms: Optional[float] = None) -> None:
         super().__init__({} if loss_dict is None else loss_dict)
         from . import fx
         from .effect_losses import GRAD_NAMES
         if should_stretch:
             raise NotImplementedError("should_stretch is not supported when training through the rendered effect")
-        if effect not in self._nodes:
-            raise ValueError(f"effect '{effect}': supported are {tuple(self._nodes)}")
+        self.kinds: Optional[Tuple[str, ...]] = None                # a sequence ``effect``: the kind of every slot
+        if not isinstance(effect, str):
+            self.kinds = effect = tuple(effect)
+            if not effect:
+                raise ValueError("effect: an empty sequence of kinds")
+            for k in effect:
+                if k not in MIXED_KINDS:
+                    raise ValueError(f"effect kind '{k}': supported are {MIXED_KINDS}")
+        elif effect not in self._nodes:
+            raise ValueError(f"effect '{effect}': supported are {tuple(self._nodes)} or a sequence out of {MIXED_KINDS}")
         self.effect = effect
         audio_loss_dict = dict(self.default_audio_loss_dict if audio_loss_dict is None else audio_loss_dict)
         for name, w in audio_loss_dict.items():
@@ -303,7 +350,8 @@ class LFOExtractionThroughEffect(BaseLightingModule):
                 raise NotImplementedError(f"audio loss '{name}' has no gradient kernel (supported: {GRAD_NAMES})")
         if not any(w > 0 for w in audio_loss_dict.values()):
             raise ValueError("audio_loss_dict needs at least one loss with a weight above 0")
-        if effect == "flanger":
+        has_flanger = effect == "flanger" or (self.kinds is not None and "flanger" in self.kinds)
+        if has_flanger:
             if max_min_delay_ms < 0 or max_lfo_delay_ms < 0:
                 raise ValueError("max_min_delay_ms and max_lfo_delay_ms must not be negative")
             self.max_min_delay_samples = fx.delay_samples(max_min_delay_ms, sr)
@@ -311,9 +359,26 @@ class LFOExtractionThroughEffect(BaseLightingModule):
         else:                                                       # no delay line: the arguments are ignored
             self.max_min_delay_samples = self.max_lfo_delay_samples = 0
         self.max_delay_samples = self.max_min_delay_samples + self.max_lfo_delay_samples
-        if effect == "flanger" and not 2 <= self.max_delay_samples <= fx.FLANGER_MAX_DELAY_SAMPLES:
+        if has_flanger and not 2 <= self.max_delay_samples <= fx.FLANGER_MAX_DELAY_SAMPLES:
             raise ValueError(f"delay line of {self.max_delay_samples} samples: the flanger kernels keep it in LDS and support "
                              f"2 .. {fx.FLANGER_MAX_DELAY_SAMPLES} samples (LFO row included)")
+        if self.kinds is not None:
+            from .data_modules import CHORUS_FX
+            if chorus_max_min_delay_ms is None:
+                chorus_max_min_delay_ms = CHORUS_FX["max_min_delay_ms"]
+            if chorus_max_lfo_delay_ms is None:
+                chorus_max_lfo_delay_ms = CHORUS_FX["max_lfo_delay_ms"]
+            self.chorus_max_min_delay_ms, self.chorus_max_lfo_delay_ms = chorus_max_min_delay_ms, chorus_max_lfo_delay_ms
+            self.chorus_max_min_delay_samples = self.chorus_max_lfo_delay_samples = 0
+            if "chorus" in self.kinds:
+                if chorus_max_min_delay_ms < 0 or chorus_max_lfo_delay_ms < 0:
+                    raise ValueError("chorus_max_min_delay_ms and chorus_max_lfo_delay_ms must not be negative")
+                self.chorus_max_min_delay_samples = fx.delay_samples(chorus_max_min_delay_ms, sr)
+                self.chorus_max_lfo_delay_samples = fx.delay_samples(chorus_max_lfo_delay_ms, sr)
+                m = self.chorus_max_min_delay_samples + self.chorus_max_lfo_delay_samples
+                if not 2 <= m <= fx.FLANGER_MAX_DELAY_SAMPLES:
+                    raise ValueError(f"chorus delay line of {m} samples: the flanger kernels keep it in LDS and support "
+                                     f"2 .. {fx.FLANGER_MAX_DELAY_SAMPLES} samples (LFO row included)")
         self.model = model
         self.sr, self.use_dry = sr, use_dry
         self.model_smooth_n_frames = model_smooth_n_frames
@@ -325,6 +390,7 @@ class LFOExtractionThroughEffect(BaseLightingModule):
         self.loss_dict = dict(audio_loss_dict, **{f"lfo_{k}": w for k, w in self.lfo_loss_dict.items()})
         self._extra_losses = {}
         self._md = None
+        self._mixed = None
 
     center_crop_mod_sig = staticmethod(LFOExtraction.center_crop_mod_sig)
 
@@ -344,8 +410,116 @@ class LFOExtractionThroughEffect(BaseLightingModule):
             self._md = torch.full((bs,), self.max_delay_samples, device=device, dtype=torch.int32)
         return self._md
 
+    def _mixed_rows(self, bs: int, device) -> Dict[str, object]:
+        """A mixed batch of ``bs`` rows on ``device`` (cached like ``_max_delay_rows``): the int32 row list of every launch
+        family, the int64 list of the dry rows, and the per-row delay-line geometry as the batcher forms it
+        (``SyntheticFxBatcher.__init__``: fp32 sample counts, chorus rows the chorus geometry, every other row the
+        flanger's; only the rows of the "delay" list are read)."""
+        m = self._mixed
+        if m is None or m["bs"] != bs or m["device"] != device:
+            lists = mixed_row_lists(self.kinds, bs)
+            kinds = [self.kinds[i % len(self.kinds)] for i in range(bs)]
+            mm = torch.tensor([self.chorus_max_min_delay_samples if k == "chorus" else self.max_min_delay_samples
+                               for k in kinds], dtype=torch.float32)
+            ml = torch.tensor([self.chorus_max_lfo_delay_samples if k == "chorus" else self.max_lfo_delay_samples
+                               for k in kinds], dtype=torch.float32)
+            m = {"bs": bs, "device": device, "lists": lists,
+                 "max_min_delay": mm.to(device), "max_lfo_delay": ml.to(device),
+                 "max_delay": (mm + ml).to(torch.int32).to(device),
+                 "max_delay_max": int(max([int(mm[i] + ml[i]) for i in lists["delay"]], default=0)),
+                 "dry_idx": torch.tensor(lists["dry"], dtype=torch.int64, device=device)}
+            for name in ("delay", "tremolo", "phaser"):
+                m[name] = torch.tensor(lists[name], dtype=torch.int32, device=device)
+            self._mixed = m
+        return m
+
+    def _mixed_constants(self, fx_params, bs: int, device) -> Dict[str, T]:
+        """ONE dict of (B,) fp32 constants for all families of a mixed batch, each formed as the data path forms it
+        (``SyntheticFxBatcher.render``: lfo_scale and min_delay are fp32 tensor products with the per-row sample counts,
+        one_minus_mix is 1 - mix in fp32), so a re-render from the label reproduces ``wet``.  Only what the kinds present
+        need is read from ``fx_params``."""
+        from . import fx
+        m = self._mixed_rows(bs, device)
+
+        def vec(name: str) -> T:
+            p = fx_params[name]
+            assert isinstance(p, T) and p.shape == (bs,), f"fx_params['{name}']: a ({bs},) tensor"
+            return p.to(device=device, dtype=torch.float32).contiguous()
+
+        lists, consts = m["lists"], {}
+        if lists["delay"] or lists["tremolo"] or lists["phaser"]:
+            consts["mix"] = vec("mix")
+            consts["one_minus_mix"] = (1.0 - consts["mix"]).contiguous()
+        if lists["delay"] or lists["phaser"]:
+            consts["feedback"], consts["depth"] = vec("feedback"), vec("depth")
+        if lists["delay"]:
+            consts["lfo_scale"] = (vec("width") * m["max_lfo_delay"]).contiguous()
+            consts["min_delay"] = (vec("min_delay_width") * m["max_min_delay"]).contiguous()
+        if lists["phaser"]:
+            consts["centre_frequency_hz"] = vec("centre_frequency_hz")
+        if self.check_fx_params:                                    # each family's ranges on its own rows
+            def on(name: str, idx: T) -> T:
+                return vec(name)[idx]
+            for fam, idx in ((f, torch.tensor(lists[f], dtype=torch.int64, device=device)) for f in lists if lists[f]):
+                if fam == "delay":
+                    fx._check_param(on("feedback", idx), idx.numel(), can_be_one=False)
+                    for name in ("min_delay_width", "width", "depth", "mix"):
+                        fx._check_param(on(name, idx), idx.numel())
+                elif fam == "tremolo":
+                    fx._check_param(on("mix", idx), idx.numel())
+                elif fam == "phaser":
+                    fx.derive_phaser_params(idx.numel(), device, on("depth", idx), on("centre_frequency_hz", idx),
+                                            on("feedback", idx), on("mix", idx), check=True)
+        return consts
+
+    def _render_rows(self, dry: T, mod: T, consts: Dict[str, T], stash: bool):
+        """wet_hat (B, N) of a mixed batch, every family through its row list into the one buffer: flanger + chorus rows
+        ``mx_flanger_fwd`` (``stash``: ``mx_flanger_fwd_stash``, the same bits), tremolo rows ``mx_tremolo_fwd``, phaser rows
+        the row-listed ``mx_phaser_mod_expand_rows`` + ``mx_phaser_fwd_stash`` with lead 0, dry rows a copy.  A family without
+        a row launches nothing.  Returns (wet_hat, the stashes ``_adjoint_rows`` needs -- empty unless ``stash``)."""
+        from . import fx
+        B, N = dry.shape
+        m = self._mixed_rows(B, dry.device)
+        wet_hat = torch.empty((B, N), device=dry.device, dtype=torch.float32)
+        stashes = {}
+        if m["dry_idx"].numel():
+            wet_hat.index_copy_(0, m["dry_idx"], dry.index_select(0, m["dry_idx"]))
+        if m["delay"].numel():
+            if stash:
+                stashes["delay"] = fx.flanger_forward_stash(dry, mod, consts, m["max_delay"], m["max_delay_max"],
+                                                            rows=m["delay"], out=wet_hat)[1]
+            else:
+                fx.flanger_forward(dry, mod, consts, m["max_delay"], m["max_delay_max"], rows=m["delay"], out=wet_hat)
+        if m["tremolo"].numel():
+            fx.tremolo_forward(dry, mod, consts, rows=m["tremolo"], out=wet_hat)
+        if m["phaser"].numel():
+            st = fx.phaser_forward_stash_lr(dry, consts, None, self.sr, N, mod, rows=m["phaser"], out=wet_hat)[1]
+            if stash:
+                stashes["phaser"] = st
+        return wet_hat, stashes
+
+    def _adjoint_rows(self, dy: T, dry: T, mod: T, consts: Dict[str, T], stashes: Dict[str, T]) -> T:
+        """d loss / d LFO (B, n_frames) of a mixed batch from d loss / d wet_hat (B, N): every family's adjoint, asked for
+        dmod alone, writes its rows of one zero-initialised buffer through the forward's row list (``mx_flanger_bwd_lr``;
+        ``mx_tremolo_bwd``; ``mx_phaser_bwd`` + ``mx_phaser_dmod_gather_rows``).  Dry rows keep the zeros."""
+        from . import fx
+        B, N = dry.shape
+        m = self._mixed_rows(B, dry.device)
+        dmod = torch.zeros((B, mod.size(1)), device=dry.device, dtype=torch.float32)
+        if m["delay"].numel():
+            fx.flanger_backward(dy, dry, mod, stashes["delay"], consts, m["max_delay"], m["max_delay_max"], rows=m["delay"],
+                                need_dx=False, params=(), dmod=dmod)
+        if m["tremolo"].numel():
+            fx.tremolo_backward(dy, dry, mod, consts, rows=m["tremolo"], need_dx=False, need_dmix=False, dmod=dmod)
+        if m["phaser"].numel():
+            fx.phaser_backward_lr(dy, dry, stashes["phaser"], consts, None, self.sr, N, mod.size(1), need_dx=False,
+                                  params_wanted=(), rows=m["phaser"], dmod=dmod)
+        return dmod
+
     def clip_constants(self, fx_params, bs: int, device) -> Dict[str, T]:
         from . import fx
+        if self.kinds is not None:
+            return self._mixed_constants(fx_params, bs, device)
         if self.effect == "tremolo":
             return fx.derive_tremolo_constants(bs, device, fx_params["mix"], check=self.check_fx_params)
         if self.effect == "phaser":
@@ -363,13 +537,16 @@ class LFOExtractionThroughEffect(BaseLightingModule):
     def render(self, dry: T, mod_sig: T, fx_params) -> T:
         """wet_hat (B, 1, N) = the effect on ``dry`` (B, 1, N) driven by ``mod_sig`` (B, n_mod) at its own rate, with the
         per-clip constants of ``fx_params``; no graph (``mx_flanger_fwd`` / ``mx_tremolo_fwd``, the data path's launches; the
-        phaser: ``mx_phaser_mod_expand`` + ``mx_phaser_fwd_stash`` with lead 0, see the class docstring)."""
+        phaser: ``mx_phaser_mod_expand`` + ``mx_phaser_fwd_stash`` with lead 0, see the class docstring; a sequence
+        ``effect``: every family on its rows, ``_render_rows``)."""
         from . import fx
         rows = self._rows(dry)
         with torch.no_grad():
             consts = self.clip_constants(fx_params, rows.size(0), rows.device)
             mod = mod_sig.detach().float().contiguous()
-            if self.effect == "tremolo":
+            if self.kinds is not None:
+                y = self._render_rows(rows, mod, consts, stash=False)[0]
+            elif self.effect == "tremolo":
                 y = fx.tremolo_forward(rows, mod, consts)
             elif self.effect == "phaser":
                 y = fx.phaser_forward_stash_lr(rows, consts, None, self.sr, rows.size(1), mod)[0]
@@ -388,7 +565,8 @@ class LFOExtractionThroughEffect(BaseLightingModule):
         if torch.is_grad_enabled() and mod_sig_hat.requires_grad:
             with torch.no_grad():
                 consts = self.clip_constants(fx_params, dry_r.size(0), dry_r.device)
-            loss, wet_hat = self._nodes[self.effect].apply(mod_sig_hat, self, dry_r, wet_r, consts, terms)
+            node = _MixedAudioLossFn if self.kinds is not None else self._nodes[self.effect]
+            loss, wet_hat = node.apply(mod_sig_hat, self, dry_r, wet_r, consts, terms)
             wet_hat = wet_hat.unsqueeze(1)
         else:
             wet_hat, loss = self.render(dry, mod_sig_hat, fx_params), None
