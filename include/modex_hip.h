@@ -325,7 +325,9 @@ int mx_conv_block_dgrad_f16(const void *dz_hi, const void *dz_lo, const void *w_
 /* First block (2 input channels) on the same matrix-core kernel: (kernel row, input channel) pairs become the 16
  * "channels" of the operand (k = kh*2 + ci, 10 used), so that one 16-deep MFMA k-step covers a tap column and the
  * K loop is a single stage.  Same reference semantics (models.py:183-195, first block: LayerNorm -> Conv2d(2,64,
- * (5,13)) -> +bias -> MaxPool(2,1)).  w_hi, w_lo: 13*2*64*8 halfs each; xk_hi, xk_lo: (B, H, 352, 16) halfs. */
+ * (5,13)) -> +bias -> MaxPool(2,1)).  w_hi, w_lo: 13*2*64*8 halfs each; xk_hi, xk_lo: (B, H, 352, 16) halfs.
+ * mx_conv_block1_fwd_f16 writes all 352 columns of out and out_amax: columns >= Wv of out are zeros, those of out_amax
+ * are unspecified (0 or 1). */
 int mx_conv_pack_weights_kvec_f16(const float *W, void *w_hi, void *w_lo, void *stream);
 int mx_conv_prep_fwd_kvec_f16(const float *x, const float *stats, int64_t B, int64_t H, int64_t Wv, void *xk_hi,
                               void *xk_lo, void *stream);
