@@ -469,6 +469,33 @@ int mx_stretch_corners_bwd(const float *x, const float *dout, int64_t rows, int6
 int mx_check_mod_sig(const float *x, int64_t rows, int64_t n, int32_t min_top, int32_t max_top,
                      int32_t min_bot, int32_t max_bot, int32_t min_gap, int32_t *valid, void *stream);
 
+/* ---- K14: evaluation LFO variants for a whole batch -- mod_extraction/modulations.py:104-160 and :191-210 as
+ * datasets.py:365-398 applies them per item (fx_config.mod_sig.quasiperiodic / .combined of configs/eval_lfo_quasi.yml and
+ * eval_lfo_combined.yml).  The reference draws a data-dependent number of random values per LFO on the host; here the draws
+ * arrive as a fixed-width table per row (S entries) that the kernel consumes in corner order.  One launch, one workgroup per
+ * row, no host round trip, no atomics, no workspace; bit-identical from run to run.  Limits (MX_ERR_UNSUPPORTED): S in
+ * 1 .. 64, n <= 16 777 216 (rows stay in global memory -- LDS holds the corner list and the section table only -- so the bound
+ * is the fp32 index arithmetic of the align_corners resampling, exact below 2^24), B < 2^31. */
+/* make_quasi_periodic + _time_stretch_section (modulations.py:104-160) on every row of base (B, n), n >= 3.  The corner map
+ * with the larger sum is taken (top if its sum EXCEEDS the bottom's, modulations.py:129-132), its entries equal to 1 are the
+ * corners c_0 < .. < c_(m-1).  Section s = base[p_s .. c_s] (p_0 = 0, p_s = c_(s-1)), size = c_s - p_s + 1,
+ * x = (int)((double)amount[b][s] * size + 0.5), new = shrink[b][s] ? max(2, size - x) : size + x; the section contributes the
+ * first new - 1 points of its align_corners resampling to `new` points (util.py:15-29).  The tail base[c_(m-1) .. n-1] is
+ * stretched when pieces and tail together fall short of n, and the concatenation is cut to n.  amount >= 0 is expected
+ * (amount * size is clamped to +-2^30).  Rows with fewer than 2 corners (modulations.py:136-137) or with more than S corners
+ * are copied unchanged.  n_corners (B,) int32 or NULL receives m, the real count, in every case.  out (B, n) must not alias
+ * base. */
+int mx_lfo_quasi_periodic(const float *base, const int32_t *shrink, const float *amount, int64_t B, int64_t n, int64_t S,
+                          float *out, int32_t *n_corners, void *stream);
+/* make_combined_mod_sig (modulations.py:191-210) for B rows: freq, phase (B,) float32; shape_tab (B, S + 1) int32 shape ids as
+ * in mx_lfo_synth.  Column 0 is the shape of the base LFO, synthesised as mx_lfo_synth does with n_src = n_out = n at rate
+ * sr, exponent 1, start 0.  With c_0 < .. < c_(m-1) the bottom corners of the base, points c_s .. c_(s+1) become
+ * make_mod_signal(L, L, freq=1, phase=0, shape_tab[b][s + 1]) with L = c_(s+1) - c_s + 1; a shared corner belongs to the
+ * later section (the later assignment wins in the reference's loop), the last corner to the last section.  Pairs beyond S
+ * keep the base; so does a row with fewer than 2 bottom corners.  n_corners (B,) int32 or NULL receives m.  out (B, n). */
+int mx_lfo_combined(const float *freq, const float *phase, const int32_t *shape_tab, int64_t B, int64_t n, int64_t S,
+                    float sr, float *out, int32_t *n_corners, void *stream);
+
 /* ---- K10: LSTM-64 effect model -- mod_extraction/models.py:311-339 (nn.LSTM(2,64) -> Linear(64,1) ->
  * + x -> tanh, input order (lfo, audio)) and its truncated BPTT, lightning.py:355-384.
  * x, lfo, y: B rows of T samples with row strides (chunks are views into (B,1,n) tensors).

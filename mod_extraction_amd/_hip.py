@@ -87,6 +87,8 @@ SIGNATURES = {
     "mx_stretch_corners": [_P, _I64, _I64, _I64, _P, _P],
     "mx_stretch_corners_bwd": [_P, _P, _I64, _I64, _I64, _P, _P],
     "mx_check_mod_sig": [_P, _I64, _I64, _I32, _I32, _I32, _I32, _I32, _P, _P],
+    "mx_lfo_quasi_periodic": [_P, _P, _P, _I64, _I64, _I64, _P, _P, _P],
+    "mx_lfo_combined": [_P, _P, _P, _I64, _I64, _I64, _F32, _P, _P, _P],
     "mx_lstm_fwd": [_P, _I64, _P, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P, _I64, _I64, _P],
     "mx_lstm_bwd_l1": [_P, _I64, _P, _I64, _P, _I64, _P, _I64, _P, _P, _P, _P, _P, _F32, _P, _I64, _I64, _P],
     "mx_lstm_bwd": [_P, _I64, _P, _I64, _P, _I64, _P, _I64, _P, _P, _P, _P, _P, _P, _I64, _I64, _P],

@@ -6,20 +6,7 @@
 // the same fp32 operations in the same sequence: the results are bit-identical to the reference
 // (tests compare with ==).  A 256-row batch is ~0.1 MFLOP; these kernels are bookkeeping, not a
 // roofline target.
-#include "common.h"
-
-// top/bottom corner value at interior index i (modulations.py:224-231):
-//   -floor( (d_l > 0 ? d_l : 0) * (d_r + 1e-16) )  and the same with d_l < 0
-__device__ __forceinline__ void corner_values(const float *m, int i, float &top, float &bot)
-{
-    const float d_l = __fsub_rn(m[i], m[i - 1]);
-    const float d_r = __fsub_rn(m[i + 1], m[i]);
-    const float nudged = __fadd_rn(d_r, 1e-16f);
-    const float rising = d_l > 0.0f ? d_l : 0.0f;
-    const float falling = d_l < 0.0f ? d_l : 0.0f;
-    top = (float)(-(long long)floorf(__fmul_rn(rising, nudged)));
-    bot = (float)(-(long long)floorf(__fmul_rn(falling, nudged)));
-}
+#include "lfo_common.h"
 
 // modulations.py:359-363 (x.unfold(-1, k, 1).mean(-1)): left-to-right fp32 sum, then / k.
 __global__ void smoothen_kernel(const float *__restrict__ x, int R, int n, int k, float *__restrict__ out)

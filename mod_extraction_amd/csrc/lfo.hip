@@ -9,54 +9,7 @@
 // (datasets.py:442-449); `n_out != n_src` applies the align_corners=True resampling of
 // util.py:15-29 on the fly (two closed-form evaluations per output point).
 // HBM traffic: 4 B written per output point -- trivially HBM-bound, 3.5 KB per 882-point LFO.
-#include "common.h"
-
-#define LFO_COS 0
-#define LFO_RECT_COS 1
-#define LFO_INV_RECT_COS 2
-#define LFO_TRI 3
-#define LFO_SAW 4
-#define LFO_RSAW 5
-#define LFO_SQR 6
-
-__device__ __forceinline__ float lfo_value(int k, int start, float step, float ph, int shape, float ex)
-{
-    const float TWO_PI_F = 6.283185307179586f;
-    const float PI_F = 3.141592653589793f;
-    const float HALF_PI_F = 1.5707963267948966f;
-    double run = (double)((long long)k + 1 + (long long)start) * (double)step;
-    float arg = __fadd_rn(__double2float_rn(run), ph);
-    float v;
-    if (shape == LFO_COS) {
-        v = __fmul_rn(__fadd_rn(cosf(__fadd_rn(arg, PI_F)), 1.0f), 0.5f);
-    } else if (shape == LFO_RECT_COS) {
-        v = fabsf(cosf(__fadd_rn(arg, HALF_PI_F)));
-    } else if (shape == LFO_INV_RECT_COS) {
-        v = __fadd_rn(-fabsf(cosf(arg)), 1.0f);
-    } else if (shape == LFO_SQR) {
-        float c = cosf(__fadd_rn(arg, PI_F));
-        float s = c > 0.0f ? 1.0f : (c < 0.0f ? -1.0f : 0.0f);
-        v = __fmul_rn(__fadd_rn(s, 1.0f), 0.5f);
-    } else {
-        float saw = __fdiv_rn(torch_remainderf(arg, TWO_PI_F), TWO_PI_F);
-        if (shape == LFO_SAW) {
-            v = saw;
-        } else if (shape == LFO_RSAW) {
-            v = __fsub_rn(1.0f, saw);
-        } else {  // LFO_TRI
-            float tri = __fmul_rn(2.0f, saw);
-            v = tri > 1.0f ? __fsub_rn(2.0f, tri) : tri;
-        }
-    }
-    if (ex != 1.0f) {
-        // torch.pow(tensor, scalar) fast paths (aten PowKernel.cpp), then the generic powf
-        if (ex == 2.0f) v = __fmul_rn(v, v);
-        else if (ex == 3.0f) v = __fmul_rn(__fmul_rn(v, v), v);
-        else if (ex == 0.5f) v = sqrtf(v);
-        else v = powf(v, ex);
-    }
-    return v;
-}
+#include "lfo_common.h"
 
 __global__ __launch_bounds__(256) void lfo_synth_kernel(const float *__restrict__ freq,
                                                         const float *__restrict__ phase,
@@ -69,16 +22,11 @@ __global__ __launch_bounds__(256) void lfo_synth_kernel(const float *__restrict_
     const int b = blockIdx.y;
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n_out) return;
-    const float TWO_PI_F = 6.283185307179586f;
     float f = freq[b], ph = phase[b];
     const int sh = shape ? shape[b] : LFO_COS;
     const float e = ex ? ex[b] : 1.0f;
     const int st = start ? start[b] : 0;
-    if (sh == LFO_RECT_COS || sh == LFO_INV_RECT_COS) {  // modulations.py:26-29 (exact halving)
-        f = __fmul_rn(f, 0.5f);
-        ph = __fmul_rn(ph, 0.5f);
-    }
-    const float step = __fdiv_rn(__fmul_rn(TWO_PI_F, f), sr);  // modulations.py:31
+    const float step = lfo_step(sh, f, ph, sr);
     float v;
     if (n_out == n_src) {
         v = lfo_value(i, st, step, ph, sh, e);

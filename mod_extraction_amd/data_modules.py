@@ -26,7 +26,8 @@ import torch
 from torch import Tensor as T
 
 from . import _hip, fx, util
-from .modulations import SHAPE_IDS, make_mod_signals
+from .modulations import (SHAPE_IDS, draw_combined_table, draw_quasi_tables, make_combined_mod_sigs, make_mod_signals,
+                          make_quasi_periodic_batch)
 
 LFO_SHAPES = ["cos", "rect_cos", "inv_rect_cos", "tri", "saw", "rsaw"]
 
@@ -39,6 +40,12 @@ PHASER_FX = {"rate_hz": (0.5, 3.0), "depth": (0.2, 1.0), "centre_frequency_hz": 
              "feedback": (0.0, 0.7), "mix": (0.2, 1.0)}        # configs/train_lfo_phaser.yml:33-48
 TREMOLO_FX = {"mix": (0.0, 1.0)}
 MOD_SIG = {"rate_hz": (0.5, 3.0), "phase": (0.0, 2 * math.pi), "shapes": LFO_SHAPES, "exp": 1.0}
+# the evaluation variants of datasets.py:365-398 (configs/eval_lfo_combined.yml, eval_lfo_quasi.yml); the ranges default to
+# make_quasi_periodic's own (modulations.py:121-126)
+MOD_SIG_VARIANTS = {"combined": False, "quasiperiodic": False, "l_min": 0.2, "l_max": 0.2, "r_min": 0.2, "r_max": 0.2,
+                    "lr_split": 0.5}
+_TABLE_KEYS = ("shape_table", "quasi_shrink", "quasi_amount")     # travel with the parameters, stay out of fx_params
+MAX_VARIANT_SECTIONS = 64                                         # the S limit of csrc/lfo_variants.hip
 
 
 def _rng(v: Any) -> Tuple[float, float]:
@@ -75,6 +82,22 @@ class SyntheticFxBatcher:
     reference's parameter stream value for value (tests/test_param_stream.py, golden from the real ``util``).  In "batch"
     order the tremolo mix is one more vectorised draw after the phaser's, made only when the batch has a tremolo slot, so
     the streams of batches without one do not move.
+
+    ``mod_sig["combined"]`` / ``mod_sig["quasiperiodic"]`` (with ``l_min / l_max / r_min / r_max / lr_split``) switch on the
+    evaluation variants of datasets.py:365-398: the label of every row that is not a phaser row (the reference's
+    ``PedalboardPhaserDataset`` applies neither) becomes ``make_combined_mod_sig`` of its rate / phase / shape -- which, like
+    the reference's function, ignores ``exp`` -- and / or is time-stretched section by section as ``make_quasi_periodic``
+    does; the effects are then rendered from that label.  Both run as one launch per batch (``mx_lfo_combined``,
+    ``mx_lfo_quasi_periodic``) on fixed-width tables of host draws, ``self.S`` entries per row:
+    ``S = min(64, 2 * (int(rate_max * n_samples / sr) + 2))``.  The tables are the LAST draws of a batch (combined, then
+    quasi, each only when its flag is on), so the streams of batches without a flag do not move.  As in the reference, the
+    base shape of a combined label is a draw of its own (column 0 of the table, modulations.py:196): ``fx_params["shape"]``
+    is drawn as always and does not describe such a label.  The tables are not part of ``fx_params``.  ``last_n_corners``
+    is the (B,) int32 device tensor of corner counts of the batch handed out last (of the quasi step when both flags are
+    on); a row whose count exceeds ``S`` kept its un-stretched label.
+    ``rng_order="reference"`` with either flag raises ``ValueError``: the reference's stream consumes a data-dependent
+    number of draws per item (two per corner, one per corner pair), so reproducing it would take a device round trip per
+    item -- a deliberate scope cut.  Unknown ``mod_sig`` keys raise ``ValueError``.
     """
 
     def __init__(self, batch_size: int, n_samples: int, sr: float, kinds: Sequence[str], device: torch.device,
@@ -92,10 +115,21 @@ class SyntheticFxBatcher:
         self.ch = _fx_from_config(chorus_fx, CHORUS_FX)
         self.ph = _fx_from_config(phaser_fx, PHASER_FX)
         self.tr = _fx_from_config(tremolo_fx, TREMOLO_FX)
-        self.ms = dict(MOD_SIG)
+        self.ms = dict(MOD_SIG, **MOD_SIG_VARIANTS)
         if mod_sig:
+            unknown = sorted(set(mod_sig) - set(self.ms))
+            if unknown:
+                raise ValueError(f"unknown mod_sig keys {unknown}: expected a subset of {sorted(self.ms)}")
             for k, v in mod_sig.items():
                 self.ms[k] = _rng(v) if isinstance(v, dict) else v
+        self.combined, self.quasiperiodic = bool(self.ms["combined"]), bool(self.ms["quasiperiodic"])
+        if rng_order == "reference" and (self.combined or self.quasiperiodic):
+            raise ValueError('mod_sig "combined" / "quasiperiodic" need rng_order="batch": the reference draws a '
+                             "data-dependent number of values per item for them")
+        self.quasi_args = tuple(float(self.ms[k]) for k in ("l_min", "l_max", "r_min", "r_max", "lr_split"))
+        # table width of the variants: twice the corners of one kind the fastest LFO can have in a clip, and a margin
+        self.S = min(MAX_VARIANT_SECTIONS, 2 * (int(self.ms["rate_hz"][1] * n_samples / float(sr)) + 2))
+        self.last_n_corners: Optional[T] = None
         self.n_lfo = n_samples // 100                               # datasets.py:382
         self.lfo_sr = self.sr // 100
         # "dry": no effect -- the wet slot carries the untouched chunk and the LFO is a label only (datasets.py:365-398 as
@@ -245,6 +279,10 @@ class SyntheticFxBatcher:
             p["proc_extra"] = torch.where(is_ph, rate_n, torch.zeros_like(rate_n))   # the reference renders n + sr/rate
         if self.has_tr:                                                           # datasets.py:492-495; the last draw of a batch
             p["mix"] = torch.where(self.kind_id == 4, self._uniform(*self.tr["mix"]), p["mix"])
+        if self.combined:                                                         # modulations.py:196,207: after every other draw
+            p["shape_table"] = draw_combined_table(B, self.S, list(self.ms["shapes"]))
+        if self.quasiperiodic:                                                    # modulations.py:111-115
+            p["quasi_shrink"], p["quasi_amount"] = draw_quasi_tables(B, self.S, *self.quasi_args)
         p.update(rate_hz=rate, phase=phase, shape=shapes, exp=torch.full((B,), float(self.ms["exp"])),
                  centre_frequency_hz=centre, lead=lead)
         return p
@@ -289,7 +327,12 @@ class SyntheticFxBatcher:
                           int(self.rows_ph.numel()), _hip.ptr(d["lead"].to(torch.int32).contiguous()), N, N + self.max_lead,
                           self._noise_seed, self._noise_counter, -self.peak, self.peak, st)
         # LFO labels at n_samples // 100 points
-        mod = make_mod_signals(self.n_lfo, self.lfo_sr, d["rate_hz"], d["phase"], shape_id, d["exp"])
+        if self.combined:                            # datasets.py:375-380: make_combined_mod_sig takes no exp
+            mod, self.last_n_corners = make_combined_mod_sigs(self.n_lfo, self.lfo_sr, d["rate_hz"], d["phase"], d["shape_table"])
+        else:
+            mod = make_mod_signals(self.n_lfo, self.lfo_sr, d["rate_hz"], d["phase"], shape_id, d["exp"])
+        if self.quasiperiodic:                       # datasets.py:384-390
+            mod, self.last_n_corners = make_quasi_periodic_batch(mod, d["quasi_shrink"], d["quasi_amount"])
         if self.has_ph:
             half_pi = torch.full((B,), math.pi / 2, device=dev)
             mod_ph = make_mod_signals(N, self.sr, d["rate_hz"], half_pi, None, None, d["lead"], n_out=self.n_lfo)
@@ -309,7 +352,7 @@ class SyntheticFxBatcher:
             # datasets.py:497 on the 882-point label: the kernel resamples it as util.py:15-29 would (the reference asserts there)
             consts = {"mix": d["mix"], "one_minus_mix": (1.0 - d["mix"]).contiguous()}
             fx.tremolo_forward(dry, mod, consts, rows=self.rows_tr, out=wet)
-        fx_params = dict(d)
+        fx_params = {k: v for k, v in d.items() if k not in _TABLE_KEYS}
         fx_params["shape"] = p["shape"]
         return self.audio[:, 0:1, :], self.audio[:, 1:2, :], mod, fx_params
 
@@ -342,7 +385,7 @@ class SyntheticFxBatcher:
             extra = self.ahead_fn(batch) if self.ahead_fn is not None else None
             ev = torch.cuda.Event()
             ev.record(self._side)
-        self._pending = (batch, extra, ev)
+        self._pending = (batch, extra, ev, self.last_n_corners)
 
     @staticmethod
     def _tensors(obj):
@@ -363,14 +406,15 @@ class SyntheticFxBatcher:
                 return batch
         if self._pending is None:
             self._launch_ahead()
-        batch, extra, ev = self._pending
+        batch, extra, ev, n_corners = self._pending
         self.last_ahead = extra
         main = torch.cuda.current_stream(self.device)
         main.wait_event(ev)
-        for t in (batch[2], *self._tensors(batch[3]), *self._tensors(extra)):
+        for t in (batch[2], *self._tensors(batch[3]), *self._tensors(extra), *self._tensors(n_corners)):
             if t.is_cuda:
                 t.record_stream(main)           # allocated on the side stream, consumed on the main stream
         self._launch_ahead()                    # overlaps with the train step the caller is about to enqueue
+        self.last_n_corners = n_corners         # of the batch handed out, not of the one just launched
         return batch
 
 

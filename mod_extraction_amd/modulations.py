@@ -291,3 +291,62 @@ def make_concave_convex_mod_sig(n_samples: int, sr: float, freq: float, phase: f
         exp[prev:c] = v
         prev = c
     return mod_sig ** exp
+
+
+# ---- the same variants for a whole batch (csrc/lfo_variants.hip) --------------------------------
+# The per-item functions above draw a data-dependent number of host random values per LFO and pull the corner indices to
+# the host; the batch forms take the draws as FIXED-WIDTH tables (S entries per row) that the kernel consumes in corner
+# order: one launch per batch, nothing returns to the host.  With the tables filled in the per-item order they compute the
+# per-item functions' outputs bit for bit (tests/test_gpu_lfo_variants.py).
+def draw_quasi_tables(B: int, S: int, l_min: float = 0.2, l_max: float = 0.2, r_min: float = 0.2, r_max: float = 0.2,
+                      lr_split: float = 0.5) -> (T, T):
+    """Host draws of ``_time_stretch_section`` for B rows of up to S sections: two ``torch.rand(B, S)`` (split, amount).
+    Returns ``shrink`` (B, S) int32 (1 = the section shrinks) and ``amount`` (B, S) float32, in [l_min, l_max] where
+    ``shrink`` is set and in [r_min, r_max] elsewhere (``util.sample_uniform``'s own fp32 expression)."""
+    u_split, u_amt = torch.rand(B, S), torch.rand(B, S)
+    shrink = u_split.double() < lr_split
+    amount = torch.where(shrink, u_amt * (l_max - l_min) + l_min, u_amt * (r_max - r_min) + r_min)
+    return shrink.to(torch.int32), amount.to(torch.float32)
+
+
+def draw_combined_table(B: int, S: int, shapes: Union[int, Sequence[str]]) -> T:
+    """Host draws of ``make_combined_mod_sig`` for B rows of up to S corner pairs: ``torch.randint(0, n_shapes, (B, S + 1))``
+    (column 0: the base shape), mapped to ``SHAPE_IDS`` when ``shapes`` is the list of names the indices choose from
+    (an int ``n_shapes`` chooses among the first ``n_shapes`` ids).  Returns (B, S + 1) int32."""
+    n_shapes = shapes if isinstance(shapes, int) else len(shapes)
+    idx = torch.randint(0, n_shapes, (B, S + 1))
+    if not isinstance(shapes, int):
+        idx = torch.tensor([SHAPE_IDS[s] for s in shapes], dtype=torch.int64)[idx]
+    return idx.to(torch.int32)
+
+
+def make_quasi_periodic_batch(mod_sig: T, shrink: T, amount: T, out: Optional[T] = None) -> (T, T):
+    """``make_quasi_periodic`` on every row of ``mod_sig`` (B, n) in one ``mx_lfo_quasi_periodic`` launch: section s of row b
+    shrinks (``shrink[b, s]`` != 0) or grows by ``int(amount[b, s] * size + 0.5)`` points.  Rows with fewer than 2 or more
+    than S = ``shrink.size(1)`` corners come back unchanged.  Returns ``(out, n_corners)``, both on the device;
+    ``n_corners`` (B,) int32 is the real corner count of every row."""
+    m = _rows2d(mod_sig)
+    assert shrink.ndim == 2 and shrink.shape == amount.shape and shrink.size(0) == m.size(0)
+    sh = shrink.to(torch.int32).contiguous()
+    am = amount.to(torch.float32).contiguous()
+    if out is None:
+        out = torch.empty_like(m)
+    assert out.shape == m.shape and out.dtype == torch.float32 and out.data_ptr() != m.data_ptr()
+    n_corners = torch.empty(m.size(0), device=m.device, dtype=torch.int32)
+    _hip.call("mx_lfo_quasi_periodic", _hip.ptr(m), _hip.ptr(sh), _hip.ptr(am), m.size(0), m.size(1), sh.size(1),
+              _hip.ptr(out), _hip.ptr(n_corners), _hip.stream())
+    return out, n_corners
+
+
+def make_combined_mod_sigs(n_samples: int, sr: float, freq: T, phase: T, shape_table: T) -> (T, T):
+    """``make_combined_mod_sig`` for a batch in one ``mx_lfo_combined`` launch: freq / phase (B,) fp32 on the device,
+    ``shape_table`` (B, S + 1) int32 shape ids -- column 0 the base shape, column s + 1 the shape between bottom corners s
+    and s + 1 (pairs beyond S keep the base).  Returns ``(out (B, n_samples), n_corners (B,) int32)``."""
+    B = freq.numel()
+    assert shape_table.ndim == 2 and shape_table.size(0) == B and shape_table.size(1) >= 2
+    tab = shape_table.to(torch.int32).contiguous()
+    out = torch.empty((B, n_samples), device=freq.device, dtype=torch.float32)
+    n_corners = torch.empty(B, device=freq.device, dtype=torch.int32)
+    _hip.call("mx_lfo_combined", _hip.ptr(freq), _hip.ptr(phase), _hip.ptr(tab), B, n_samples, tab.size(1) - 1, float(sr),
+              _hip.ptr(out), _hip.ptr(n_corners), _hip.stream())
+    return out, n_corners
