@@ -722,6 +722,30 @@ int mx_reduce_rows_adamw_step(const float *part, int64_t R, float *param, float 
                               int64_t n, int64_t step, float lr, float beta1, float beta2, float eps, float weight_decay,
                               float grad_scale, void *stream);
 
+/* ---- K12 with gradient clipping (csrc/optim_clip.hip) -- the trainer keys gradient_clip_val / gradient_clip_algorithm of
+ * the reference's configs/trained/*.yml, i.e. torch.nn.utils.clip_grad_norm_ (2-norm) and clip_grad_value_ on the one flat
+ * gradient; the clip coefficient is formed and consumed on the device.
+ *
+ * mx_grad_sumsq: stat[0] = sum of grad[i]^2, i in [0, n), in fp64 (squares exact).  Two launches: workgroup w of G sums the
+ * 4096-element chunks w, w + G, ... into part[w] (fixed order inside the workgroup), then one workgroup adds part[0..G) in index
+ * order.  No atomics: the same data gives the same bits.  part: at least G doubles, stat: at least 2 doubles (stat[1] is not
+ * written here); grad is only read.
+ *   G = mx_sumsq_partials(n) = min(ceil(n / 4096), 1024)      (restated as optim.sumsq_partials in the Python package)
+ * NULL pointers or n <= 0: MX_ERR_ARG. */
+int mx_grad_sumsq(const float *grad, int64_t n, double *part, double *stat, void *stream);
+
+/* mx_adamw_step with the clip applied to the gradient as it is read (grad itself stays un-clipped); all else as mx_adamw_step.
+ *   clip_mode 1 (norm):  norm = sqrt(stat[0]) * (double)grad_scale;  coef = min(1.0, (double)clip_val / (norm + 1e-6));
+ *                        s = (float)((double)grad_scale * coef);  gi = grad[i] * s.  stat[0] from mx_grad_sumsq on the same
+ *                        stream.  coef == 1 gives s == grad_scale and the bits of mx_adamw_step.
+ *   clip_mode 2 (value): t = grad[i] * grad_scale;  gi = t > c ? c : (t < -c ? -c : t), c = clip_val (a NaN stays a NaN, as
+ *                        under torch.clamp); stat[0] is not read and s = grad_scale.
+ * stat[1] = (double)s is written by one thread.  NULL pointers, step <= 0, n <= 0, a mode outside {1, 2} or a clip_val that is
+ * not finite and positive: MX_ERR_ARG. */
+int mx_adamw_step_clip(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, int64_t n, int64_t step, float lr,
+                       float beta1, float beta2, float eps, float weight_decay, float grad_scale, int32_t clip_mode,
+                       float clip_val, double *stat, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

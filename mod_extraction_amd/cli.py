@@ -8,7 +8,8 @@ Supported schema (what the shipped configs use):
   * a value may be a path to another YAML (``model: ../configs/models/spectral_2dcnn.yml``); paths are
     tried relative to the current directory (the reference runs from ``scripts/``) and to the config file
   * the "link if possible" rules of configs/cli_config.yml:21-45 (n_samples / sr from data to the models)
-  * ``seed_everything``, ``trainer.{max_epochs, num_sanity_val_steps, limit_*_batches}``, ``custom.*``,
+  * ``seed_everything``, ``trainer.{max_epochs, num_sanity_val_steps, limit_*_batches, gradient_clip_val,
+    gradient_clip_algorithm, accumulate_grad_batches}`` (a YAML ``null`` is the default), ``custom.*``,
     ``ckpt_path`` (Lightning ``.ckpt`` or bare ``.pt`` state dict, prefixes stripped like
     scripts/extract_model_weights.py:38-47)
 GPU-only: there is no CPU fallback, so the reference's CPU overrides (cli.py:128-143) do not apply.
@@ -211,7 +212,8 @@ class CustomLightningCLI:
             device = torch.device("cuda", self.env["local_rank"])
         self.device = device
         self.custom = self.config.get("custom", {}) or {}
-        keys = ("max_epochs", "num_sanity_val_steps", "limit_train_batches", "limit_val_batches")
+        keys = ("max_epochs", "num_sanity_val_steps", "limit_train_batches", "limit_val_batches", "gradient_clip_val",
+                "gradient_clip_algorithm", "accumulate_grad_batches")
         tkw = dict(trainer_defaults or {})
         tkw.update({k: v for k, v in (self.config.get("trainer") or {}).items() if k in keys})
         tkw = {k: v for k, v in tkw.items() if k in keys + ("log_fn", "checkpoints")}

@@ -16,7 +16,7 @@ from typing import Any, Callable, Dict, List, Optional
 import torch
 import torch.distributed as dist
 
-from .optim import FlatAdamW
+from .optim import FlatAdamW, check_clip
 
 
 def dist_env() -> Dict[str, int]:
@@ -136,7 +136,16 @@ def _limit(n: int, limit) -> int:
 class Trainer:
     def __init__(self, max_epochs: int = 1, limit_train_batches=None, limit_val_batches=None, num_sanity_val_steps: int = 0,
                  log_fn: Optional[Callable[[str], None]] = print, checkpoints: Optional["CheckpointKeeper"] = None,
-                 **ignored: Any) -> None:
+                 gradient_clip_val: Optional[float] = None, gradient_clip_algorithm: Optional[str] = None,
+                 accumulate_grad_batches: Optional[int] = None, **ignored: Any) -> None:
+        """``gradient_clip_val`` / ``gradient_clip_algorithm`` / ``accumulate_grad_batches`` as in ``pl.Trainer`` (None: no
+        clip / "norm" / 1); they apply to automatic-optimization modules, and ``fit`` refuses them for a manual one."""
+        self.gradient_clip_val, self.gradient_clip_algorithm = check_clip(gradient_clip_val, gradient_clip_algorithm)
+        k = 1 if accumulate_grad_batches is None else accumulate_grad_batches
+        if isinstance(k, bool) or not isinstance(k, int) or k < 1:
+            raise ValueError(f"accumulate_grad_batches {accumulate_grad_batches!r}: expected an integer >= 1 or None")
+        self.accumulate_grad_batches = k
+        self._window_has_grad = False       # a backward has run since the accumulation window opened
         self.max_epochs = max_epochs
         self.limit_train_batches, self.limit_val_batches = limit_train_batches, limit_val_batches
         self.num_sanity_val_steps = num_sanity_val_steps
@@ -150,17 +159,33 @@ class Trainer:
         if self.log_fn is not None and self.env["rank"] == 0:
             self.log_fn(msg)
 
-    def train_step(self, module, optimizer: FlatAdamW, batch) -> Optional[torch.Tensor]:
-        """forward + loss + backward + all-reduce + AdamW for an LFOExtraction-style module."""
-        optimizer.zero_grad()
+    def train_step(self, module, optimizer: FlatAdamW, batch, window_index: int = 0, window_close: bool = True
+                   ) -> Optional[torch.Tensor]:
+        """forward + loss + backward + all-reduce + AdamW for an LFOExtraction-style module.
+
+        With ``accumulate_grad_batches = k > 1`` the caller passes the position of this micro-batch in its window:
+        ``window_index`` 0 opens it (``zero_grad()``, backward inside ``direct_backward()``), later ones accumulate with a
+        plain backward, and ``window_close`` (index k - 1, or the last batch of the epoch) ends it with ONE all-reduce and
+        ONE optimizer step at ``grad_scale = scale / k`` -- always k, also for a short last window, as Lightning divides every
+        micro-loss by k.  The defaults are a window of one batch."""
+        k = self.accumulate_grad_batches
+        if window_index == 0:
+            optimizer.zero_grad()
+            self._window_has_grad = False
         loss = module.training_step(batch, 0)
         if loss is not None:
-            with optimizer.direct_backward():       # first backward after zero_grad(): gradients may be written in place
-                loss.backward()
-        elif self.env["world_size"] == 1:
+            if window_index == 0:
+                with optimizer.direct_backward():   # first backward after zero_grad(): gradients may be written in place
+                    loss.backward()
+            else:
+                loss.backward()                     # accumulates into the flat gradient
+            self._window_has_grad = True
+        if not window_close:
+            return loss
+        if not self._window_has_grad and self.env["world_size"] == 1:
             return None                 # Lightning skips the optimizer step when training_step returns None
         scale = allreduce_flat_grad(optimizer.flat_grad, self.env["world_size"])   # DDP: stay in lock-step
-        optimizer.step(grad_scale=scale)
+        optimizer.step(grad_scale=scale if k == 1 else scale / k)
         return loss
 
     def validate(self, module, datamodule, n_steps: Optional[int] = None) -> Dict[str, float]:
@@ -184,6 +209,12 @@ class Trainer:
 
     def fit(self, module, datamodule, optimizer: FlatAdamW) -> List[Dict[str, float]]:
         manual = getattr(module, "automatic_optimization", True) is False
+        if manual and (self.gradient_clip_val is not None or self.accumulate_grad_batches > 1):
+            # Lightning refuses both under manual optimization: the module takes its own optimizer steps
+            raise ValueError("gradient_clip_val / accumulate_grad_batches of the trainer do not apply to a manual-optimization "
+                             "module (it steps the optimizer itself): set the optimizer's clip_val / clip_algorithm instead")
+        if self.gradient_clip_val is not None:
+            optimizer.set_gradient_clip(self.gradient_clip_val, self.gradient_clip_algorithm)
         if self.num_sanity_val_steps:
             self.validate(module, datamodule, self.num_sanity_val_steps)
         # (an extractor that is being trained must see the weights of the step that uses it: no look-ahead then)
@@ -220,7 +251,9 @@ class Trainer:
                     kw = {"prep": datamodule.take_ahead()} if prefetch else {}
                     module.training_step(batch, i, optimizer=optimizer, world_size=self.env["world_size"], **kw)
                 else:
-                    self.train_step(module, optimizer, batch)
+                    j = i % self.accumulate_grad_batches
+                    self.train_step(module, optimizer, batch, window_index=j,
+                                    window_close=j == self.accumulate_grad_batches - 1 or i == n - 1)
             metrics = reduce_metrics(module.logged, self.env["world_size"], metric_names(module, "train"))
             metrics.update(self.validate(module, datamodule))
             metrics["epoch"] = epoch
