@@ -48,27 +48,60 @@ class BaseLightingModule(nn.Module):
         self.loss_funcs = nn.ModuleList([] if self._fused_lfo else
                                         [L.get_loss_func_by_name(name) for name in self.loss_dict])
         self.logged: Dict[str, List[T]] = defaultdict(list)
+        self._extra_losses = {}           # loss modules outside effect_loss_terms (mrstft, ...), built once, by name
 
     def log(self, name: str, value: T) -> None:
         """Stands in for LightningModule.log(on_epoch=True, sync_dist=True): values are kept as
         device scalars; the trainer reduces them to epoch means (and all-reduces across ranks)."""
         self.logged[name].append(value.detach())
 
-    def calc_and_log_losses(self, y_hat: T, y: T, prefix: str, should_log: bool = True) -> T:
-        """lightning.py:33-62: weighted sum of the named losses; zero-weight terms are only logged."""
-        if self._fused_lfo:
-            loss, terms = L.lfo_loss(y_hat, y, self.loss_dict)
-        else:
-            terms = {name: f(y_hat, y) for name, f in zip(self.loss_dict, self.loss_funcs)}
-            loss = None
-            for name, w in self.loss_dict.items():
-                if w > 0:
-                    loss = w * terms[name] if loss is None else loss + w * terms[name]
-        if should_log:
-            for name in self.loss_dict:
-                self.log(f"{prefix}/{name}", terms[name])
-            self.log(f"{prefix}/loss", loss)
+    @staticmethod
+    def weighted_sum(terms: Dict[str, T], weights: Dict[str, float]) -> Optional[T]:
+        """sum_k w_k terms[k] over the positive weights, in the order of ``weights`` (the first term starts the sum); None
+        without a positive weight."""
+        loss = None
+        for name, w in weights.items():
+            if w > 0:
+                loss = w * terms[name] if loss is None else loss + w * terms[name]
         return loss
+
+    def calc_and_log_losses(self, y_hat: T, y: T, loss_dict: Dict[str, float], prefix: str, log_total: bool = True) -> Optional[T]:
+        """lightning.py:33-62: weighted sum of the losses ``loss_dict`` names (those the constructor was given); zero-weight
+        terms are only logged.  Every term is logged as ``{prefix}{name}``, the sum (``log_total``) as ``{prefix}loss``."""
+        if self._fused_lfo:
+            loss, terms = L.lfo_loss(y_hat, y, loss_dict)
+        else:
+            terms = {name: f(y_hat, y) for name, f in zip(loss_dict, self.loss_funcs)}
+            loss = self.weighted_sum(terms, loss_dict)
+        for name in loss_dict:
+            self.log(f"{prefix}{name}", terms[name])
+        if log_total:
+            self.log(f"{prefix}loss", loss)
+        return loss
+
+    @staticmethod
+    def center_crop_mod_sig(mod_sig: T, size: int) -> T:
+        if size == mod_sig.size(-1):
+            return mod_sig
+        assert size < mod_sig.size(-1)
+        padding = mod_sig.size(-1) - size
+        pad_l = padding // 2
+        return mod_sig[..., pad_l:pad_l + size]
+
+    def _loss_module(self, name: str):
+        """One module per loss name for the lifetime of the step object (the MR-STFT module owns window / twiddle tables on
+        the device: building it per batch re-uploaded them); the same object serves the gradient and the logging.  A plain
+        dict: these modules are no submodules and stay out of the state dict."""
+        mod = self._extra_losses.get(name)
+        if mod is None:
+            mod = self._extra_losses[name] = L.get_loss_func_by_name(name)
+        return mod
+
+    def _grad_modules(self):
+        """The loss modules ``effect_loss_grad`` reuses, by the dict that names the step's audio losses."""
+        names = getattr(self, "audio_loss_dict", self.loss_dict)
+        return {"mrstft": self._loss_module("mrstft") if "mrstft" in names else None,
+                "logmel": self._loss_module("log_mel_l1") if "log_mel_l1" in names else None}
 
 
 class LFOExtraction(BaseLightingModule):
@@ -91,15 +124,6 @@ class LFOExtraction(BaseLightingModule):
         self.max_n_corners = max_n_corners
         self.stretch_smooth_n_frames = stretch_smooth_n_frames
         self.sub_batch_size = sub_batch_size
-
-    @staticmethod
-    def center_crop_mod_sig(mod_sig: T, size: int) -> T:
-        if size == mod_sig.size(-1):
-            return mod_sig
-        assert size < mod_sig.size(-1)
-        padding = mod_sig.size(-1) - size
-        pad_l = padding // 2
-        return mod_sig[..., pad_l:pad_l + size]
 
     def common_step(self, batch, is_training: bool):
         """lightning.py:96-158."""
@@ -130,7 +154,7 @@ class LFOExtraction(BaseLightingModule):
             if self.stretch_smooth_n_frames > 1:
                 mod_sig = self.center_crop_mod_sig(mod_sig, mod_sig_hat.size(-1))
         assert mod_sig.shape == mod_sig_hat.shape
-        loss = self.calc_and_log_losses(mod_sig_hat, mod_sig.contiguous(), prefix)
+        loss = self.calc_and_log_losses(mod_sig_hat, mod_sig.contiguous(), self.loss_dict, f"{prefix}/")
         data_dict = {"wet": wet.detach(), "mod_sig": mod_sig.detach(), "mod_sig_hat": mod_sig_hat.detach()}
         if dry is not None:
             data_dict["dry"] = dry.detach()
@@ -160,32 +184,31 @@ class LFOExtraction(BaseLightingModule):
             return step(batch, is_training=False)
 
 
-def _audio_loss_node(ctx, step, wet_hat, wet, terms, adjoint):
-    """What the audio-loss nodes of every effect share, after the effect's forward has rendered ``wet_hat`` (B, N): the
-    value-and-gradient kernels of the weighted losses (``effect_loss_grad``), the effect's ``adjoint(dy) -> dmod`` at once,
-    the unweighted terms and the weighted sum.  Only d loss / d mod_sig_hat (B, n_frames) is kept for the backward; d loss /
-    d wet_hat and whatever the adjoint closes over do not outlive the call."""
-    from .effect_losses import effect_loss_grad, effect_loss_terms
-    a, t = wet_hat.unsqueeze(1), wet.unsqueeze(1)
-    weighted: Dict[str, T] = {}
-    dy = effect_loss_grad(a, t, step.audio_loss_dict, values=weighted, **step._grad_modules())
-    dmod = adjoint(dy)
-    w = {k: v for k, v in step.audio_loss_dict.items() if v > 0}
-    terms.update({k: v / w[k] for k, v in weighted.items()})
-    if any(k in w for k in ("l1", "mse", "esr", "dc")):
-        terms.update({k: v for k, v in effect_loss_terms(a, t).items() if k in w})
-    loss = None
-    for k, wk in w.items():
-        loss = wk * terms[k] if loss is None else loss + wk * terms[k]
-    ctx.save_for_backward(dmod)
-    ctx.mark_non_differentiable(wet_hat)
-    return loss, wet_hat
-
-
 class _EffectAudioLossFn(torch.autograd.Function):
-    """loss = sum_k w_k loss_k(effect(dry, mod_sig_hat), wet) as ONE autograd node: ``forward(ctx, mod_sig_hat, step, dry,
-    wet, consts, terms)`` returns (loss, wet_hat (B, N)) and fills ``terms`` with the unweighted value of every weighted
-    loss; the gradient was computed in the forward (``_audio_loss_node``), the backward scales it."""
+    """loss = sum_k w_k loss_k(effect(dry, mod_sig_hat), wet) as ONE autograd node for every ``effect``: ``forward(ctx,
+    mod_sig_hat, step, dry, wet, consts, terms)`` returns (loss, wet_hat (B, N)) and fills ``terms`` with the unweighted
+    value of every weighted loss.  Every family renders its rows into one wet_hat (``step._render_rows``), the
+    value-and-gradient kernels of the weighted losses run once (``effect_loss_grad``), and every family's adjoint writes its
+    rows of one (B, n_frames) gradient at once (``step._adjoint_rows``).  Only that gradient is kept for the backward, which
+    scales it; d loss / d wet_hat, the stashes (allocated for all B rows) and the adjoints' workspaces do not outlive the
+    call."""
+
+    @staticmethod
+    def forward(ctx, mod_sig_hat, step, dry, wet, consts, terms):
+        from .effect_losses import effect_loss_grad, effect_loss_terms
+        mod = mod_sig_hat.detach().float().contiguous()
+        wet_hat, stashes = step._render_rows(dry, mod, consts, stash=True)
+        a, t = wet_hat.unsqueeze(1), wet.unsqueeze(1)
+        weighted: Dict[str, T] = {}
+        dy = effect_loss_grad(a, t, step.audio_loss_dict, values=weighted, **step._grad_modules())
+        dmod = step._adjoint_rows(dy, dry, mod, consts, stashes)
+        w = {k: v for k, v in step.audio_loss_dict.items() if v > 0}
+        terms.update({k: v / w[k] for k, v in weighted.items()})
+        if any(k in w for k in ("l1", "mse", "esr", "dc")):
+            terms.update({k: v for k, v in effect_loss_terms(a, t).items() if k in w})
+        ctx.save_for_backward(dmod)
+        ctx.mark_non_differentiable(wet_hat)
+        return step.weighted_sum(terms, step.audio_loss_dict), wet_hat
 
     @staticmethod
     def backward(ctx, g, _g_wet_hat):
@@ -193,62 +216,7 @@ class _EffectAudioLossFn(torch.autograd.Function):
         return dmod * g, None, None, None, None, None
 
 
-class _FlangerAudioLossFn(_EffectAudioLossFn):
-    """The flanger / chorus: the stash forward (``mx_flanger_fwd_stash`` on the low-rate LFO) and the adjoint
-    (``mx_flanger_bwd_lr``); the (B, N) stash and the adjoint's workspace do not outlive the call."""
-
-    @staticmethod
-    def forward(ctx, mod_sig_hat, step, dry, wet, consts, terms):
-        from . import fx
-        mod = mod_sig_hat.detach().float().contiguous()
-        md, M = step._max_delay_rows(dry.size(0), dry.device), step.max_delay_samples
-        wet_hat, stash = fx.flanger_forward_stash(dry, mod, consts, md, M)
-        return _audio_loss_node(ctx, step, wet_hat, wet, terms, lambda dy: fx.flanger_backward(
-            dy, dry, mod, stash, consts, md, M, need_dx=False, params=())[1])
-
-
-class _TremoloAudioLossFn(_EffectAudioLossFn):
-    """The tremolo: ``mx_tremolo_fwd`` on the low-rate LFO and ``mx_tremolo_bwd`` asked for dmod alone (no stash: the
-    effect has no state)."""
-
-    @staticmethod
-    def forward(ctx, mod_sig_hat, step, dry, wet, consts, terms):
-        from . import fx
-        mod = mod_sig_hat.detach().float().contiguous()
-        wet_hat = fx.tremolo_forward(dry, mod, consts)
-        return _audio_loss_node(ctx, step, wet_hat, wet, terms, lambda dy: fx.tremolo_backward(
-            dy, dry, mod, consts, need_dx=False, need_dmix=False)[1])
-
-
-class _PhaserAudioLossFn(_EffectAudioLossFn):
-    """The phaser: ``mx_phaser_mod_expand`` + ``mx_phaser_fwd_stash`` on the low-rate LFO (lead 0, empty filter state) and
-    ``mx_phaser_bwd`` + ``mx_phaser_dmod_gather`` asked for dmod alone; the stash and the two group-rate rows do not
-    outlive the call."""
-
-    @staticmethod
-    def forward(ctx, mod_sig_hat, step, dry, wet, consts, terms):
-        from . import fx
-        mod = mod_sig_hat.detach().float().contiguous()
-        n = dry.size(1)
-        wet_hat, stash, _ = fx.phaser_forward_stash_lr(dry, consts, None, step.sr, n, mod)
-        return _audio_loss_node(ctx, step, wet_hat, wet, terms, lambda dy: fx.phaser_backward_lr(
-            dy, dry, stash, consts, None, step.sr, n, mod.size(1), need_dx=False, params_wanted=())[1])
-
-
-class _MixedAudioLossFn(_EffectAudioLossFn):
-    """A batch that mixes effects: every family renders its rows into ONE wet_hat (B, N) through its row list
-    (``LFOExtractionThroughEffect._render_rows``) and its adjoint writes its rows of ONE zero-initialised (B, n_frames)
-    gradient (``_adjoint_rows``); dry rows are a copy of ``dry`` and keep a zero gradient.  The stashes (allocated for all B
-    rows) do not outlive the call."""
-
-    @staticmethod
-    def forward(ctx, mod_sig_hat, step, dry, wet, consts, terms):
-        mod = mod_sig_hat.detach().float().contiguous()
-        wet_hat, stashes = step._render_rows(dry, mod, consts, stash=True)
-        return _audio_loss_node(ctx, step, wet_hat, wet, terms,
-                                lambda dy: step._adjoint_rows(dy, dry, mod, consts, stashes))
-
-
+EFFECTS = ("flanger", "tremolo", "phaser")              # what a string ``effect`` may name
 MIXED_KINDS = ("flanger", "chorus", "phaser", "tremolo", "dry")
 
 
@@ -265,28 +233,27 @@ def mixed_row_lists(kinds: Sequence[str], bs: int) -> Dict[str, List[int]]:
 
 class LFOExtractionThroughEffect(BaseLightingModule):
     """Trains the LFO extractor on dry / wet pairs WITHOUT an LFO label: the extractor's LFO drives a differentiable
-    effect -- ``effect="flanger"`` (flanger / chorus, the default), ``effect="tremolo"`` or ``effect="phaser"`` -- on ``dry`` and an audio-domain
-    loss compares the result with ``wet``.  The reference has no such step
+    effect on ``dry`` and an audio-domain loss compares the result with ``wet``.  The reference has no such step
     (its lightning.py:65-199 trains against the ground-truth LFO only; its flanger, fx.py:72-119, has no usable autograd).
 
     Same batch 4-tuple ``(dry, wet, mod_sig, fx_params)`` and metric naming as ``LFOExtraction``; ``training_step`` returns a
     loss with a grad graph, so ``trainer.Trainer`` drives it unchanged.
-    * ``max_min_delay_ms`` / ``max_lfo_delay_ms``: the flanger geometry (with a string ``effect``: ONE flanger or chorus
-      geometry per module, as in ``fx.MonoFlangerChorusModule``).  ``effect="tremolo"`` and ``effect="phaser"`` ignore both
-      and have no delay-line limit.  ``chorus_max_min_delay_ms`` / ``chorus_max_lfo_delay_ms`` (default
-      ``data_modules.CHORUS_FX``: 30 ms / 10 ms): the geometry of the "chorus" rows of a mixed batch.
-    * ``effect``: a string = ONE effect family per module, or a sequence of kinds out of "flanger", "chorus", "phaser",
-      "tremolo", "dry" = a batch that mixes them: row i is of kind ``effect[i % len(effect)]``, the batcher's own rule
-      (``data_modules.SyntheticFxBatcher``, datasets.py:79-83), so ``InterwovenDataModule`` batches and each DDP rank's
-      local batch line up with ``effect=("flanger", "chorus", "phaser")``.  Every family renders its rows into one shared
-      wet_hat and its adjoint writes its rows of one shared gradient through the kernels' row lists
-      (``_MixedAudioLossFn``); the per-row delay-line lengths and constants are formed with the batcher's own fp32
-      arithmetic.  "dry" rows are copied and get a zero gradient.  ``fx_params`` then carries what the kinds present need,
-      each as ONE (B,) tensor over all rows (the batcher's merged ``depth`` / ``feedback`` / ``mix``).  The caveats below
-      apply row by row.
-    * ``fx_params`` carries the per-clip ``feedback``, ``min_delay_width``, ``width``, ``depth``, ``mix`` as (B,) tensors;
-      the tremolo needs only ``mix``; the phaser needs ``depth``, ``centre_frequency_hz``, ``feedback``, ``mix`` (its
-      ``rate_hz`` and ``lead`` are ignored: the LFO is the extractor's)
+    * ``effect``: "flanger" (flanger / chorus, the default), "tremolo" or "phaser" = that effect on every row; or a
+      sequence of kinds out of "flanger", "chorus", "phaser", "tremolo", "dry" = a batch that mixes them: row i is of kind
+      ``effect[i % len(effect)]``, the batcher's own rule (``data_modules.SyntheticFxBatcher``, datasets.py:79-83), so
+      ``InterwovenDataModule`` batches and each DDP rank's local batch line up with ``effect=("flanger", "chorus",
+      "phaser")``.  A string is the sequence of that one kind: there is ONE path.  Every launch family (flanger + chorus;
+      tremolo; phaser) renders its rows into one shared wet_hat and its adjoint writes its rows of one shared gradient
+      through the kernels' row lists (``_render_rows`` / ``_adjoint_rows``); a family that owns every row is launched
+      without a list.  "dry" rows are copied and get a zero gradient.  The caveats below apply row by row.
+    * ``max_min_delay_ms`` / ``max_lfo_delay_ms``: the geometry of the "flanger" rows (with ``effect="flanger"``: ONE flanger
+      or chorus geometry per module, as in ``fx.MonoFlangerChorusModule``); ignored without such a row.
+      ``chorus_max_min_delay_ms`` / ``chorus_max_lfo_delay_ms`` (default ``data_modules.CHORUS_FX``: 30 ms / 10 ms): the
+      geometry of the "chorus" rows of a sequence.  The tremolo and the phaser have no delay-line limit.
+    * ``fx_params`` carries what the kinds present need, each as ONE (B,) tensor over all rows (the batcher's merged
+      ``depth`` / ``feedback`` / ``mix``) or a python float: the flanger and chorus ``feedback``, ``min_delay_width``,
+      ``width``, ``depth``, ``mix``; the tremolo only ``mix``; the phaser ``depth``, ``centre_frequency_hz``, ``feedback``,
+      ``mix`` (its ``rate_hz`` and ``lead`` are ignored: the LFO is the extractor's)
       (``check_fx_params``: range-check them on every step, which costs host synchronisations).
     * ``audio_loss_dict``: names from ``effect_losses.GRAD_NAMES``; zero-weight names are only logged.
     * ``loss_dict`` (optional, default none): an LFO-domain term (lightning.py:33-62) added to the loss when the batch carries
@@ -302,7 +269,7 @@ class LFOExtractionThroughEffect(BaseLightingModule):
     therefore no smoothing.  The tremolo has no state, so this caveat does not apply to it: the re-render of a cropped
     clip does not depend on the samples before the crop.
 
-    ``effect="phaser"``, the lead-in rule: the step re-renders from ``dry`` ALONE, with lead 0 and empty filter state
+    The phaser's lead-in rule: the step re-renders from ``dry`` ALONE, with lead 0 and empty filter state
     (``mx_phaser_fwd_stash`` on the LFO expanded by ``mx_phaser_mod_expand``).  The batch's ``wet`` was rendered by JUCE's
     oscillator after ``fx_params["lead"]`` warm-up samples, which the batch tuple does not carry -- in the reference and the
     data path that lead exists to randomise the LFO's phase.  So at the true label the loss is small but NOT exactly 0, for
@@ -312,7 +279,6 @@ class LFOExtractionThroughEffect(BaseLightingModule):
 
     ``should_stretch`` is not wired in (the corner stretch has a backward, but not on this path)."""
     default_audio_loss_dict = {"mrstft": 1.0}
-    _nodes = {"flanger": _FlangerAudioLossFn, "tremolo": _TremoloAudioLossFn, "phaser": _PhaserAudioLossFn}
 
     def __init__(self,
                  model: nn.Module,
@@ -341,16 +307,17 @@ class LFOExtractionThroughEffect(BaseLightingModule):
             for k in effect:
                 if k not in MIXED_KINDS:
                     raise ValueError(f"effect kind '{k}': supported are {MIXED_KINDS}")
-        elif effect not in self._nodes:
-            raise ValueError(f"effect '{effect}': supported are {tuple(self._nodes)} or a sequence out of {MIXED_KINDS}")
+        elif effect not in EFFECTS:
+            raise ValueError(f"effect '{effect}': supported are {EFFECTS} or a sequence out of {MIXED_KINDS}")
         self.effect = effect
+        self._kinds: Tuple[str, ...] = (effect,) if self.kinds is None else self.kinds      # the slots every step goes by
         audio_loss_dict = dict(self.default_audio_loss_dict if audio_loss_dict is None else audio_loss_dict)
         for name, w in audio_loss_dict.items():
             if w > 0 and name not in GRAD_NAMES:
                 raise NotImplementedError(f"audio loss '{name}' has no gradient kernel (supported: {GRAD_NAMES})")
         if not any(w > 0 for w in audio_loss_dict.values()):
             raise ValueError("audio_loss_dict needs at least one loss with a weight above 0")
-        has_flanger = effect == "flanger" or (self.kinds is not None and "flanger" in self.kinds)
+        has_flanger = "flanger" in self._kinds
         if has_flanger:
             if max_min_delay_ms < 0 or max_lfo_delay_ms < 0:
                 raise ValueError("max_min_delay_ms and max_lfo_delay_ms must not be negative")
@@ -388,42 +355,23 @@ class LFOExtractionThroughEffect(BaseLightingModule):
         # the base class holds the LFO-domain term; loss_dict names every metric this step logs (trainer.metric_names)
         self.lfo_loss_dict = self.loss_dict
         self.loss_dict = dict(audio_loss_dict, **{f"lfo_{k}": w for k, w in self.lfo_loss_dict.items()})
-        self._extra_losses = {}
-        self._md = None
         self._mixed = None
 
-    center_crop_mod_sig = staticmethod(LFOExtraction.center_crop_mod_sig)
-
-    def _loss_module(self, name: str):
-        """One module per loss name for the lifetime of the step (device tables are built once)."""
-        mod = self._extra_losses.get(name)
-        if mod is None:
-            mod = self._extra_losses[name] = L.get_loss_func_by_name(name)
-        return mod
-
-    def _grad_modules(self):
-        return {"mrstft": self._loss_module("mrstft") if "mrstft" in self.audio_loss_dict else None,
-                "logmel": self._loss_module("log_mel_l1") if "log_mel_l1" in self.audio_loss_dict else None}
-
-    def _max_delay_rows(self, bs: int, device) -> T:
-        if self._md is None or self._md.size(0) != bs or self._md.device != device:
-            self._md = torch.full((bs,), self.max_delay_samples, device=device, dtype=torch.int32)
-        return self._md
-
     def _mixed_rows(self, bs: int, device) -> Dict[str, object]:
-        """A mixed batch of ``bs`` rows on ``device`` (cached like ``_max_delay_rows``): the int32 row list of every launch
-        family, the int64 list of the dry rows, and the per-row delay-line geometry as the batcher forms it
-        (``SyntheticFxBatcher.__init__``: fp32 sample counts, chorus rows the chorus geometry, every other row the
-        flanger's; only the rows of the "delay" list are read)."""
+        """The row plan of a batch of ``bs`` rows on ``device`` (cached): the int32 row list of every launch family, the
+        int64 list of the dry rows, the per-row delay-line geometry as the batcher forms it (``SyntheticFxBatcher.__init__``:
+        fp32 sample counts, chorus rows the chorus geometry, every other row the flanger's; only the rows of the "delay"
+        list are read), and "all_rows": the family that owns every row of the batch, if one does (else None)."""
         m = self._mixed
         if m is None or m["bs"] != bs or m["device"] != device:
-            lists = mixed_row_lists(self.kinds, bs)
-            kinds = [self.kinds[i % len(self.kinds)] for i in range(bs)]
+            lists = mixed_row_lists(self._kinds, bs)
+            kinds = [self._kinds[i % len(self._kinds)] for i in range(bs)]
             mm = torch.tensor([self.chorus_max_min_delay_samples if k == "chorus" else self.max_min_delay_samples
                                for k in kinds], dtype=torch.float32)
             ml = torch.tensor([self.chorus_max_lfo_delay_samples if k == "chorus" else self.max_lfo_delay_samples
                                for k in kinds], dtype=torch.float32)
             m = {"bs": bs, "device": device, "lists": lists,
+                 "all_rows": next((f for f in ("delay", "tremolo", "phaser") if len(lists[f]) == bs > 0), None),
                  "max_min_delay": mm.to(device), "max_lfo_delay": ml.to(device),
                  "max_delay": (mm + ml).to(torch.int32).to(device),
                  "max_delay_max": int(max([int(mm[i] + ml[i]) for i in lists["delay"]], default=0)),
@@ -433,101 +381,105 @@ class LFOExtractionThroughEffect(BaseLightingModule):
             self._mixed = m
         return m
 
-    def _mixed_constants(self, fx_params, bs: int, device) -> Dict[str, T]:
-        """ONE dict of (B,) fp32 constants for all families of a mixed batch, each formed as the data path forms it
-        (``SyntheticFxBatcher.render``: lfo_scale and min_delay are fp32 tensor products with the per-row sample counts,
-        one_minus_mix is 1 - mix in fp32), so a re-render from the label reproduces ``wet``.  Only what the kinds present
-        need is read from ``fx_params``."""
+    @staticmethod
+    def _launch_rows(m: Dict[str, object], family: str) -> Optional[T]:
+        """The row list a family's launches get.  A family that owns every row gets None: by the kernels' row-list contract
+        a listed row runs the very same code as without a list, so the bits are the same, and the launches, their arguments
+        and the allocations of ``effect="flanger"`` / ``"tremolo"`` / ``"phaser"`` are those of the un-listed wrappers
+        (``_render_rows`` / ``_adjoint_rows`` then allocate nothing themselves)."""
+        return None if m["all_rows"] == family else m[family]
+
+    def clip_constants(self, fx_params, bs: int, device) -> Dict[str, T]:
+        """ONE dict of (B,) fp32 constants for all families of the batch, each formed as the data path forms it
+        (``SyntheticFxBatcher.render``, ``fx.derive_clip_constants``): a tensor parameter meets the per-row sample count in
+        fp32 and one_minus_mix is 1 - mix in fp32; a python float meets them in double and is rounded once.  So a re-render
+        from the label reproduces ``wet``.  Only what the kinds present need is read from ``fx_params``."""
         from . import fx
         m = self._mixed_rows(bs, device)
+        lists = m["lists"]
 
-        def vec(name: str) -> T:
+        def vec(name: str, f=lambda v: v) -> T:
             p = fx_params[name]
-            assert isinstance(p, T) and p.shape == (bs,), f"fx_params['{name}']: a ({bs},) tensor"
-            return p.to(device=device, dtype=torch.float32).contiguous()
+            if isinstance(p, T):
+                assert p.shape == (bs,), f"fx_params['{name}']: a ({bs},) tensor or a python float"
+                return f(p.to(device=device, dtype=torch.float32)).contiguous()
+            return f(torch.full((bs,), float(p), device=device, dtype=torch.float64)).float()
 
-        lists, consts = m["lists"], {}
+        def on(name: str, fam: str) -> fx.Param:                    # a family's rows of a parameter (all rows, a float: as is)
+            p = fx_params[name]
+            return vec(name)[m[fam].long()] if isinstance(p, T) and m["all_rows"] != fam else p
+
+        if self.check_fx_params:                                    # each family's ranges on its own rows
+            n = {f: len(lists[f]) for f in lists}
+            if n["delay"]:
+                fx._check_param(on("feedback", "delay"), n["delay"], can_be_one=False)
+                for name in ("min_delay_width", "width", "depth", "mix"):
+                    fx._check_param(on(name, "delay"), n["delay"])
+            if n["tremolo"]:
+                fx._check_param(on("mix", "tremolo"), n["tremolo"])
+            if n["phaser"]:
+                fx.derive_phaser_params(n["phaser"], device, on("depth", "phaser"), on("centre_frequency_hz", "phaser"),
+                                        on("feedback", "phaser"), on("mix", "phaser"), check=True)
+        consts = {}
         if lists["delay"] or lists["tremolo"] or lists["phaser"]:
             consts["mix"] = vec("mix")
-            consts["one_minus_mix"] = (1.0 - consts["mix"]).contiguous()
+        if lists["delay"] or lists["tremolo"]:
+            consts["one_minus_mix"] = vec("mix", lambda v: 1.0 - v)
         if lists["delay"] or lists["phaser"]:
             consts["feedback"], consts["depth"] = vec("feedback"), vec("depth")
         if lists["delay"]:
-            consts["lfo_scale"] = (vec("width") * m["max_lfo_delay"]).contiguous()
-            consts["min_delay"] = (vec("min_delay_width") * m["max_min_delay"]).contiguous()
+            consts["lfo_scale"] = vec("width", lambda v: v * m["max_lfo_delay"])
+            consts["min_delay"] = vec("min_delay_width", lambda v: v * m["max_min_delay"])
         if lists["phaser"]:
             consts["centre_frequency_hz"] = vec("centre_frequency_hz")
-        if self.check_fx_params:                                    # each family's ranges on its own rows
-            def on(name: str, idx: T) -> T:
-                return vec(name)[idx]
-            for fam, idx in ((f, torch.tensor(lists[f], dtype=torch.int64, device=device)) for f in lists if lists[f]):
-                if fam == "delay":
-                    fx._check_param(on("feedback", idx), idx.numel(), can_be_one=False)
-                    for name in ("min_delay_width", "width", "depth", "mix"):
-                        fx._check_param(on(name, idx), idx.numel())
-                elif fam == "tremolo":
-                    fx._check_param(on("mix", idx), idx.numel())
-                elif fam == "phaser":
-                    fx.derive_phaser_params(idx.numel(), device, on("depth", idx), on("centre_frequency_hz", idx),
-                                            on("feedback", idx), on("mix", idx), check=True)
         return consts
 
     def _render_rows(self, dry: T, mod: T, consts: Dict[str, T], stash: bool):
-        """wet_hat (B, N) of a mixed batch, every family through its row list into the one buffer: flanger + chorus rows
+        """wet_hat (B, N), every family through its row list (``_launch_rows``) into the one buffer: flanger + chorus rows
         ``mx_flanger_fwd`` (``stash``: ``mx_flanger_fwd_stash``, the same bits), tremolo rows ``mx_tremolo_fwd``, phaser rows
-        the row-listed ``mx_phaser_mod_expand_rows`` + ``mx_phaser_fwd_stash`` with lead 0, dry rows a copy.  A family without
-        a row launches nothing.  Returns (wet_hat, the stashes ``_adjoint_rows`` needs -- empty unless ``stash``)."""
+        ``mx_phaser_mod_expand`` + ``mx_phaser_fwd_stash`` with lead 0, dry rows a copy.  A family without a row launches
+        nothing.  Returns (wet_hat, the stashes ``_adjoint_rows`` needs -- empty unless ``stash``)."""
         from . import fx
         B, N = dry.shape
         m = self._mixed_rows(B, dry.device)
-        wet_hat = torch.empty((B, N), device=dry.device, dtype=torch.float32)
+        wet_hat = None if m["all_rows"] else torch.empty((B, N), device=dry.device, dtype=torch.float32)
         stashes = {}
         if m["dry_idx"].numel():
             wet_hat.index_copy_(0, m["dry_idx"], dry.index_select(0, m["dry_idx"]))
         if m["delay"].numel():
+            geometry, rows = (m["max_delay"], m["max_delay_max"]), self._launch_rows(m, "delay")
             if stash:
-                stashes["delay"] = fx.flanger_forward_stash(dry, mod, consts, m["max_delay"], m["max_delay_max"],
-                                                            rows=m["delay"], out=wet_hat)[1]
+                wet_hat, stashes["delay"] = fx.flanger_forward_stash(dry, mod, consts, *geometry, rows=rows, out=wet_hat)
             else:
-                fx.flanger_forward(dry, mod, consts, m["max_delay"], m["max_delay_max"], rows=m["delay"], out=wet_hat)
+                wet_hat = fx.flanger_forward(dry, mod, consts, *geometry, rows=rows, out=wet_hat)
         if m["tremolo"].numel():
-            fx.tremolo_forward(dry, mod, consts, rows=m["tremolo"], out=wet_hat)
+            wet_hat = fx.tremolo_forward(dry, mod, consts, rows=self._launch_rows(m, "tremolo"), out=wet_hat)
         if m["phaser"].numel():
-            st = fx.phaser_forward_stash_lr(dry, consts, None, self.sr, N, mod, rows=m["phaser"], out=wet_hat)[1]
+            wet_hat, st, _ = fx.phaser_forward_stash_lr(dry, consts, None, self.sr, N, mod, rows=self._launch_rows(m, "phaser"),
+                                                        out=wet_hat)
             if stash:
                 stashes["phaser"] = st
         return wet_hat, stashes
 
     def _adjoint_rows(self, dy: T, dry: T, mod: T, consts: Dict[str, T], stashes: Dict[str, T]) -> T:
-        """d loss / d LFO (B, n_frames) of a mixed batch from d loss / d wet_hat (B, N): every family's adjoint, asked for
-        dmod alone, writes its rows of one zero-initialised buffer through the forward's row list (``mx_flanger_bwd_lr``;
-        ``mx_tremolo_bwd``; ``mx_phaser_bwd`` + ``mx_phaser_dmod_gather_rows``).  Dry rows keep the zeros."""
+        """d loss / d LFO (B, n_frames) from d loss / d wet_hat (B, N): every family's adjoint, asked for dmod alone, writes
+        its rows of one zero-initialised buffer through the forward's row list (``mx_flanger_bwd_lr``; ``mx_tremolo_bwd``;
+        ``mx_phaser_bwd`` + ``mx_phaser_dmod_gather``).  Dry rows keep the zeros.  A family that owns every row writes every
+        row: no zeros then, its wrapper's own ``torch.empty``."""
         from . import fx
         B, N = dry.shape
         m = self._mixed_rows(B, dry.device)
-        dmod = torch.zeros((B, mod.size(1)), device=dry.device, dtype=torch.float32)
+        dmod = None if m["all_rows"] else torch.zeros((B, mod.size(1)), device=dry.device, dtype=torch.float32)
         if m["delay"].numel():
-            fx.flanger_backward(dy, dry, mod, stashes["delay"], consts, m["max_delay"], m["max_delay_max"], rows=m["delay"],
-                                need_dx=False, params=(), dmod=dmod)
+            dmod = fx.flanger_backward(dy, dry, mod, stashes["delay"], consts, m["max_delay"], m["max_delay_max"],
+                                       rows=self._launch_rows(m, "delay"), need_dx=False, params=(), dmod=dmod)[1]
         if m["tremolo"].numel():
-            fx.tremolo_backward(dy, dry, mod, consts, rows=m["tremolo"], need_dx=False, need_dmix=False, dmod=dmod)
+            dmod = fx.tremolo_backward(dy, dry, mod, consts, rows=self._launch_rows(m, "tremolo"), need_dx=False,
+                                       need_dmix=False, dmod=dmod)[1]
         if m["phaser"].numel():
-            fx.phaser_backward_lr(dy, dry, stashes["phaser"], consts, None, self.sr, N, mod.size(1), need_dx=False,
-                                  params_wanted=(), rows=m["phaser"], dmod=dmod)
+            dmod = fx.phaser_backward_lr(dy, dry, stashes["phaser"], consts, None, self.sr, N, mod.size(1), need_dx=False,
+                                         params_wanted=(), rows=self._launch_rows(m, "phaser"), dmod=dmod)[1]
         return dmod
-
-    def clip_constants(self, fx_params, bs: int, device) -> Dict[str, T]:
-        from . import fx
-        if self.kinds is not None:
-            return self._mixed_constants(fx_params, bs, device)
-        if self.effect == "tremolo":
-            return fx.derive_tremolo_constants(bs, device, fx_params["mix"], check=self.check_fx_params)
-        if self.effect == "phaser":
-            return fx.derive_phaser_params(bs, device, fx_params["depth"], fx_params["centre_frequency_hz"],
-                                           fx_params["feedback"], fx_params["mix"], check=self.check_fx_params)
-        return fx.derive_clip_constants(bs, device, self.max_min_delay_samples, self.max_lfo_delay_samples,
-                                        fx_params["feedback"], fx_params["min_delay_width"], fx_params["width"],
-                                        fx_params["depth"], fx_params["mix"], check=self.check_fx_params)
 
     @staticmethod
     def _rows(audio: T) -> T:
@@ -536,28 +488,17 @@ class LFOExtractionThroughEffect(BaseLightingModule):
 
     def render(self, dry: T, mod_sig: T, fx_params) -> T:
         """wet_hat (B, 1, N) = the effect on ``dry`` (B, 1, N) driven by ``mod_sig`` (B, n_mod) at its own rate, with the
-        per-clip constants of ``fx_params``; no graph (``mx_flanger_fwd`` / ``mx_tremolo_fwd``, the data path's launches; the
-        phaser: ``mx_phaser_mod_expand`` + ``mx_phaser_fwd_stash`` with lead 0, see the class docstring; a sequence
-        ``effect``: every family on its rows, ``_render_rows``)."""
-        from . import fx
+        per-clip constants of ``fx_params``; no graph and no stash kept (``_render_rows``: the data path's launches; the
+        phaser with lead 0, see the class docstring)."""
         rows = self._rows(dry)
         with torch.no_grad():
             consts = self.clip_constants(fx_params, rows.size(0), rows.device)
-            mod = mod_sig.detach().float().contiguous()
-            if self.kinds is not None:
-                y = self._render_rows(rows, mod, consts, stash=False)[0]
-            elif self.effect == "tremolo":
-                y = fx.tremolo_forward(rows, mod, consts)
-            elif self.effect == "phaser":
-                y = fx.phaser_forward_stash_lr(rows, consts, None, self.sr, rows.size(1), mod)[0]
-            else:
-                y = fx.flanger_forward(rows, mod, consts, self._max_delay_rows(rows.size(0), rows.device),
-                                       self.max_delay_samples)
+            y = self._render_rows(rows, mod_sig.detach().float().contiguous(), consts, stash=False)[0]
         return y.unsqueeze(1)
 
     def audio_loss(self, mod_sig_hat: T, dry: T, wet: T, fx_params, prefix: Optional[str] = None):
         """(loss, wet_hat (B, 1, N)) for an LFO (B, n_frames); with grad mode on and an LFO that requires grad the loss
-        carries the graph of the effect's ``_EffectAudioLossFn``, otherwise nothing is stashed and no backward kernel runs.  ``prefix``:
+        carries the graph of ``_EffectAudioLossFn``, otherwise nothing is stashed and no backward kernel runs.  ``prefix``:
         log every audio term under it."""
         from .effect_losses import effect_loss_terms
         dry_r, wet_r = self._rows(dry), self._rows(wet)
@@ -565,8 +506,7 @@ class LFOExtractionThroughEffect(BaseLightingModule):
         if torch.is_grad_enabled() and mod_sig_hat.requires_grad:
             with torch.no_grad():
                 consts = self.clip_constants(fx_params, dry_r.size(0), dry_r.device)
-            node = _MixedAudioLossFn if self.kinds is not None else self._nodes[self.effect]
-            loss, wet_hat = node.apply(mod_sig_hat, self, dry_r, wet_r, consts, terms)
+            loss, wet_hat = _EffectAudioLossFn.apply(mod_sig_hat, self, dry_r, wet_r, consts, terms)
             wet_hat = wet_hat.unsqueeze(1)
         else:
             wet_hat, loss = self.render(dry, mod_sig_hat, fx_params), None
@@ -579,27 +519,11 @@ class LFOExtractionThroughEffect(BaseLightingModule):
                     if k not in terms:
                         terms[k] = self._loss_module(k)(wet_hat, wet)
             if loss is None:
-                for k, w in self.audio_loss_dict.items():
-                    if w > 0:
-                        loss = w * terms[k] if loss is None else loss + w * terms[k]
+                loss = self.weighted_sum(terms, self.audio_loss_dict)
             if prefix is not None:
                 for k in self.audio_loss_dict:
                     self.log(f"{prefix}/{k}", terms[k])
         return loss, wet_hat
-
-    def _lfo_term(self, mod_sig_hat: T, mod_sig: T, prefix: str) -> Optional[T]:
-        """lightning.py:33-62 on the LFO itself (the optional supervised term)."""
-        if self._fused_lfo:
-            loss, terms = L.lfo_loss(mod_sig_hat, mod_sig, self.lfo_loss_dict)
-        else:
-            terms = {name: f(mod_sig_hat, mod_sig) for name, f in zip(self.lfo_loss_dict, self.loss_funcs)}
-            loss = None
-            for name, w in self.lfo_loss_dict.items():
-                if w > 0:
-                    loss = w * terms[name] if loss is None else loss + w * terms[name]
-        for name in self.lfo_loss_dict:
-            self.log(f"{prefix}/lfo_{name}", terms[name])
-        return loss
 
     def common_step(self, batch, is_training: bool):
         prefix = "train" if is_training else "val"
@@ -623,7 +547,8 @@ class LFOExtractionThroughEffect(BaseLightingModule):
             wet = self.center_crop_mod_sig(wet, n_samples).contiguous()
         loss, wet_hat = self.audio_loss(mod_sig_hat, dry, wet, fx_params, prefix)
         if self.lfo_loss_dict and mod_sig is not None:
-            lfo_term = self._lfo_term(mod_sig_hat, mod_sig.contiguous(), prefix)
+            lfo_term = self.calc_and_log_losses(mod_sig_hat, mod_sig.contiguous(), self.lfo_loss_dict, f"{prefix}/lfo_",
+                                                log_total=False)
             if lfo_term is not None:
                 loss = loss + lfo_term
         self.log(f"{prefix}/loss", loss)
@@ -686,8 +611,6 @@ class TBPTTLFOEffectModeling(BaseLightingModule):
                 raise NotImplementedError(f"effect-model loss '{name}' has no gradient kernel (supported: {GRAD_NAMES})")
         # only nn.L1Loss weighted (every shipped config): the BPTT kernel evaluates its gradient itself
         self._fused_l1 = all(w <= 0 or name == "l1" for name, w in self.loss_dict.items())
-        self._mrstft = None
-        self._extra_losses = {}           # loss modules outside effect_loss_terms (mrstft, ...), built once, by name
         self.warmup_n_samples, self.step_n_samples = warmup_n_samples, step_n_samples
         self.effect_model = effect_model
         self.lfo_model_weights_path = lfo_model_weights_path
@@ -719,8 +642,6 @@ class TBPTTLFOEffectModeling(BaseLightingModule):
         if self.lfo_model is not None and self.freeze_lfo_model:
             self.lfo_model.eval()               # frozen extractor stays in eval mode (lightning.py:243-244)
         return self
-
-    center_crop_mod_sig = staticmethod(LFOExtraction.center_crop_mod_sig)
 
     def extract_mod_sig(self, wet: T, mod_sig: Optional[T] = None, fx_params=None):
         """lightning.py:254-272."""
@@ -940,11 +861,9 @@ class TBPTTLFOEffectModeling(BaseLightingModule):
             for name in self.loss_dict:
                 if name not in terms:
                     terms[name] = self._loss_module(name)(_channel_rows(wet_hat), _channel_rows(wet_c))
-            loss = None
-            for name, w in self.loss_dict.items():
+            for name in self.loss_dict:
                 self.log(f"{prefix}/{name}", terms[name])
-                if w > 0:
-                    loss = w * terms[name] if loss is None else loss + w * terms[name]
+            loss = self.weighted_sum(terms, self.loss_dict)
             self.log(f"{prefix}/loss", loss)
         data_dict = {"dry": dry_c, "wet": wet_c, "wet_hat": wet_hat, "mod_sig_hat": mod_sig_hat}
         if mod_sig is not None:
@@ -993,21 +912,6 @@ class TBPTTLFOEffectModeling(BaseLightingModule):
         optimizer.step(grad_scale=allreduce_flat_grad(optimizer.flat_grad, world_size))
         em.detach_hidden()
         return y.detach(), lfo_sr, mod_sig_hat
-
-    def _loss_module(self, name: str):
-        """One module per loss name for the lifetime of the step object (the MR-STFT module owns window / twiddle tables on
-        the device: building it per batch re-uploaded them); `mrstft` is the same object for the gradient and for logging."""
-        mod = self._extra_losses.get(name)
-        if mod is None:
-            mod = self._extra_losses[name] = L.get_loss_func_by_name(name)
-            if name == "mrstft":
-                self._mrstft = mod
-        return mod
-
-    def _grad_modules(self):
-        """The loss modules ``effect_loss_grad`` reuses (their device tables are built once; the same objects log the terms)."""
-        return {"mrstft": self._loss_module("mrstft") if "mrstft" in self.loss_dict else None,
-                "logmel": self._loss_module("log_mel_l1") if "log_mel_l1" in self.loss_dict else None}
 
     def training_step(self, batch, batch_idx: int = 0, optimizer=None, world_size: int = 1, prep=None):
         assert optimizer is not None, "manual optimisation: pass the FlatAdamW optimizer"

@@ -15,7 +15,9 @@ tests/test_gpu_audio_loss_step.py, test_gpu_tremolo_step.py and test_gpu_phaser_
 4. it optimises: the recipe of tests/test_gpu_phaser_step.py::test_it_optimises on ("flanger", "chorus", "phaser"), B = 6;
    the per-kind ratios are printed, not gated.
 5. trainer.Trainer drives the module with InterwovenDataModule unchanged.
-6. one geometry: effect=("flanger",) gives the loss and gradient bits of effect="flanger"."""
+6. one geometry: effect=("flanger",) gives the loss and gradient bits of effect="flanger"; the same for the tremolo and the
+   phaser.
+7. a string effect is its un-listed launch sequence, written out by hand: wet_hat, gradient and loss bit for bit."""
 import math
 
 import numpy as np
@@ -236,16 +238,67 @@ def test_one_geometry_is_the_single_effect_step(dev):
     from mod_extraction_amd import lightning
     B, N = 4, 22272
     weights = {"mrstft": 1.0, "log_mel_l1": 0.5, "l1": 0.5}
-    dry, wet, mod, fxp = batch_of(dev, ("flanger",), B, N, 13)
-    h0 = (0.9 * mod + 0.05).contiguous()
-    out = []
-    for effect in ("flanger", ("flanger",)):
-        step = lightning.LFOExtractionThroughEffect(torch.nn.Identity(), sr=SR, effect=effect, audio_loss_dict=weights)
-        h = h0.clone().requires_grad_(True)
-        loss, wet_hat = step.audio_loss(h, dry, wet, fxp)
-        loss.backward()
-        out.append((loss.detach(), wet_hat, h.grad))
-        assert torch.equal(step.render(dry, mod, fxp), wet)
-    (l0, w0, g0), (l1, w1, g1) = out
-    assert float(l0) > 0 and float(g0.abs().max()) > 0
-    assert torch.equal(l0, l1) and torch.equal(w0, w1) and torch.equal(g0, g1)
+    for effect in ("flanger", "tremolo", "phaser"):
+        dry, wet, mod, fxp = batch_of(dev, (effect,), B, N, 13, fixed_lead=0)
+        h0 = (0.9 * mod + 0.05).contiguous()
+        out = []
+        for e in (effect, (effect,)):
+            step = lightning.LFOExtractionThroughEffect(torch.nn.Identity(), sr=SR, effect=e, audio_loss_dict=weights)
+            h = h0.clone().requires_grad_(True)
+            loss, wet_hat = step.audio_loss(h, dry, wet, fxp)
+            loss.backward()
+            out.append((loss.detach(), wet_hat, h.grad))
+            if effect != "phaser":                                              # the phaser's lead-in rule: near, not equal
+                assert torch.equal(step.render(dry, mod, fxp), wet), effect
+        (l0, w0, g0), (l1, w1, g1) = out
+        assert float(l0) > 0 and float(g0.abs().max()) > 0, effect
+        assert torch.equal(l0, l1) and torch.equal(w0, w1) and torch.equal(g0, g1), effect
+
+
+@pytest.mark.parametrize("effect", ["flanger", "tremolo", "phaser"])
+def test_string_effect_is_its_unlisted_launch_sequence(dev, effect):
+    """effect="flanger" / "tremolo" / "phaser" against the launch sequence written out by hand, no step code: the
+    ``fx.derive_*`` constants, the family's un-listed stash forward, ``effect_loss_grad``, the un-listed adjoint asked for
+    dmod alone, the weighted sum in dict order.  wet_hat, the gradient and the loss are torch.equal to those."""
+    from mod_extraction_amd import fx, lightning
+    from mod_extraction_amd.effect_losses import effect_loss_grad, effect_loss_terms
+    from mod_extraction_amd.util import linear_interpolate_last_dim
+    B, N, n_frames = 3, 22272, 88
+    weights = {"mrstft": 1.0, "log_mel_l1": 0.5, "l1": 0.5}
+    dry, wet, mod, fxp = batch_of(dev, (effect,), B, N, 17, fixed_lead=0)
+    step = lightning.LFOExtractionThroughEffect(torch.nn.Identity(), sr=SR, effect=effect, audio_loss_dict=weights)
+    t = torch.linspace(0.0, 1.0, n_frames, device=dev)                          # an LFO away from the label
+    bump = 0.1 * torch.sin(2 * math.pi * (1.5 * t[None, :] + torch.arange(B, device=dev)[:, None] / B))
+    h = (linear_interpolate_last_dim(mod, n_frames, align_corners=True) + bump).clamp(0.0, 1.0).clone().requires_grad_(True)
+    loss, wet_hat = step.audio_loss(h, dry, wet, fxp)
+    loss.backward()
+    x, lfo = dry[:, 0], h.detach()
+    if effect == "flanger":
+        c = fx.derive_clip_constants(B, dev, 44, 441, fxp["feedback"], fxp["min_delay_width"], fxp["width"], fxp["depth"],
+                                     fxp["mix"], check=False)
+        md = torch.full((B,), 485, device=dev, dtype=torch.int32)
+        y, st = fx.flanger_forward_stash(x, lfo, c, md, 485)
+    elif effect == "tremolo":
+        c = fx.derive_tremolo_constants(B, dev, fxp["mix"], check=False)
+        y = fx.tremolo_forward(x, lfo, c)
+    else:
+        c = fx.derive_phaser_params(B, dev, fxp["depth"], fxp["centre_frequency_hz"], fxp["feedback"], fxp["mix"], check=False)
+        y, st, _ = fx.phaser_forward_stash_lr(x, c, None, SR, N, lfo)
+    weighted = {}
+    dy = effect_loss_grad(y.unsqueeze(1), wet, weights, values=weighted, **step._grad_modules())
+    if effect == "flanger":
+        want = fx.flanger_backward(dy, x, lfo, st, c, md, 485, need_dx=False, params=())[1]
+    elif effect == "tremolo":
+        want = fx.tremolo_backward(dy, x, lfo, c, need_dx=False, need_dmix=False)[1]
+    else:
+        want = fx.phaser_backward_lr(dy, x, st, c, None, SR, N, n_frames, need_dx=False, params_wanted=())[1]
+    terms = {k: v / weights[k] for k, v in weighted.items()}
+    terms["l1"] = effect_loss_terms(y.unsqueeze(1), wet)["l1"]
+    want_loss = 1.0 * terms["mrstft"] + 0.5 * terms["log_mel_l1"] + 0.5 * terms["l1"]
+    print(f"{effect}: loss {float(loss.detach()):.6e} (by hand {float(want_loss):.6e}), max |grad| {float(want.abs().max()):.3e}, "
+          f"{int((h.grad != want).sum())} of {want.numel()} gradient values and "
+          f"{int((wet_hat[:, 0] != y).sum())} of {y.numel()} samples differ")
+    assert not torch.equal(y, x) and float(want.abs().max()) > 0 and torch.isfinite(want).all()
+    assert torch.equal(wet_hat[:, 0], y)
+    assert h.grad.shape == (B, n_frames) and torch.equal(h.grad, want)
+    assert float(loss) > 0 and torch.equal(loss.detach(), want_loss)

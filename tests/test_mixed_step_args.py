@@ -144,3 +144,51 @@ def test_shipped_config_builds_its_object_graph():
     assert cli.resolve_class(c.optimizer_spec["class_path"]) is optim.FlatAdamW
     assert sum(p.numel() for p in c.model.parameters()) == 1340353
     assert c.trainer.max_epochs == 400
+
+
+@pytest.mark.parametrize("effect", ["flanger", "tremolo", "phaser"])
+def test_string_effect_constants_are_fx_derive(effect):
+    """One rule for the constants: a string effect's are those of its ``fx.derive_*``, key for key and bit for bit, for
+    tensor parameters (they meet the sample counts in fp32) and for python floats (in double, rounded once)."""
+    from mod_extraction_amd import fx
+    torch.manual_seed(1)
+    B = 5
+    step = step_of(effect)
+    as_tensors = {k: torch.rand(B) for k in ("feedback", "min_delay_width", "width", "depth", "mix")}
+    as_tensors["centre_frequency_hz"] = 100.0 + 1000.0 * torch.rand(B)
+    as_floats = {"feedback": 0.3, "min_delay_width": 0.7, "width": 0.1, "depth": 0.9, "mix": 0.6, "centre_frequency_hz": 1300.1}
+    for fxp in (as_tensors, as_floats):
+        if effect == "flanger":
+            want = fx.derive_clip_constants(B, CPU, 44, 441, fxp["feedback"], fxp["min_delay_width"], fxp["width"],
+                                            fxp["depth"], fxp["mix"])
+        elif effect == "tremolo":
+            want = fx.derive_tremolo_constants(B, CPU, fxp["mix"])
+        else:
+            want = fx.derive_phaser_params(B, CPU, fxp["depth"], fxp["centre_frequency_hz"], fxp["feedback"], fxp["mix"])
+        got = step.clip_constants(fxp, B, CPU)
+        assert set(got) == set(want)
+        for k in want:
+            assert got[k].dtype == torch.float32 and got[k].is_contiguous() and torch.equal(got[k], want[k]), k
+    # check_fx_params: the family owns every row, the ranges are checked on the parameters as they are
+    checked = step_of(effect, check_fx_params=True)
+    checked.clip_constants(as_tensors, B, CPU)
+    checked.clip_constants(as_floats, B, CPU)
+    for bad in (dict(as_tensors, mix=as_tensors["mix"] + 1.0), dict(as_floats, mix=1.5)):
+        with pytest.raises(AssertionError):
+            checked.clip_constants(bad, B, CPU)
+
+
+def test_string_flanger_row_plan():
+    """The row plan of a string effect: every row the one geometry, one family that owns all rows."""
+    step = step_of("flanger")
+    B = 6
+    m = step._mixed_rows(B, CPU)
+    assert torch.equal(m["max_delay"], torch.full((B,), 485, dtype=torch.int32)) and m["max_delay"].dtype == torch.int32
+    assert m["max_delay_max"] == 485 == step.max_delay_samples
+    assert m["delay"].tolist() == list(range(B)) and m["all_rows"] == "delay"
+    assert step_of(("flanger", "chorus"))._mixed_rows(B, CPU)["all_rows"] == "delay"       # one family, two geometries
+    assert step_of("tremolo")._mixed_rows(B, CPU)["all_rows"] == "tremolo"
+    assert step_of("phaser")._mixed_rows(B, CPU)["all_rows"] == "phaser"
+    assert step_of(("flanger", "phaser"))._mixed_rows(B, CPU)["all_rows"] is None
+    assert step_of(("flanger", "phaser"))._mixed_rows(1, CPU)["all_rows"] == "delay"       # a batch without a phaser row
+    assert step_of(("dry",))._mixed_rows(B, CPU)["all_rows"] is None

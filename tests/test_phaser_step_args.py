@@ -24,8 +24,11 @@ def test_phaser_step_lists_its_metrics():
 
 def test_phaser_node_is_registered_and_unknown_effects_still_raise():
     from mod_extraction_amd import lightning
-    assert set(lightning.LFOExtractionThroughEffect._nodes) == {"flanger", "tremolo", "phaser"}
-    assert issubclass(lightning._PhaserAudioLossFn, lightning._EffectAudioLossFn)
+    for effect in ("flanger", "tremolo", "phaser"):
+        assert lightning.LFOExtractionThroughEffect(torch.nn.Identity(), effect=effect).effect == effect
+    for effect in ("chorus", "dry"):                                                    # kinds of a sequence, not strings
+        with pytest.raises(ValueError):
+            lightning.LFOExtractionThroughEffect(torch.nn.Identity(), effect=effect)
     with pytest.raises(ValueError):
         lightning.LFOExtractionThroughEffect(torch.nn.Identity(), effect="wah")
 
