@@ -707,6 +707,31 @@ int mx_logmel_l1_loss(const float *y_hat, int64_t y_hat_stride, const float *y, 
                       int32_t accumulate, double *part, float *scratch, float *value, float *dx, int64_t dx_stride,
                       void *stream);
 
+/* ---- K15: FIR pre-emphasis and the ESR taken after it (csrc/pre_emph_loss.hip) -- mod_extraction/wright_code.py:47-73
+ * (WrightPreEmph; Conv1d is a cross-correlation) and losses.py:34-38 (ESRLoss) on its outputs.  The linear map F on a row
+ * x[0..T), taps (K,) a device pointer, the stages applied one after the other in fp32:
+ *   stage 1  f[n] = sum_k taps[k] x[n-(K-1)+k], n = 0..T-1, x[<0] = 0;
+ *   stage 2  (low_pass != 0 only, taps [0.85, 1], no padding)  g[n] = 0.85 f[n] + f[n+1], n = 0..T-2;
+ * so F x has L = T entries without low_pass and T - 1 with it.  F^T is the exact transpose of the two stages, boundary rows
+ * included.  All rows carry a row stride.  NULL pointers, B <= 0, T <= 0, L <= 0 (T == 1 with low_pass), an output stride
+ * below the output row length: MX_ERR_ARG; K < 1, K > 16 or T >= 2^30: MX_ERR_UNSUPPORTED; all before any launch.
+ *
+ * mx_pre_emph: out[b, 0..L) = F(x[b, 0..T)); transpose != 0: out[b, 0..T) = F^T(x[b, 0..L)) (the backward of the former).
+ * x_stride must cover the input row (else MX_ERR_ARG); B <= 65535. */
+int mx_pre_emph(const float *x, int64_t x_stride, int64_t B, int64_t T, const float *taps, int64_t K, int32_t low_pass,
+                int32_t transpose, float *out, int64_t out_stride, void *stream);
+/* part (B, 2) = per-clip ( sum (F(y - y_hat))^2, sum (F y)^2 ): fp64 sums in a fixed order, no atomics.  The pre-emphasised
+ * ESR is mean_b part[b,0] / (part[b,1] + eps). */
+int mx_pre_emph_esr_sums(const float *y_hat, int64_t y_hat_stride, const float *y, int64_t y_stride, int64_t B, int64_t T,
+                         const float *taps, int64_t K, int32_t low_pass, float *part, void *stream);
+/* dy (B rows of T samples, stride dy_stride >= T, also when L = T - 1) = or (accumulate != 0) +=
+ *   w * d/d y_hat [ mean_b sum (F(y - y_hat))^2 / (sum (F y)^2 + eps) ] = (2 w / B) F^T F (y_hat - y) / (sum (F y)^2 + eps),
+ * and part as mx_pre_emph_esr_sums leaves it: one launch gives value and gradient (one workgroup per clip, a reduction sweep,
+ * then the write sweep while the row is cache-resident, as mx_effect_loss_grad). */
+int mx_pre_emph_esr_grad(const float *y_hat, int64_t y_hat_stride, const float *y, int64_t y_stride, int64_t B, int64_t T,
+                         const float *taps, int64_t K, int32_t low_pass, float w, float eps, int32_t accumulate,
+                         float *part, float *dy, int64_t dy_stride, void *stream);
+
 /* ---- K12: AdamW -- torch.optim.AdamW (configs/opt/adam_w.yml), flat fp32 buffers of n elements;
  * step = 1-based step index; grad_scale multiplies the gradient first (1/world after a sum
  * all-reduce). */

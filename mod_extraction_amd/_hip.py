@@ -124,6 +124,9 @@ SIGNATURES = {
                        _I64, _P],
     "mx_logmel_l1_loss": [_P, _I64, _P, _I64, _I64, _I64, _P, _P, _P, _P, _P, _I64, _I64, _I64, _F32, _F32, _I32, _P, _P,
                           _P, _P, _I64, _P],
+    "mx_pre_emph": [_P, _I64, _I64, _I64, _P, _I64, _I32, _I32, _P, _I64, _P],
+    "mx_pre_emph_esr_sums": [_P, _I64, _P, _I64, _I64, _I64, _P, _I64, _I32, _P, _P],
+    "mx_pre_emph_esr_grad": [_P, _I64, _P, _I64, _I64, _I64, _P, _I64, _I32, _F32, _F32, _I32, _P, _P, _I64, _P],
     "mx_adamw_step": [_P, _P, _P, _P, _I64, _I64, _F32, _F32, _F32, _F32, _F32, _F32, _P],
     "mx_reduce_rows_adamw_step": [_P, _I64, _P, _P, _P, _P, _I64, _I64, _F32, _F32, _F32, _F32, _F32, _F32, _P],
     "mx_grad_sumsq": [_P, _I64, _P, _P, _P],

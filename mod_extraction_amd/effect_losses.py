@@ -23,16 +23,18 @@ def effect_loss_terms(y_hat: T, y: T, eps: float = 1e-8) -> Dict[str, T]:
             "dc": ((s_e / Tn) ** 2 / (s_yy / Tn + eps)).mean()}                   # losses.py:61-66
 
 
-GRAD_NAMES = ("l1", "mse", "esr", "dc", "mrstft", "log_mel_l1")      # losses whose d/dy_hat the TBPTT step can back-propagate
+GRAD_NAMES = ("l1", "mse", "esr", "dc", "mrstft", "log_mel_l1", "esr_pre")      # losses whose d/dy_hat the TBPTT step can back-propagate
 
 
 def effect_loss_grad(y_hat: T, y: T, weights: Dict[str, float], eps: float = 1e-8, mrstft=None, logmel=None,
-                     values: Optional[Dict[str, T]] = None) -> T:
+                     pre_emph=None, values: Optional[Dict[str, T]] = None) -> T:
     """d (sum_k weights[k] * loss_k(y_hat, y)) / d y_hat as a (B, T) tensor -- the backward half of
     ``calc_and_log_losses`` (lightning.py:33-62,380-382) for the effect model's output chunk.  ``mrstft``: a
     ``MultiResolutionSTFTLoss`` module to reuse (window / twiddle tables); ``logmel``: a ``losses.LogMelLoss`` module to
-    reuse (window, twiddle, filter bank and band tables on the device).  ``values``: a dict that receives the WEIGHTED
-    values (device scalars) the value-and-gradient kernels of mrstft / log_mel_l1 produce alongside their gradients."""
+    reuse (window, twiddle, filter bank and band tables on the device); ``pre_emph``: a ``losses.PreEmphESRLoss`` module to
+    reuse (taps on the device; its filter and eps are the ones ``esr_pre`` is taken with).  ``values``: a dict that receives
+    the WEIGHTED values (device scalars) the value-and-gradient kernels of mrstft / log_mel_l1 / esr_pre produce alongside
+    their gradients."""
     assert y_hat.shape == y.shape and y_hat.ndim == 3 and y_hat.size(1) == 1
     a, t = y_hat.detach()[:, 0, :], y.detach()[:, 0, :]
     assert a.stride(1) == 1 and t.stride(1) == 1
@@ -55,6 +57,14 @@ def effect_loss_grad(y_hat: T, y: T, weights: Dict[str, float], eps: float = 1e-
         value, dy = logmel_l1_value_and_grad(mod, a, t, scale=w["log_mel_l1"], dx=dy, accumulate=bool(acc))
         if values is not None:
             values["log_mel_l1"] = value
+        acc = 1
+    if "esr_pre" in w:
+        from .losses import PreEmphESRLoss, pre_emph_esr_value_and_grad
+        mod = pre_emph if pre_emph is not None else PreEmphESRLoss()
+        value, dy = pre_emph_esr_value_and_grad(mod, a, t, scale=w["esr_pre"], dx=dy, accumulate=bool(acc),
+                                                need_value=values is not None)
+        if values is not None:
+            values["esr_pre"] = value
         acc = 1
     if dy is None:
         dy = torch.empty((B, Tn), device=a.device, dtype=torch.float32)

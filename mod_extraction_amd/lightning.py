@@ -94,14 +94,29 @@ class BaseLightingModule(nn.Module):
         dict: these modules are no submodules and stay out of the state dict."""
         mod = self._extra_losses.get(name)
         if mod is None:
-            mod = self._extra_losses[name] = L.get_loss_func_by_name(name)
+            if name == "esr_pre":               # the step's own filter, not the defaults of get_loss_func_by_name
+                mod = L.PreEmphESRLoss(self.pre_emph_filter_cfs, self.pre_emph_low_pass)
+            else:
+                mod = L.get_loss_func_by_name(name)
+            self._extra_losses[name] = mod
         return mod
+
+    pre_emph_filter_cfs: Tuple[float, ...] = (-0.95, 1.0)        # the filter of "esr_pre" (Wright & Valimaki's pre-emphasis)
+    pre_emph_low_pass = False
+
+    def _set_pre_emph(self, filter_cfs: Sequence[float], low_pass: bool) -> None:
+        """The ``pre_emph_filter_cfs`` / ``pre_emph_low_pass`` arguments of the audio-loss steps: checked here, at
+        construction (ValueError for no tap or more than the kernels' 16), used by ``_loss_module("esr_pre")``."""
+        from .wright_code import PreEmphTaps
+        taps = PreEmphTaps(filter_cfs, low_pass)
+        self.pre_emph_filter_cfs, self.pre_emph_low_pass = taps.filter_cfs, taps.low_pass
 
     def _grad_modules(self):
         """The loss modules ``effect_loss_grad`` reuses, by the dict that names the step's audio losses."""
         names = getattr(self, "audio_loss_dict", self.loss_dict)
         return {"mrstft": self._loss_module("mrstft") if "mrstft" in names else None,
-                "logmel": self._loss_module("log_mel_l1") if "log_mel_l1" in names else None}
+                "logmel": self._loss_module("log_mel_l1") if "log_mel_l1" in names else None,
+                "pre_emph": self._loss_module("esr_pre") if "esr_pre" in names else None}
 
 
 class LFOExtraction(BaseLightingModule):
@@ -256,6 +271,8 @@ class LFOExtractionThroughEffect(BaseLightingModule):
       ``mix`` (its ``rate_hz`` and ``lead`` are ignored: the LFO is the extractor's)
       (``check_fx_params``: range-check them on every step, which costs host synchronisations).
     * ``audio_loss_dict``: names from ``effect_losses.GRAD_NAMES``; zero-weight names are only logged.
+    * ``pre_emph_filter_cfs`` / ``pre_emph_low_pass``: the filter of the "esr_pre" loss (``losses.PreEmphESRLoss``; 1 .. 16
+      taps), ignored without that name.
     * ``loss_dict`` (optional, default none): an LFO-domain term (lightning.py:33-62) added to the loss when the batch carries
       ``mod_sig``; it is logged as ``{prefix}/lfo_{name}``.
     The LFO enters the effect at the extractor's own rate (n_frames points, resampled in-kernel exactly as the data path
@@ -293,8 +310,11 @@ class LFOExtractionThroughEffect(BaseLightingModule):
                  check_fx_params: bool = False,
                  effect: Union[str, Sequence[str]] = "flanger",
                  chorus_max_min_delay_ms: Optional[float] = None,
-                 chorus_max_lfo_delay_ms: Optional[float] = None) -> None:
+                 chorus_max_lfo_delay_ms: Optional[float] = None,
+                 pre_emph_filter_cfs: Sequence[float] = (-0.95, 1.0),
+                 pre_emph_low_pass: bool = False) -> None:
         super().__init__({} if loss_dict is None else loss_dict)
+        self._set_pre_emph(pre_emph_filter_cfs, pre_emph_low_pass)
         from . import fx
         from .effect_losses import GRAD_NAMES
         if should_stretch:
@@ -578,7 +598,11 @@ class TBPTTLFOEffectModeling(BaseLightingModule):
     1024-sample chunk).  ``automatic_optimization`` is False like in the reference: ``training_step``
     receives the optimizer and runs the 83 inner steps itself; under DDP every inner step is one
     all-reduce of the 70 KB flat gradient, and a rank without any valid LFO still takes part with
-    zero gradients (the reference would return None there and dead-lock DDP)."""
+    zero gradients (the reference would return None there and dead-lock DDP).
+
+    ``pre_emph_filter_cfs`` / ``pre_emph_low_pass``: the filter of the "esr_pre" loss (``losses.PreEmphESRLoss``; 1 .. 16
+    taps).  Every chunk's gradient filters that chunk with its own zero history, which is what ``WrightPreEmph`` does per
+    call; the logged ``{prefix}/esr_pre`` is taken over the whole clip after the warm-up, like every other term."""
     default_loss_dict = {"l1": 1.0, "esr": 0.0, "dc": 0.0}
 
     def __init__(self,
@@ -596,8 +620,11 @@ class TBPTTLFOEffectModeling(BaseLightingModule):
                  max_n_corners: int = 16,
                  stretch_smooth_n_frames: int = 0,
                  discard_invalid_lfos: bool = True,
-                 loss_dict: Optional[Dict[str, float]] = None) -> None:
+                 loss_dict: Optional[Dict[str, float]] = None,
+                 pre_emph_filter_cfs: Sequence[float] = (-0.95, 1.0),
+                 pre_emph_low_pass: bool = False) -> None:
         super().__init__(loss_dict)
+        self._set_pre_emph(pre_emph_filter_cfs, pre_emph_low_pass)
         assert warmup_n_samples > 0
         # param_model (lightning.py:344-347,371-375): any nn.Module wet (B, C, n) -> (B, P); its output is repeated over time and
         # concatenated to the LFO as extra latent channels (the effect model then has latent_dim = 1 + P, i.e. the general LSTM

@@ -151,6 +151,65 @@ class LogMelLoss(nn.Module):
         return logmel_l1_value_and_grad(self, a, t, need_grad=False)[0]
 
 
+def pre_emph_esr_value_and_grad(mod: "PreEmphESRLoss", a: T, t: T, need_grad: bool = True, scale: float = 1.0,
+                                dx: Optional[T] = None, accumulate: bool = False,
+                                need_value: bool = True) -> Tuple[Optional[T], Optional[T]]:
+    """a (prediction), t (target): (rows, T) with unit inner stride.  Returns (scale * loss as a device scalar,
+    d (scale * loss) / d a or None) from ONE launch: ``mx_pre_emph_esr_grad`` (value and gradient) or, without a gradient,
+    ``mx_pre_emph_esr_sums``.  ``dx``: a (rows, T) float32 tensor with unit inner stride to write the gradient into
+    (``accumulate``: add it onto what ``dx`` holds) instead of a fresh one.  ``need_value=False``: the value (a few small
+    torch kernels on the per-clip sums) is not formed and None is returned in its place -- a TBPTT step that only
+    back-propagates launches the gradient kernel alone."""
+    assert a.shape == t.shape and a.ndim == 2 and a.stride(1) == 1 and t.stride(1) == 1
+    assert a.dtype == torch.float32 and t.dtype == torch.float32
+    if not a.is_cuda:
+        raise _hip.HipLibraryError("mod_extraction_amd ops need tensors on a HIP device (no CPU fallback)")
+    B, Tn = a.shape
+    taps = mod.taps
+    if taps.out_len(Tn) <= 0:
+        raise ValueError(f"esr_pre with low_pass needs more than 1 sample, got {Tn}")
+    part = torch.empty((B, 2), device=a.device, dtype=torch.float32)
+    head = (a.data_ptr(), a.stride(0), t.data_ptr(), t.stride(0), B, Tn, _hip.ptr(taps.on(a.device)),
+            len(taps.filter_cfs), int(taps.low_pass))
+    if need_grad:
+        if dx is None:
+            dx = torch.empty((B, Tn), device=a.device, dtype=torch.float32)
+            accumulate = False
+        assert dx.shape == (B, Tn) and dx.stride(1) == 1 and dx.dtype == torch.float32
+        _hip.call("mx_pre_emph_esr_grad", *head, float(scale), float(mod.eps), int(bool(accumulate)), _hip.ptr(part),
+                  dx.data_ptr(), dx.stride(0), _hip.stream())
+    else:
+        dx = None
+        _hip.call("mx_pre_emph_esr_sums", *head, _hip.ptr(part), _hip.stream())
+    if not need_value:
+        return None, dx
+    value = (part[:, 0] / (part[:, 1] + mod.eps)).mean()                     # losses.py:34-38 on the filtered pair
+    return (value if scale == 1.0 else scale * value), dx
+
+
+class PreEmphESRLoss(nn.Module):
+    """``esr_pre``: the reference's ``ESRLoss`` (losses.py:14-38: per-clip ratio, mean over the clips, eps 1e-8) applied to
+    the outputs of ``WrightPreEmph(filter_cfs, low_pass)`` (wright_code.py:47-73), evaluated by ``mx_pre_emph_esr_sums``
+    without materialising the filtered signals.  The module owns the tap buffer on the device.  Like ``LogMelLoss`` the
+    gradient reaches training through ``effect_losses.effect_loss_grad`` (``pre_emph_esr_value_and_grad``), not autograd: a
+    prediction that requires grad raises instead of silently returning a constant."""
+
+    def __init__(self, filter_cfs=(-0.95, 1.0), low_pass: bool = False, eps: float = 1e-8) -> None:
+        super().__init__()
+        from .wright_code import PreEmphTaps
+        self.taps = PreEmphTaps(filter_cfs, low_pass)
+        self.eps = float(eps)
+
+    def forward(self, input: T, target: T) -> T:
+        if input.requires_grad and torch.is_grad_enabled():
+            raise NotImplementedError("esr_pre is forward-only on this path (evaluation metric)")
+        assert input.shape == target.shape and input.ndim == 3
+        n = input.size(-1)
+        a = input.detach().reshape(-1, n).contiguous().float()
+        t = target.detach().reshape(-1, n).contiguous().float()
+        return pre_emph_esr_value_and_grad(self, a, t, need_grad=False)[0]
+
+
 def apply_reduction(losses: T, reduction: str = "none") -> T:
     """losses.py:133-139."""
     if reduction == "mean":
@@ -177,5 +236,7 @@ def get_loss_func_by_name(name: str) -> nn.Module:
         return get_effect_loss(name)
     elif name == "log_mel_l1":
         return LogMelLoss()
+    elif name == "esr_pre":
+        return PreEmphESRLoss()
     else:
         raise KeyError
