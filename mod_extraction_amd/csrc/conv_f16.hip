@@ -32,7 +32,6 @@
 // gradients stay on the exact-fp32 kernels (conv2d.hip, wgrad.hip).
 #include "conv_common.h"
 #include <hip/hip_fp16.h>
-#include <cstdlib>
 
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 #define F16_WSCALE 256.0f
@@ -299,8 +298,7 @@ __device__ __forceinline__ void store_tile32(const floatx4 (&acc)[44], int i, fl
 __device__ __forceinline__ float acc_elem(const floatx16 (&acc)[CV_WT], int i, int r) { return acc[i][r]; }
 __device__ __forceinline__ float acc_elem(const floatx4 (&acc)[44], int, int) { return 0.0f; }      // (plain rows: 32x32 layout only)
 
-// HALF = tiles a wave finishes per exchange round (3: two rounds through 96 KB of LDS; 1: six rounds through 32 KB)
-template <int OUTMODE, typename ACC, int HALF = 3>
+template <int OUTMODE, typename ACC>
 __device__ __forceinline__ void conv_f16_epilogue(ACC &acc, const ConvF16Args &a, unsigned char *smem,
                                                   int b, int h0, int row, int c, int lane)
 {
@@ -353,6 +351,7 @@ __device__ __forceinline__ void conv_f16_epilogue(ACC &acc, const ConvF16Args &a
                 st_q[j][q] = 0.0f;
             }
         __syncthreads();                                                // the K loop's LDS images are dead
+        constexpr int HALF = 3;                                         // tiles a wave finishes per exchange round: two rounds through 96 KB of LDS
         constexpr int ROUNDS = 6 / HALF, SLOTS = 2 * HALF;
 #pragma unroll
         for (int round = 0; round < ROUNDS; ++round) {
@@ -626,11 +625,11 @@ __device__ __forceinline__ void glds16(unsigned long long gsrc, unsigned lds_wav
 }
 #define DMA_WAIT() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
 
-// NCB x NKH = K stages: 4 channel blocks x 5 kernel rows for the 64-channel blocks; 1 x 1 for the first block, whose
-// operand already carries (kernel row, input channel) as its 16 "channels" (mx_conv_prep_fwd_kvec_f16).
-template <int T, int OUTMODE, int NCB = 4, int NKH = CV_KH>
+// Launched as the dense data gradient (plain rows * 1/S); the forward runs on conv_f16x3_dma16_kernel below.
+template <int T>
 __global__ __launch_bounds__(256, 1) void conv_f16x3_dma_kernel(ConvF16Args a)
 {
+    constexpr int NCB = 4, NKH = CV_KH;               // K stages: 4 channel blocks x 5 kernel rows
     constexpr int PWP = CV_PITCH + 12 * T;            // patch positions per row (w = q - 6T)
     constexpr int WSL = CV_KW * 64 * 16;              // halfs per packed weight stage and split
     constexpr int PLANE = PWP * 16;                   // bytes of one (split, row, khalf) plane
@@ -823,446 +822,27 @@ __global__ __launch_bounds__(256, 1) void conv_f16x3_dma_kernel(ConvF16Args a)
 #undef DMA_SLOT_B2
 #undef DMA_NB
     }
-    conv_f16_epilogue<OUTMODE>(acc, a, smem, b, h0, row, c, lane);
+    conv_f16_epilogue<1>(acc, a, smem, b, h0, row, c, lane);
 }
 
-// Epilogue of the first block's "pair-wave" layout: wave = (channel tile jt, column half c) holds BOTH rows of the pooling
-// pair -- acc[2t + r], t < 5: column tile c*6 + t, row r; acc[10]: column tile 5, row c -- so the max over the pair is taken
-// in registers and only the pooled tile (with its 16 argmax bits per lane packed into one word) goes through LDS for the
-// transposition to 16-byte stores, in a region private to the wave: 17 LDS writes + 5 reads per pooled tile instead of
-// 32 + 8, and no workgroup barrier.  Only the middle column tile, whose two rows sit in two waves, is exchanged: each of
-// the two waves finishes 16 of its 32 channels.  scr: 4 waves x 4 352 B + 2 x 2 x 4 KB, inside the patch buffer the taps
-// are done with.
-#ifdef C1_DIAG           // diagnostic build (tools/exp_block1.py): cycle stamps of wave 0 summed over workgroups and row pairs
-__device__ unsigned long long c1_diag[8];
-struct C1Diag { unsigned long long prev, sum[8]; };
-#define C1_STAMP(i) do { const unsigned long long t_ = __builtin_readcyclecounter(); dg.sum[i] += t_ - dg.prev; dg.prev = t_; } while (0)
-#define C1_DIAG_PARAM , C1Diag &dg
-#define C1_DIAG_ARG , dg
-extern "C" __attribute__((visibility("default"))) int mx_diag_c1(unsigned long long *out, int reset)
-{
-    if (reset) { unsigned long long z[8] = {0}; return (int)hipMemcpyToSymbol(HIP_SYMBOL(c1_diag), z, sizeof z); }
-    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(c1_diag), 8 * sizeof(unsigned long long));
-}
-#else
-#define C1_STAMP(i) do { } while (0)
-#define C1_DIAG_PARAM
-#define C1_DIAG_ARG
-#endif
-struct PairwaveConsts { float bias[4], slope[4], nshift[4]; };       // of channel rows jt*32 + q*8 + (lane >> 3): loaded once per workgroup
-__device__ __forceinline__ PairwaveConsts pairwave_consts(const ConvF16Args &a, int jt, int lane)
-{
-    PairwaveConsts k;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        k.bias[q] = a.bias[jt * 32 + q * 8 + (lane >> 3)];
-        k.slope[q] = a.stats_part != nullptr ? a.slope_out[jt * 32 + q * 8 + (lane >> 3)] : 1.0f;
-        k.nshift[q] = -(k.bias[q] > 0.0f ? k.bias[q] : k.slope[q] * k.bias[q]);
-    }
-    return k;
-}
-__device__ __forceinline__ void conv1_pairwave_epilogue(floatx16 (&acc)[CV_WT], const ConvF16Args &a, const PairwaveConsts &kc,
-                                                        unsigned char *smem, int b, int h0, int jt, int c, int lane C1_DIAG_PARAM)
-{
-    const int l32 = lane & 31, wave = jt * 2 + c;
-    const float inv = 1.0f / F16_WSCALE;
-    const int hp = h0 >> 1, Hp = a.H >> 1;
-    const int co_l = lane >> 3, w4 = (lane & 7) * 4;                    // transposed role of the lane inside a tile
-    const int rbit0 = co_l & 3, fhalf = (co_l >> 2) & 1;               // co row q*8 + co_l = register q*4 + rbit0 of lane half fhalf
-    float *const img = reinterpret_cast<float *>(smem + wave * 4352);
-    unsigned *const flg = reinterpret_cast<unsigned *>(smem + wave * 4352 + 4096);
-    float *const mid = reinterpret_cast<float *>(smem + 4 * 4352);     // [jt][row][32 co][32 w]
-    const bool want_stats = a.stats_part != nullptr;                   // workgroup-uniform
-    // One wave per SIMD: the vector unit issues ~one instruction per 5 cycles, and this epilogue was as long as the 429
-    // matrix instructions before it (ablation, tools/exp_block1.py: 1.09 of 2.05 ms with the MFMAs removed, the same with its
-    // global stores removed too).  So the arithmetic is written on 4-vectors (packed fp32 instructions: x * 2^-k + bias is
-    // ONE rounding either way, the multiplication being exact), the pad-column masks exist only for the column tiles that
-    // reach past Wv (wave-uniform test), and a store's address is a scalar base + one 32-bit lane offset per channel row.
-    floatx4 st_s[4], st_q[4];
-    unsigned voff[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        st_s[q] = floatx4{0.0f, 0.0f, 0.0f, 0.0f};
-        st_q[q] = floatx4{0.0f, 0.0f, 0.0f, 0.0f};
-        voff[q] = (unsigned)((q * 8 + co_l) * Hp * CV_PITCH + w4);
-    }
-    const size_t sbase = (((size_t)b * CV_CO + jt * 32) * Hp + hp) * CV_PITCH;       // wave-uniform
-    float *const out_b = a.out + sbase;
-    unsigned char *const amax_b = a.out_amax + sbase;
-    __syncthreads();                                                    // every wave is done with the patch (and the next one is visible)
-    C1_STAMP(4);
-    store_tile32(acc, 10, mid + (jt * 2 + c) * 1024, lane);             // this wave's row of the middle tile
-    // one pooled tile: values tv (already the maximum of the pair), argmax bits in fl[e] bit (q*4 + rbit0)
-    auto finish = [&](int wt, int q, const floatx4 &tv, const uint4 &flw) {
-        const int w = wt * 32 + w4;
-        const unsigned fl[4] = {flw.x, flw.y, flw.z, flw.w};
-        const floatx4 invv = {inv, inv, inv, inv}, bv4 = {kc.bias[q], kc.bias[q], kc.bias[q], kc.bias[q]};
-        floatx4 m = __builtin_elementwise_fma(tv, invv, bv4);
-        unsigned am = 0;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) am |= ((fl[e] >> (q * 4 + rbit0)) & 1u) << (8 * e);
-        const floatx4 slv = {kc.slope[q], kc.slope[q], kc.slope[q], kc.slope[q]};
-        const floatx4 shv = {kc.nshift[q], kc.nshift[q], kc.nshift[q], kc.nshift[q]};
-        const bool partial = wt * 32 + 32 > a.Wv;                       // wave-uniform: pad columns inside this tile
-        if (partial) {
-            asm volatile("" ::: "memory");                              // a real branch (if-converted it costs 16 selects per call)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) m[e] = w + e < a.Wv ? m[e] : 0.0f;
-        }
-        const floatx4 sm = m * slv;
-        floatx4 dlt;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) dlt[e] = m[e] > 0.0f ? m[e] : sm[e];
-        dlt = dlt + shv;
-        if (partial) {
-            asm volatile("" ::: "memory");
-#pragma unroll
-            for (int e = 0; e < 4; ++e) dlt[e] = w + e < a.Wv ? dlt[e] : 0.0f;   // pad columns add nothing
-        }
-        st_s[q] += dlt;
-        st_q[q] += dlt * dlt;
-#if defined(C1_ABL) && (C1_ABL & 4)
-        if (m[0] + m[1] + m[2] + m[3] != 12345.0f && am != 77u) return;
-#endif
-        *reinterpret_cast<floatx4 *>(out_b + (voff[q] + (unsigned)(wt * 32))) = m;
-        *reinterpret_cast<unsigned *>(amax_b + (voff[q] + (unsigned)(wt * 32))) = am;
-    };
-#pragma unroll
-    for (int t = 0; t < 5; ++t) {
-        unsigned flags = 0;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const bool take_bot = acc[2 * t + 1][r] > acc[2 * t][r];     // ties keep the first row (torch)
-            img[mfma_row(r, lane) * 32 + l32] = take_bot ? acc[2 * t + 1][r] : acc[2 * t][r];
-            flags |= (take_bot ? 1u : 0u) << r;
-        }
-        flg[lane] = flags;
-        // the wave's own LDS operations execute in order: no barrier between its writes and its reads (compiler fences only)
-        asm volatile("" ::: "memory");
-#ifdef C1_DIAG2
-        C1_STAMP(5);                                                    // pooling + LDS writes (and their completion)
-#endif
-        const uint4 flw = *reinterpret_cast<const uint4 *>(flg + fhalf * 32 + w4);
-        floatx4 tvq[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) tvq[q] = *reinterpret_cast<const floatx4 *>(img + (q * 8 + co_l) * 32 + w4);
-#ifdef C1_DIAG2
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        C1_STAMP(6);                                                    // LDS reads
-#endif
-#pragma unroll
-        for (int q = 0; q < 4; ++q) finish(c * 6 + t, q, tvq[q], flw);
-        asm volatile("" ::: "memory");
-#ifdef C1_DIAG2
-        C1_STAMP(7);                                                    // arithmetic + stores
-#endif
-    }
-#ifndef C1_DIAG2
-    C1_STAMP(5);
-#endif
-    __syncthreads();                                                    // both rows of the middle tile are in LDS
-#ifndef C1_DIAG2
-    C1_STAMP(6);
-#endif
-    {
-        const float *top = mid + (jt * 2 + 0) * 1024, *bot = mid + (jt * 2 + 1) * 1024;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            if ((q >> 1) != c) continue;                                // wave c finishes channel rows 16 c .. 16 c + 15 of the tile (q stays a constant)
-            const floatx4 tv = *reinterpret_cast<const floatx4 *>(top + (q * 8 + co_l) * 32 + w4);
-            const floatx4 bv = *reinterpret_cast<const floatx4 *>(bot + (q * 8 + co_l) * 32 + w4);
-            floatx4 mv;
-            unsigned fl[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const bool take_bot = bv[e] > tv[e];
-                mv[e] = take_bot ? bv[e] : tv[e];
-                fl[e] = (take_bot ? 1u : 0u) << (q * 4 + rbit0);
-            }
-            finish(5, q, mv, uint4{fl[0], fl[1], fl[2], fl[3]});
-        }
-    }
-#ifndef C1_DIAG2
-    C1_STAMP(7);
-#endif
-    if (want_stats) {
-        // [wave][q][lane] partial sums -> thread co < 64 adds the 2 waves x 8 column lanes of its channel in a fixed order
-        float *xch = reinterpret_cast<float *>(smem + 4 * 4352 + 4 * 4096);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            xch[(wave * 4 + q) * 64 + lane] = (st_s[q][0] + st_s[q][1]) + (st_s[q][2] + st_s[q][3]);
-            xch[1024 + (wave * 4 + q) * 64 + lane] = (st_q[q][0] + st_q[q][1]) + (st_q[q][2] + st_q[q][3]);
-        }
-        __syncthreads();
-        const int co = threadIdx.x;
-        if (co < CV_CO) {
-            const int cjt = co >> 5, q = (co >> 3) & 3, col = co & 7;
-            float s1 = 0.0f, s2 = 0.0f;
-#pragma unroll
-            for (int cc = 0; cc < 2; ++cc)
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    s1 += xch[((cjt * 2 + cc) * 4 + q) * 64 + col * 8 + e];
-                    s2 += xch[1024 + ((cjt * 2 + cc) * 4 + q) * 64 + col * 8 + e];
-                }
-            float *sp = a.stats_part + (((size_t)b * Hp + hp) * CV_CO + co) * 2;
-            sp[0] = s1;
-            sp[1] = s2;
-        }
-    }
-}
-
-// ---- first block, persistent (2 input channels as a k-vector operand: ONE K stage of 13 taps per output row pair) --------
-// On conv_f16x3_dma_kernel<1, 0, 1, 1> a workgroup's life was: fetch weights + patch (nothing to overlap with), 13 taps of
-// matrix work, an epilogue that stores 112 KB -- strictly one after the other, one workgroup per CU (LDS): 36 us per row pair
-// for 8 us of matrix work.  Here a workgroup keeps the block's 53 KB of weights in LDS and walks a contiguous range of row
-// pairs: the next row pair's patch arrives by LDS-DMA during the taps, the pooled rows of the previous one are still
-// draining to memory meanwhile, and the max-pool exchange runs through the patch buffer the taps have just finished with
-// (six rounds of 32 KB).  Measured: 2.31 -> 2.15 ms per 256 clips x 256 mel bins (17 -> 16.5 us per row pair), i.e. the fetch
-// was NOT what the row pair waited for.  Cycle stamps (C1_DIAG build, tools/exp_block1.py) per row pair and wave: 15.0 k
-// cycles of taps (429 MFMAs = 13.7 k), no wait for the next patch, 14.4 k of epilogue -- and the two simply add, one wave
-// per SIMD has nothing to overlap them with.  Inside the epilogue: pooling + LDS writes 3.5 k, waiting for the LDS reads
-// 0.5 k, arithmetic + stores 6.7 k, middle tile + statistics + barriers 3.7 k: a lone wave issues one vector instruction
-// per ~7 cycles (dependent chains), whatever the instruction.  What does NOT help (all measured, same box): half the LDS
-// traffic and 5 instead of 12 barriers (the pair-wave layout below: 2.07 -> 2.02 ms), half the vector instructions
-// (packed fp32, masks only on the tile that has pad columns: no change), no global stores at all (no change: they are free),
-// no transposition but dword + byte stores straight from the accumulator layout (2.15 ms: slower), staggered workgroups
-// (no change).  With the MFMAs removed the kernel runs at the HBM floor (1.1 ms).  What would: the epilogue's vector work
-// under the NEXT row pair's matrix instructions in the SAME wave (pooled values carried in 94 registers: projected ~1.35 ms)
-// -- not built.  Two waves per SIMD at half the wave tile were built twice, parity-green, and are not faster: (a) half-row
-// workgroups of 256 registers / 78 KB, two per CU: 1.95-2.05 ms -- the two run IN phase (a start offset changes nothing) and
-// the single patch buffer that fits leaves every fetch exposed (11 k cycles per half row pair); (b) one 512-thread workgroup,
-// weights once, two wave groups half a period apart by construction (equal barrier counts in the tap and the epilogue
-// phase bodies): 5.1 ms, although its taps alone take 1.31 ms and its epilogue alone 1.09 ms -- the phase barrier makes the
-// tap group wait for the other group's store drain (vmcnt counts stores with the LDS-DMA loads) and its 78 spilled
-// registers; both removed again.
-// Floors at these sizes: 5.2 GB at ~4.7 TB/s = 1.1 ms, 1.8 PFLOP at 1.7 GHz = 1.0 ms.
-//   LDS = W (13 taps x 2 splits: 52 KB) | P[2] (46 KB each)
-// PW (pair-wave): wave = (channel tile, column half) with both rows of the pooling pair (conv1_pairwave_epilogue); a tap
-// then reads 2 weight + 22 patch fragments instead of 4 + 12.
-#ifndef C1_ABL
-#define C1_ABL 0        // ablation knobs (wrong results; tools/exp_block1.py): 1 no epilogue, 2 no MFMAs, 4 no global stores, 8 no DMA in the loop
-#endif
-template <int PWM>       // 0: wave = (row, column half), rows exchanged through LDS; 1: pair-wave (conv1_pairwave_epilogue)
-__global__ __launch_bounds__(256, 1) void conv1_f16x3_persist_kernel(ConvF16Args a, int n_tiles, int tiles_per_wg)
-{
-    constexpr bool PW = PWM != 0;
-    constexpr int T = 1;
-    constexpr int PWP = CV_PITCH + 12 * T;
-    constexpr int PLANE = PWP * 16;
-    constexpr int P_SLOTS = 8 * PWP;
-    constexpr int P_PIECES = (P_SLOTS + 63) / 64;
-    constexpr int P_BYTES = P_PIECES * 1024;
-    constexpr int PPW = (P_PIECES + 3) / 4;                      // 12
-    constexpr int W_SPLIT = CV_KW * 2048, W_BYTES = 2 * W_SPLIT;
-    constexpr int ROWB = CV_PITCH * 32;
-    static_assert(PPW == 12, "DMA schedule");
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    unsigned char *const Wl = smem, *const P0 = smem + W_BYTES;
-    const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char *)smem;
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int row = wave >> 1, c = wave & 1, half = lane >> 5, l32 = lane & 31;
-    // XCD-contiguous ranges of row pairs (workgroups go to the 8 XCDs round-robin in launch order)
-    int wg = blockIdx.x;
-    if ((gridDim.x & 7) == 0) wg = (wg & 7) * (gridDim.x >> 3) + (wg >> 3);
-    const int t_begin = wg * tiles_per_wg, t_end = min(t_begin + tiles_per_wg, n_tiles);
-    if (t_begin >= t_end) return;
-    const int Hp = a.H >> 1, H = a.H;
-    int desc[PPW];
-#pragma unroll
-    for (int k = 0; k < PPW; ++k) {
-        const int i = (wave + 4 * k) * 64 + lane;
-        const int plane = i / PWP, pos = i - plane * PWP, w = pos - 6 * T;
-        const int split = plane >> 2, r = (plane >> 1) & 1, part = plane & 1;
-        desc[k] = (i < P_SLOTS && w >= 0 && w < CV_PITCH) ? ((split << 30) | (r << 29) | (r * ROWB + w * 32 + part * 16)) : -1;
-    }
-    const unsigned long long zero_src = (unsigned long long)k_zero_slot, xh = (unsigned long long)a.x_hi,
-                             xl = (unsigned long long)a.x_lo, wh = (unsigned long long)a.w_hi, wlo = (unsigned long long)a.w_lo;
-    struct DmaSlot { unsigned long long src; unsigned lds; };
-    // patch piece k of row pair `tile` -> patch buffer pb (the operand row h carries its five kernel rows as channels: no halo rows)
-    auto slot_p = [&](int tile, int pb, int k) {
-        const bool in_range = wave + 4 * k < P_PIECES;
-        const int pp = in_range ? wave + 4 * k : wave + 4 * (k - 1);
-        const int d = in_range ? desc[k] : desc[k > 0 ? k - 1 : 0];
-        const int tb = tile / Hp, th0 = (tile - tb * Hp) * 2;
-        const long long st_off = ((long long)tb * H + th0) * (CV_PITCH * 32);
-        const bool ok = d >= 0;                                   // both rows of a pair are inside the image (H is even)
-        const unsigned long long src = ((d & (1 << 30)) ? xl : xh) + st_off + (unsigned)(d & 0xFFFFF);
-        DmaSlot r;
-        r.src = ok ? src : zero_src;
-        r.lds = lds0 + W_BYTES + pb * P_BYTES + pp * 1024;
-        return r;
-    };
-    auto slot_issue = [&](const DmaSlot &d) { glds16(d.src, d.lds); };
-
-    // prologue: all 13 taps of the weights (52 pieces: 13 per wave), the first row pair's patch
-#pragma unroll
-    for (int j = 0; j < CV_KW; ++j) {
-        const int pw = wave + 4 * j, split = pw / (2 * CV_KW), rem = pw - split * (2 * CV_KW);
-        glds16((split ? wlo : wh) + ((unsigned long long)rem * 512 + lane * 8) * 2, lds0 + split * W_SPLIT + rem * 1024);
-    }
-#pragma unroll
-    for (int k = 0; k < PPW; ++k)
-        if (wave + 4 * k < P_PIECES) slot_issue(slot_p(t_begin, 0, k));
-    DMA_WAIT();
-    __syncthreads();
-
-    PairwaveConsts kc;
-    if (PWM == 1) kc = pairwave_consts(a, row, lane);
-#ifdef C1_DIAG
-    C1Diag dg;
-    dg.prev = __builtin_readcyclecounter();
-    for (int i = 0; i < 8; ++i) dg.sum[i] = 0;
-#endif
-#pragma unroll 1
-    for (int tile = t_begin; tile < t_end; ++tile) {
-        C1_STAMP(0);                                            // loop overhead + the barrier at the end of the previous row pair
-        const int pb = (tile - t_begin) & 1;
-        unsigned char *const Pc = P0 + pb * P_BYTES;
-        const int tn = tile + 1 < t_end ? tile + 1 : tile;       // the row pair whose patch the DMA slots fetch (last: a harmless repeat)
-        const int b = tile / Hp, h0 = (tile - b * Hp) * 2;
-        floatx16 acc[CV_WT];
-#pragma unroll
-        for (int i = 0; i < CV_WT; ++i)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][r] = 0.0f;
-        const unsigned char *b_p = Pc + (row * 2 + half) * PLANE + (c * 6 * 32 + l32) * 16;
-        const unsigned char *bm_p = Pc + (row * 2 + half) * PLANE + (5 * 32 + l32) * 16;
-        // pair-wave: row (= wave >> 1) is the channel tile; patch rows r = 0, 1 at b_q + r * 2 * PLANE
-        const unsigned char *b_q = Pc + half * PLANE + (c * 6 * 32 + l32) * 16;
-        const unsigned char *bm_q = Pc + (c * 2 + half) * PLANE + (5 * 32 + l32) * 16;
-        constexpr int NFA = PW ? 2 : 4, NFB = PW ? 11 : 6, NRD = NFA + 2 * NFB;
-        half8 FA[2][NFA], FBH[2][NFB], FBL[2][NFB];
-        auto rd = [&](int f, int kw, int r) {
-            if (PW) {
-                if (r < 2) {
-                    FA[f][r] = *reinterpret_cast<const half8 *>(Wl + r * W_SPLIT + (kw * 2 + half) * 1024 + (row * 32 + l32) * 16);
-                } else {
-                    const int u = (r - 2) >> 1, lo = (r - 2) & 1;
-                    const unsigned char *p = (u < 10 ? b_q + (u & 1) * 2 * PLANE + (u >> 1) * 32 * 16 : bm_q) + lo * 4 * PLANE + kw * T * 16;
-                    if (lo) FBL[f][u] = *reinterpret_cast<const half8 *>(p);
-                    else FBH[f][u] = *reinterpret_cast<const half8 *>(p);
-                }
-            } else if (r < 4) {
-                const int ch = (r >> 1) ? (c ^ 1) : c;
-                FA[f][r] = *reinterpret_cast<const half8 *>(Wl + (r & 1) * W_SPLIT + (kw * 2 + half) * 1024 + (ch * 32 + l32) * 16);
-            } else {
-                const int tl = (r - 4) >> 1, lo = (r - 4) & 1;
-                const unsigned char *p = (tl < 5 ? b_p + tl * 32 * 16 : bm_p) + lo * 4 * PLANE + kw * T * 16;
-                if (lo) FBL[f][tl] = *reinterpret_cast<const half8 *>(p);
-                else FBH[f][tl] = *reinterpret_cast<const half8 *>(p);
-            }
-        };
-        auto mma = [&](int f, int i) {
-            const int term = i / 11, u = i - term * 11;
-            if (C1_ABL & 2) {
-                if (i == 0) acc[0][0] += (float)FA[f][0][0] + (float)FBH[f][0][0];       // keep the reads alive
-            } else if (PW) {
-                acc[u] = mfma16(FA[f][term == 0 ? 1 : 0], term == 1 ? FBL[f][u] : FBH[f][u], acc[u]);
-            } else {
-                const int tl = u < 10 ? (u >> 1) : 5, j = u < 10 ? (u & 1) : 0;
-                const half8 av = FA[f][2 * j + (term == 0 ? 1 : 0)];
-                const half8 bv = term == 1 ? FBL[f][tl] : FBH[f][tl];
-                acc[u] = mfma16(av, bv, acc[u]);
-            }
-        };
-        // reads of a tap's fragments behind the previous tap's MFMAs: R1 in the first segment (16 MFMAs), the rest in the second (17)
-        constexpr int R1 = PW ? 12 : 8;
-#pragma unroll
-        for (int r = 0; r < NRD; ++r) rd(0, 0, r);
-#pragma unroll
-        for (int t = 0; t < CV_KW; ++t) {
-            // one tap: 33 MFMAs on fragment set t & 1, the next tap's reads into the other set and -- taps 0..5 -- two DMA
-            // pieces of the next row pair's patch
-            const int f = t & 1;
-            __builtin_amdgcn_sched_barrier(0);
-            const DmaSlot sa = slot_p(tn, pb ^ 1, t < 6 ? 2 * t : 0), sb = slot_p(tn, pb ^ 1, t < 6 ? 2 * t + 1 : 0);
-#pragma unroll
-            for (int i = 0; i < 16; ++i) mma(f, i);
-            if (t + 1 < CV_KW) {
-#pragma unroll
-                for (int r = 0; r < R1; ++r) rd(f ^ 1, t + 1, r);
-                if (PW) {
-#pragma unroll
-                    for (int g = 0; g < 12; ++g) {
-                        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-                    }
-                    __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
-                } else {
-#pragma unroll
-                    for (int g = 0; g < 8; ++g) {
-                        __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
-                        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-                    }
-                }
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            if (t < 6 && !(C1_ABL & 8)) slot_issue(sa);
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int i = 16; i < 33; ++i) mma(f, i);
-            if (t + 1 < CV_KW) {
-#pragma unroll
-                for (int r = R1; r < NRD; ++r) rd(f ^ 1, t + 1, r);
-                if (PW) {
-#pragma unroll
-                    for (int g = 0; g < 12; ++g) {
-                        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-                    }
-                    __builtin_amdgcn_sched_group_barrier(0x008, 5, 0);
-                } else {
-#pragma unroll
-                    for (int g = 0; g < 8; ++g) {
-                        __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
-                        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-                    }
-                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                }
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            if (t < 6 && !(C1_ABL & 8)) slot_issue(sb);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        // the next patch has landed (its pieces were issued seven taps ago; the previous row pair's stores have retired long
-        // since) BEFORE this row pair's stores are issued: a wait behind them would expose their latency
-        C1_STAMP(1);                                            // the 13 taps
-        DMA_WAIT();
-        C1_STAMP(2);                                            // waiting for the next patch
-        // bias + max-pool + argmax (+ LayerNorm partial sums) through the patch buffer the taps are done with; the barrier at
-        // its head also publishes the next patch
-        if (C1_ABL & 1) {
-            if (acc[0][0] + acc[3][5] + acc[7][2] + acc[10][9] == 12345.0f) a.out[tile] = 1.0f;
-            __syncthreads();
-        } else if (PWM == 1) conv1_pairwave_epilogue(acc, a, kc, Pc, b, h0, row, c, lane C1_DIAG_ARG);
-        else conv_f16_epilogue<0, floatx16[CV_WT], 1>(acc, a, Pc, b, h0, row, c, lane);
-        C1_STAMP(3);                                            // the epilogue
-        __syncthreads();                                        // the exchange images are dead: the next DMA may overwrite them
-    }
-#ifdef C1_DIAG
-    if (threadIdx.x == 0)
-        for (int i = 0; i < 8; ++i) atomicAdd(&c1_diag[i], dg.sum[i]);
-#endif
-}
-
-// ---- first block, persistent, TILE-OUTER (round 5; MODEX_BLOCK1_PERSIST=3, the default) --------------------------------------
-// The kernel above keeps all 176 accumulator registers of a row pair alive through its 13 taps and then runs a 14 k-cycle
-// epilogue that nothing overlaps: one wave per SIMD, taps and epilogue simply add (15.0 k + 14.4 k cycles per row pair).  The
+// ---- first block, persistent, TILE-OUTER (2 input channels as a k-vector operand: ONE K stage of 13 taps per output row pair) ----
+// A workgroup walks a contiguous range of row pairs; the next row pair's patch arrives by LDS-DMA during the current one's taps.
+// The row-pair-outer kernels this one replaced (retired) kept all 176 accumulator registers of a row pair alive
+// through its 13 taps and then ran a 14 k-cycle epilogue that nothing overlapped: one wave per SIMD, taps and epilogue simply
+// add (15.0 k + 14.4 k cycles per row pair).  The
 // first block is special: K = 13 taps x 16 "channels" only, so the WEIGHTS of a wave's 32 output channels fit in registers
 // (13 taps x {hi, lo} x 4 = 104) and the loops can be turned inside out:
 //   for each 32-column tile:  both rows of the pooling pair x 13 taps x 3 split products = 78 matrix instructions on TWO
 //   accumulators (32 registers), patch fragments straight from the LDS image (4 ds_read_b128 per tap, one tap ahead),
 // and the tile is DONE: its max-pool, transposition through the wave's private LDS image, bias, LayerNorm partial sums and
-// 16-byte stores (the pair-wave epilogue above, cut into pieces) run in the shadow of the matrix instructions of tile t + 1
+// 16-byte stores run, cut into pieces, in the shadow of the matrix instructions of tile t + 1
 // (two accumulator sets, ping-pong), with no workgroup barrier inside a row pair.
 // Waves = (channel tile jt, column half c); 352 columns = 11 tiles: c = 0 takes tiles 0..5, c = 1 tiles 5..10 -- tile 5 is
 // computed by both (bit-identical values, stored twice; its partial sums are counted once): 6 x 78 = 468 instead of 429 matrix
 // instructions per wave and row pair, in exchange for no cross-wave exchange of the middle tile.
 // (A first version with swapped operands -- a lane = one channel, 16-byte stores straight from the accumulators, no LDS at all
 //  -- was store-bound: 64 scattered 16-byte pieces per store instruction, 2.1 ms for the stores alone.)
-//   LDS = P[2] (46 KB each: the row pair's patch, LDS-DMA double buffered as above) | 4 transposition images (17 KB) | sums (8 KB) | DMA descriptors (12 KB)
+//   LDS = P[2] (46 KB each: the row pair's patch, LDS-DMA double buffered) | 4 transposition images (17 KB) | sums (8 KB) | DMA descriptors (12 KB)
 // Measured (one box, 256 clips x 256 mel bins): 2.23 -> 2.06 ms inside the train step, 1.97 -> 1.92 ms alone.  Ablations (alone):
 // without the matrix instructions 1.18 ms, without the global stores 1.68 ms: ~2 500 vector / LDS / store instructions ride on 468
 // matrix instructions per row pair, and a lone wave issues one of them per ~7 cycles -- the wave is VECTOR-ISSUE bound (17.6 k
@@ -1271,8 +851,20 @@ __global__ __launch_bounds__(256, 1) void conv1_f16x3_persist_kernel(ConvF16Args
 // tile's epilogue under the next pair's first tile, sums exchanged one pair late): parity-green, 2.27 ms in the step -- the
 // accumulators carried around the loop cost 100 more AGPR copies than the exposed epilogue saved.
 #ifndef C1T_ABL
-#define C1T_ABL 0       // ablation knobs of the tile-outer kernel (wrong results; tools/exp_block1.py): 1 no epilogue, 2 no matrix instructions, 4 no global stores
+#define C1T_ABL 0       // ablation knobs of the tile-outer kernel (wrong results; tools/exp_block1.py): 1 no epilogue, 2 no matrix instructions, 4 no global stores, 8 no LDS-DMA in the loop
 #endif
+struct Conv1Consts { float bias[4], slope[4], nshift[4]; };          // of channel rows jt*32 + q*8 + (lane >> 3): loaded once per workgroup
+__device__ __forceinline__ Conv1Consts conv1_consts(const ConvF16Args &a, int jt, int lane)
+{
+    Conv1Consts k;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        k.bias[q] = a.bias[jt * 32 + q * 8 + (lane >> 3)];
+        k.slope[q] = a.stats_part != nullptr ? a.slope_out[jt * 32 + q * 8 + (lane >> 3)] : 1.0f;
+        k.nshift[q] = -(k.bias[q] > 0.0f ? k.bias[q] : k.slope[q] * k.bias[q]);
+    }
+    return k;
+}
 template <bool STATS>     // STATS: leave the next block's LayerNorm partial sums (stats_part / slope_out given); a template so that a tile's epilogue is branch-free
 __global__ __launch_bounds__(256, 1) void conv1_f16x3_tile_kernel(ConvF16Args a, int n_tiles, int tiles_per_wg)
 {
@@ -1335,8 +927,9 @@ __global__ __launch_bounds__(256, 1) void conv1_f16x3_tile_kernel(ConvF16Args a,
     // row pair's stores to retire (first version of this kernel: 2.7 ms)
 #pragma unroll
     for (int kw = 0; kw < CV_KW; ++kw) asm volatile("" : "+v"(WH[kw]), "+v"(WL[kw]));
-    // transposed role of the lane in the epilogue (conv1_pairwave_epilogue): 4 channel rows q*8 + co_l, 4 columns w4 .. w4 + 3
-    const PairwaveConsts kc = pairwave_consts(a, jt, lane);
+    // transposed role of the lane in the epilogue (a finished tile comes back from the wave's LDS image as [co][w]): 4 channel
+    // rows q*8 + co_l, 4 columns w4 .. w4 + 3
+    const Conv1Consts kc = conv1_consts(a, jt, lane);
     const int co_l = lane >> 3, w4 = (lane & 7) * 4, rbit0 = co_l & 3, fhalf = (co_l >> 2) & 1;
     float *const img = reinterpret_cast<float *>(scr + wave * 4352);
     unsigned *const flg = reinterpret_cast<unsigned *>(scr + wave * 4352 + 4096);
@@ -1460,7 +1053,7 @@ __global__ __launch_bounds__(256, 1) void conv1_f16x3_tile_kernel(ConvF16Args a,
                 }
                 // two DMA pieces of the next row pair's patch per tile (descriptor read from LDS a tap earlier)
                 if (t < NT && (kw == 3 || kw == 8)) dnext = desc_l[(2 * t + (kw == 8 ? 1 : 0)) * 256 + tid];
-                if (t < NT && (kw == 4 || kw == 9) && !(C1_ABL & 8)) issue_piece(tn, pb ^ 1, 2 * t + (kw == 9 ? 1 : 0), dnext);
+                if (t < NT && (kw == 4 || kw == 9) && !(C1T_ABL & 8)) issue_piece(tn, pb ^ 1, 2 * t + (kw == 9 ? 1 : 0), dnext);
                 if (t < NT) {
 #pragma unroll
                     for (int q_ = 0; q_ < 6; ++q_) {
@@ -1530,9 +1123,9 @@ __global__ __launch_bounds__(256, 1) void conv1_f16x3_tile_kernel(ConvF16Args a,
 //   fragments live in a RING of six tiles read four tiles ahead of their use (across pair boundaries), and only the 8 A
 //   fragments are double buffered: 12 + 16 fragment vectors (112 registers).
 #ifndef DMA16_ABL
-#define DMA16_ABL 0     // ablation knobs (wrong results): 1 = no LDS-DMA issue inside the loop, 2 = no barrier behind the straddling pair
+#define DMA16_ABL 0     // ablation knob (wrong results): 2 = no barrier behind the straddling pair
 #endif
-// RING: the patch lives in a ring of FOUR ROW SLOTS instead of two 2-row buffers.  Stage (cb, kh) reads input rows
+// The patch lives in a ring of FOUR ROW SLOTS (the first version: two 2-row buffers, P0 / P1 in the notes above).  Stage (cb, kh) reads input rows
 //   j = kh (for output row 0) and kh + 1 (output row 1) of the six rows j = 0..5 = h0 - 2 .. h0 + 3 of channel block cb;
 //   row number n = 6 cb + j lives in slot n & 3.  Consecutive kernel-row stages of a channel block share a row, so a stage
 //   fetches ONE new row for its successor (its row kh + 1), and a second one (row 0, in one burst behind the mid-stage
@@ -1542,12 +1135,10 @@ __global__ __launch_bounds__(256, 1) void conv1_f16x3_tile_kernel(ConvF16Args a,
 //   slots; the odd stage still issues its patch pieces only behind the barrier that follows the straddling pair.  The
 //   fragment bases become per-couple values (a dozen vector adds per 3 432 matrix instructions).
 //   Measured (one box, inside the train step): block 2 / 3 / 4 forward 12.24 -> 11.77 / 5.92 -> 5.72 / 2.96 -> 2.88 ms.
-#ifndef DMA16_PWP_PAD
-#define DMA16_PWP_PAD 1   // 0: the round-4 plane pitch (same-box A/B)
-#endif
-template <int T, bool RING>
+template <int T, bool RING>       // RING is always true: the kernel keeps the name the profiles and bench.py's roofline block know it by
 __global__ __launch_bounds__(256, 1) void conv_f16x3_dma16_kernel(ConvF16Args a)
 {
+    static_assert(RING, "the four-row ring is the only patch scheme");
     constexpr int NCB = 4, NKH = CV_KH;
     // Plane pitch of the patch images, in positions.  A B fragment of this kernel is read by lane groups (tap parity, k half): the
     // hardware serves a ds_read_b128 sixteen lanes at a time -- eight lanes of k half 0 and eight of k half 1 -- and with 352 + 12 T
@@ -1555,25 +1146,19 @@ __global__ __launch_bounds__(256, 1) void conv_f16x3_dma16_kernel(ConvF16Args a)
     // every patch-fragment read took twice its cycles (SQ_LDS_BANK_CONFLICT = 43 % of the kernel's LDS cycles at T = 1, 2 and 0.2 %
     // at T = 4, whose 6 400-byte planes are a multiple of 256: profiles/r05/pmc_b64_lds.txt).  Rounded up to a multiple of 16
     // positions every plane starts on bank 0 -- the extra positions are halo (zeros) and fit the same number of DMA pieces.
-    constexpr int PWP = DMA16_PWP_PAD ? (CV_PITCH + 12 * T + 15) / 16 * 16 : CV_PITCH + 12 * T;
+    constexpr int PWP = (CV_PITCH + 12 * T + 15) / 16 * 16;
     constexpr int WSL = CV_KW * 64 * 16;
     constexpr int PLANE = PWP * 16;
-    constexpr int P_SLOTS = 8 * PWP;
-    constexpr int P_PIECES = (P_SLOTS + 63) / 64;
-    constexpr int P_BYTES = P_PIECES * 1024;
-    constexpr int PPW = (P_PIECES + 3) / 4;
     constexpr int W_SPLIT = 7 * 2048, W_BYTES = 2 * W_SPLIT;
-    constexpr int ROWB = NCB * CV_PITCH * 32;
     constexpr int N_STAGE = NCB * NKH;
-    static_assert(PPW >= 12 && PPW <= 13 && N_STAGE % 2 == 0, "DMA schedule");
-    constexpr int R_PIECES = (4 * PWP + 63) / 64;                // RING: pieces of one patch row = 4 planes [split][khalf]
+    static_assert(N_STAGE % 2 == 0, "DMA schedule");
+    constexpr int R_PIECES = (4 * PWP + 63) / 64;                // pieces of one patch row = 4 planes [split][khalf]
     constexpr int SLOT_BYTES = R_PIECES * 1024;
     constexpr int RPW = (R_PIECES + 3) / 4;                      //       per wave
-    static_assert(RPW >= 6 && RPW <= 7, "DMA schedule (ring)");
-    constexpr int NDESC = RING ? RPW : PPW;
-    constexpr int SP_STRIDE = RING ? 2 * PLANE : 4 * PLANE;      // bytes between the hi and lo images of a patch row
+    static_assert(RPW >= 6 && RPW <= 7, "DMA schedule");
+    constexpr int SP_STRIDE = 2 * PLANE;                         // bytes between the hi and lo images of a patch row
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    constexpr int W0_OFF = 0, W1_OFF = W_BYTES, P0_OFF = 2 * W_BYTES, P1_OFF = 2 * W_BYTES + P_BYTES;
+    constexpr int W0_OFF = 0, W1_OFF = W_BYTES, P0_OFF = 2 * W_BYTES;
     const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char *)smem;
 
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1591,18 +1176,15 @@ __global__ __launch_bounds__(256, 1) void conv_f16x3_dma16_kernel(ConvF16Args a)
 #pragma unroll
         for (int r = 0; r < 4; ++r) acc[i][r] = 0.0f;
 
-    int desc[NDESC];
+    // patch piece descriptors of one row: bit 31 = no source (halo column / padding slot), bit 30 = split, low bits = byte offset
+    // of the slot's 16 bytes inside the operand row
+    int desc[RPW];
 #pragma unroll
-    for (int k = 0; k < NDESC; ++k) {
+    for (int k = 0; k < RPW; ++k) {
         const int i = (wave + 4 * k) * 64 + lane;
         const int plane = i / PWP, pos = i - plane * PWP, w = pos - 6 * T;
-        if (RING) {
-            const int split = plane >> 1, part = plane & 1;
-            desc[k] = (i < 4 * PWP && w >= 0 && w < CV_PITCH) ? ((split << 30) | (w * 32 + part * 16)) : -1;
-        } else {
-            const int split = plane >> 2, r = (plane >> 1) & 1, part = plane & 1;
-            desc[k] = (i < P_SLOTS && w >= 0 && w < CV_PITCH) ? ((split << 30) | (r << 29) | (r * ROWB + w * 32 + part * 16)) : -1;
-        }
+        const int split = plane >> 1, part = plane & 1;
+        desc[k] = (i < 4 * PWP && w >= 0 && w < CV_PITCH) ? ((split << 30) | (w * 32 + part * 16)) : -1;
     }
     const unsigned long long zero_src = (unsigned long long)k_zero_slot, xh = (unsigned long long)a.x_hi,
                              xl = (unsigned long long)a.x_lo, wh = (unsigned long long)a.w_hi, wlo = (unsigned long long)a.w_lo;
@@ -1618,26 +1200,11 @@ __global__ __launch_bounds__(256, 1) void conv_f16x3_dma16_kernel(ConvF16Args a)
         d.lds = lds0 + woff + split * W_SPLIT + rem * 1024;
         return d;
     };
-    auto slot_p = [&](int st, int poff, int k) {
-        const bool in_range = wave + 4 * k < P_PIECES;
-        const int pp = in_range ? wave + 4 * k : wave + 4 * (k - 1);
-        const int d = in_range ? desc[k < NDESC ? k : 0] : desc[(k > 0 && k - 1 < NDESC) ? k - 1 : 0];
-        const int cb = st / NKH, kh = st - cb * NKH, hx0 = h0 + kh - NKH / 2;
-        const bool v0 = hx0 >= 0 && hx0 < H, v1 = hx0 + 1 >= 0 && hx0 + 1 < H;
-        const long long st_off = (((long long)b * H + hx0) * NCB + cb) * (CV_PITCH * 32);
-        const unsigned long long base_h = xh + st_off, base_l = xl + st_off;
-        const bool ok = d >= 0 && ((d & (1 << 29)) ? v1 : v0);
-        const unsigned long long src = ((d & (1 << 30)) ? base_l : base_h) + (unsigned)(d & 0xFFFFF);
-        DmaSlot r;
-        r.src = ok ? src : zero_src;
-        r.lds = lds0 + poff + pp * 1024;
-        return r;
-    };
-    // RING: piece k of input row j (= h0 - 2 + j) of channel block cb -> row slot (6 cb + j) & 3; cb == NCB: zeros (no next stage)
+    // piece k of input row j (= h0 - 2 + j) of channel block cb -> row slot (6 cb + j) & 3; cb == NCB: zeros (no next stage)
     auto slot_row = [&](int cb, int j, int k) {
         const bool in_range = wave + 4 * k < R_PIECES;
         const int pp = in_range ? wave + 4 * k : wave + 4 * (k - 1);
-        const int d = in_range ? desc[k < NDESC ? k : 0] : desc[(k > 0 && k - 1 < NDESC) ? k - 1 : 0];
+        const int d = in_range ? desc[k] : desc[k > 0 ? k - 1 : 0];
         const int hx = h0 + j - NKH / 2;
         const bool v = hx >= 0 && hx < H && cb < NCB;
         const long long st_off = (((long long)b * H + hx) * NCB + cb) * (CV_PITCH * 32);
@@ -1657,36 +1224,21 @@ __global__ __launch_bounds__(256, 1) void conv_f16x3_dma16_kernel(ConvF16Args a)
     // prologue: taps 0..5 of stage 0 and its patch
 #pragma unroll
     for (int j = 0; j < 6; ++j) slot_issue(slot_w(0, 0, 6, W0_OFF, j));
-    if (RING) {
-        row_burst(0, 0);
-        row_burst(0, 1);
-    } else {
-#pragma unroll
-        for (int k = 0; k < PPW; ++k)
-            if (wave + 4 * k < P_PIECES) slot_issue(slot_p(0, P0_OFF, k));
-    }
-    if ((DMA16_ABL & 1) && !RING) {                                     // ablation: every buffer holds valid operands once, nothing moves afterwards
-#pragma unroll
-        for (int j = 0; j < 7; ++j) slot_issue(slot_w(0, 6, 7, W1_OFF, j));
-#pragma unroll
-        for (int k = 0; k < PPW; ++k)
-            if (wave + 4 * k < P_PIECES) slot_issue(slot_p(1, P1_OFF, k));
-    }
+    row_burst(0, 0);
+    row_burst(0, 1);
     DMA_WAIT();
     __syncthreads();
 
     // lane parts of the fragment addresses.  A = weights of channel half hh ^ c (hh relative to the wave), B = patch.
-    //   regular pair : + buffer offset + split * W_SPLIT + first tap slot * 2048 + (ct & 1) * 256   /   + patch offset + nt * 256 + kw * T * 16 + split * 4 * PLANE
-    //   straddling   : parity-0 lanes -> tap slot 6 of W1 / tap 12 of P0 (the even stage), parity-1 lanes -> tap slot 0 of W0 / tap 0 of P1
-    const int a_k = khf * 1024 + l16 * 16, b_k = RING ? khf * PLANE + l16 * 16 : (row * 2 + khf) * PLANE + l16 * 16;
+    //   regular pair : + buffer offset + split * W_SPLIT + first tap slot * 2048 + (ct & 1) * 256   /   + row slot + nt * 256 + kw * T * 16 + split * SP_STRIDE
+    //   straddling   : parity-0 lanes -> tap slot 6 of W1 / tap 12 of the even stage's row, parity-1 lanes -> tap slot 0 of W0 / tap 0 of the odd stage's row
+    const int a_k = khf * 1024 + l16 * 16, b_k = khf * PLANE + l16 * 16;
     const unsigned char *const a_p0 = smem + a_k + tp * 2048 + c * 512, *const a_p1 = smem + a_k + tp * 2048 + (c ^ 1) * 512;
-    // (one pointer per patch buffer: P1 lies beyond the 64 KB reach of a ds_read's immediate offset)
-    // (RING: re-based per stage couple below)
-    const unsigned char *b_pE = smem + P0_OFF + b_k + (c * 6 * 32 + tp * T) * 16, *bm_pE = smem + P0_OFF + b_k + (5 * 32 + tp * T) * 16;
-    const unsigned char *b_pO = b_pE + P_BYTES, *bm_pO = bm_pE + P_BYTES;
-    const int sa_off = tp ? W0_OFF : W1_OFF + 6 * 2048, sb_off = tp ? P1_OFF : P0_OFF + 12 * T * 16;
+    // patch fragment bases of the even / odd stage and of the straddling pair: re-based per stage couple below (the rows move round the ring)
+    const unsigned char *b_pE, *bm_pE, *b_pO, *bm_pO, *bs_p, *bsm_p;
+    const int b_x = (c * 6 * 32 + tp * T) * 16, bm_x = (5 * 32 + tp * T) * 16;      // column parts of the regular pairs' bases
+    const int sa_off = tp ? W0_OFF : W1_OFF + 6 * 2048;
     const unsigned char *const as_p0 = smem + a_k + sa_off + c * 512, *const as_p1 = smem + a_k + sa_off + (c ^ 1) * 512;
-    const unsigned char *bs_p = smem + b_k + sb_off + c * 6 * 32 * 16, *bsm_p = smem + b_k + sb_off + 5 * 32 * 16;
 
     // fragments: A double buffered [buf][ctr * 2 + split] (ctr = channel tile relative to the wave: 0, 1 = half c), B ring [slot][split]
     // with slot = nt % 6 for column tile nt < 10 and 4, 5 for the middle tile's halves 10, 11
@@ -1747,8 +1299,8 @@ __global__ __launch_bounds__(256, 1) void conv_f16x3_dma16_kernel(ConvF16Args a)
                 __builtin_amdgcn_sched_barrier(0);                                                     \
             }                                                                                          \
         }                                                                                              \
-        if ((NS) >= 1 && !(DMA16_ABL & 1)) slot_issue(s1_);                                            \
-        if ((NS) >= 2 && !(DMA16_ABL & 1)) slot_issue(s2_);                                            \
+        if ((NS) >= 1) slot_issue(s1_);                                                                \
+        if ((NS) >= 2) slot_issue(s2_);                                                                \
         __builtin_amdgcn_sched_barrier(0);                                                             \
     }
     // groups 2, 5, 8, 10 of a pair carry its DMA slots SBASE + 0..3; the others none
@@ -1766,44 +1318,41 @@ __global__ __launch_bounds__(256, 1) void conv_f16x3_dma16_kernel(ConvF16Args a)
     DMA16_S_(BUF, 8, RC, NA, RA, NB, RN, SLOTN, SLOT_A, SLOT_B, (SBASE) + 2)              \
     DMA16_G_(BUF, 9, RC, NA, RA, NB, RN)                                                  \
     DMA16_S_(BUF, 10, RC, NA, RA, NB, RN, SLOTN, SLOT_A, SLOT_B, (SBASE) + 3)
-    // fragment readers of the schedule below: patch of the even stage in P0, of the odd stage in P1
+    // fragment readers of the schedule below: patch of the even stage (b_pE), of the odd stage (b_pO), of the straddling pair
 #define RB_E(KW) [&](int nt_, int sp_) { rdB(0, KW, nt_, sp_); }
 #define RB_O(KW) [&](int nt_, int sp_) { rdB(1, KW, nt_, sp_); }
 #define RB_S [&](int nt_, int sp_) { rdB_str(nt_, sp_); }
 #define RA_(WOFF, TL) [&](int buf_, int q_) { rdA(buf_, WOFF, TL, q_); }
 #define R_NONE [&](int, int) {}
-#define NO_SLOTN(J) 0
-#define NO_SLOT(J) DmaSlot{}
 
 #pragma unroll 1
     for (int s = 0; s < N_STAGE; s += 2) {
         const int so = s + 1, sn = s + 2 < N_STAGE ? s + 2 : s + 1;      // odd stage; the stage after it (last couple: harmless repeats)
-        // RING: the new rows of the odd stage (fetched during the even one) and of stage s + 2 (fetched during the odd one):
+        // the new rows of the odd stage (fetched during the even one) and of stage s + 2 (fetched during the odd one):
         // row A = kernel row + 1 of the successor, always; row B = its row 0, only when it opens a channel block
         const int cbo = so / NKH, kho = so - cbo * NKH, cbn = (s + 2) / NKH, khn = (s + 2) - cbn * NKH;
-        const bool two_e = RING && kho == 0, two_o = RING && khn == 0 && s + 2 < N_STAGE;
-        if (RING) {
+        const bool two_e = kho == 0, two_o = khn == 0 && s + 2 < N_STAGE;
+        {
             const int n0e = (s / NKH) * 6 + s % NKH + row, n0o = cbo * 6 + kho + row;
             const int oe = P0_OFF + (n0e & 3) * SLOT_BYTES, oo = P0_OFF + (n0o & 3) * SLOT_BYTES;
-            b_pE = smem + oe + b_k + (c * 6 * 32 + tp * T) * 16;
-            bm_pE = smem + oe + b_k + (5 * 32 + tp * T) * 16;
-            b_pO = smem + oo + b_k + (c * 6 * 32 + tp * T) * 16;
-            bm_pO = smem + oo + b_k + (5 * 32 + tp * T) * 16;
+            b_pE = smem + oe + b_k + b_x;
+            bm_pE = smem + oe + b_k + bm_x;
+            b_pO = smem + oo + b_k + b_x;
+            bm_pO = smem + oo + b_k + bm_x;
             const int os = tp ? oo : oe + 12 * T * 16;
             bs_p = smem + b_k + os + c * 6 * 32 * 16;
             bsm_p = smem + b_k + os + 5 * 32 * 16;
         }
-        // ================= even stage s: taps 0..11 (patch P0; W0 = taps 0..5, W1 = taps 6..12) =================
-        // DMA phase A (12 slots): W1 <- taps 6..12 of s in slots 0..6, patch pieces 0..4 of stage s + 1 -> P1; ends on vmcnt(5)
-        //     phase B (12 slots): W0 <- taps 0..6 of s + 1 in slots 0..6 with patch pieces 5.. riding along (piece 12 in slot 7)
+        // ================= even stage s: taps 0..11 (W0 = taps 0..5, W1 = taps 6..12) =================
+        // DMA phase A (12 slots): W1 <- taps 6..12 of s in slots 0..6, pieces 0..4 of the odd stage's new row in slots 7..11; ends on vmcnt(5)
+        //     phase B (12 slots): W0 <- taps 0..6 of s + 1 in slots 0..6 with the row's pieces 5.. riding along
 #define EA_SLOTN(J) 1
-#define NPW_ (RING ? RPW : PPW)
-#define PATCH_E_(K) (RING ? slot_row(cbo, kho + 1, (K)) : slot_p(so, P1_OFF, (K)))
-#define PATCH_O_(K) (RING ? slot_row(cbn, khn + 1, (K)) : slot_p(sn, P0_OFF, (K)))
+#define PATCH_E_(K) slot_row(cbo, kho + 1, (K))
+#define PATCH_O_(K) slot_row(cbn, khn + 1, (K))
 #define EA_SLOT1(J) ((J) < 7 ? slot_w(s, 6, 7, W1_OFF, (J)) : PATCH_E_((J) - 7))
-#define EB_SLOTN(J) (((J) < 7 ? 1 : 0) + ((J) + 5 < NPW_ ? 1 : 0))
-#define EB_SLOT1(J) ((J) < 7 ? slot_w(so, 0, 7, W0_OFF, (J)) : PATCH_E_((J) + 5 < NPW_ ? (J) + 5 : NPW_ - 1))
-#define EB_SLOT2(J) PATCH_E_((J) + 5 < NPW_ ? (J) + 5 : NPW_ - 1)
+#define EB_SLOTN(J) (((J) < 7 ? 1 : 0) + ((J) + 5 < RPW ? 1 : 0))
+#define EB_SLOT1(J) ((J) < 7 ? slot_w(so, 0, 7, W0_OFF, (J)) : PATCH_E_((J) + 5 < RPW ? (J) + 5 : RPW - 1))
+#define EB_SLOT2(J) PATCH_E_((J) + 5 < RPW ? (J) + 5 : RPW - 1)
 #pragma unroll
         for (int q = 0; q < 8; ++q) rdA(0, W0_OFF, 0, q);
 #pragma unroll
@@ -1821,22 +1370,22 @@ __global__ __launch_bounds__(256, 1) void conv_f16x3_dma16_kernel(ConvF16Args a)
         DMA16_PAIR(1, RB_E(10), 0, R_NONE, 0, R_NONE, EB_SLOTN, EB_SLOT1, EB_SLOT2, 8)          // the next pair straddles: its operands land with the barrier
         DMA_WAIT();
         __syncthreads();
-        // ================= odd stage s + 1: the straddling pair, then taps 1..12 (patch P1; W0 = taps 0..6, W1 = taps 7..12) =====
+        // ================= odd stage s + 1: the straddling pair, then taps 1..12 (W0 = taps 0..6, W1 = taps 7..12) =====
         // DMA phase A (16 slots): W1 <- taps 7..12 of s + 1 in slots 0..5 (tap slot 6 of W1 keeps the even stage's tap 12);
-        //                         after the barrier behind the straddling pair: patch pieces 0..5 of stage s + 2 -> P0 in slots 6..11;
+        //                         after the barrier behind the straddling pair: pieces 0..5 of stage s + 2's new row in slots 6..11;
         //                         ends on vmcnt(6)
-        //     phase B (12 slots): W0 <- taps 0..5 of s + 2 in slots 0..5 with patch pieces 6.. riding along
+        //     phase B (12 slots): W0 <- taps 0..5 of s + 2 in slots 0..5 with the row's piece 6 riding along
 #define OA_SLOTN(J) ((J) < 12 ? 1 : 0)
 #define OA_SLOT1(J) ((J) < 6 ? slot_w(so, 7, 6, W1_OFF, (J)) : PATCH_O_((J) < 12 ? (J) - 6 : 5))
-#define OB_SLOTN(J) (((J) < 6 ? 1 : 0) + ((J) + 6 < NPW_ ? 1 : 0))
-#define OB_SLOT1(J) ((J) < 6 ? slot_w(sn, 0, 6, W0_OFF, (J)) : PATCH_O_((J) + 6 < NPW_ ? (J) + 6 : NPW_ - 1))
-#define OB_SLOT2(J) PATCH_O_((J) + 6 < NPW_ ? (J) + 6 : NPW_ - 1)
+#define OB_SLOTN(J) (((J) < 6 ? 1 : 0) + ((J) + 6 < RPW ? 1 : 0))
+#define OB_SLOT1(J) ((J) < 6 ? slot_w(sn, 0, 6, W0_OFF, (J)) : PATCH_O_((J) + 6 < RPW ? (J) + 6 : RPW - 1))
+#define OB_SLOT2(J) PATCH_O_((J) + 6 < RPW ? (J) + 6 : RPW - 1)
 #pragma unroll
         for (int q = 0; q < 8; ++q) rdA_str(0, q);
 #pragma unroll
         for (int nt = 0; nt < 4; ++nt) { rdB_str(nt, 0); rdB_str(nt, 1); }
         DMA16_PAIR(0, RB_S, 1, RA_(W0_OFF, 1), 1, RB_O(1), OA_SLOTN, OA_SLOT1, OA_SLOT1, 0)     // slots 0..3: weights only
-        if (!(DMA16_ABL & 2)) __builtin_amdgcn_s_barrier();   // every wave holds the straddling pair's operands: P0 may be overwritten from here on
+        if (!(DMA16_ABL & 2)) __builtin_amdgcn_s_barrier();   // every wave holds the straddling pair's operands: patch pieces may be issued from here on
         DMA16_PAIR(1, RB_O(1), 1, RA_(W0_OFF, 3), 1, RB_O(3), OA_SLOTN, OA_SLOT1, OA_SLOT1, 4)
         DMA16_PAIR(0, RB_O(3), 1, RA_(W0_OFF, 5), 1, RB_O(5), OA_SLOTN, OA_SLOT1, OA_SLOT1, 8)
         DMA16_PAIR(1, RB_O(5), 0, R_NONE, 1, RB_O(7), OA_SLOTN, OA_SLOT1, OA_SLOT1, 12)
@@ -1860,8 +1409,6 @@ __global__ __launch_bounds__(256, 1) void conv_f16x3_dma16_kernel(ConvF16Args a)
 #undef RB_S
 #undef RA_
 #undef R_NONE
-#undef NO_SLOTN
-#undef NO_SLOT
 #undef EA_SLOTN
 #undef EA_SLOT1
 #undef EB_SLOTN
@@ -1872,34 +1419,33 @@ __global__ __launch_bounds__(256, 1) void conv_f16x3_dma16_kernel(ConvF16Args a)
 #undef OB_SLOTN
 #undef OB_SLOT1
 #undef OB_SLOT2
-#undef NPW_
 #undef PATCH_E_
 #undef PATCH_O_
     asm volatile("s_nop 7\n\ts_nop 7" ::: "memory");           // the asm MFMAs are invisible to the hazard recogniser: results settled before the epilogue reads them
     conv_f16_epilogue<0>(acc, a, smem, b, h0, row, c, lane);
 }
 
-template <int T, bool RING>
+template <int T>
 static int launch_f16_dma16(const ConvF16Args &a, int B, hipStream_t st)
 {
-    constexpr int PWP = DMA16_PWP_PAD ? (CV_PITCH + 12 * T + 15) / 16 * 16 : CV_PITCH + 12 * T;
-    constexpr size_t lds = 2 * (2 * 7 * 2048) + (RING ? 4 * (size_t)((4 * PWP + 63) / 64) : 2 * (size_t)((8 * PWP + 63) / 64)) * 1024;
+    constexpr int PWP = (CV_PITCH + 12 * T + 15) / 16 * 16;
+    constexpr size_t lds = 2 * (2 * 7 * 2048) + 4 * (size_t)((4 * PWP + 63) / 64) * 1024;      // W[2] + four row slots
     static_assert(lds <= 160 * 1024, "LDS budget");
     static MxLdsLatch latch = {};                             // per device (common.h)
-    if (mx_set_dyn_lds(latch, (const void *)conv_f16x3_dma16_kernel<T, RING>, lds) != MX_OK) return MX_ERR_LAUNCH;
-    hipLaunchKernelGGL((conv_f16x3_dma16_kernel<T, RING>), dim3(a.H / 2, B), dim3(256), lds, st, a);
+    if (mx_set_dyn_lds(latch, (const void *)conv_f16x3_dma16_kernel<T, true>, lds) != MX_OK) return MX_ERR_LAUNCH;
+    hipLaunchKernelGGL((conv_f16x3_dma16_kernel<T, true>), dim3(a.H / 2, B), dim3(256), lds, st, a);
     return mx_launch_status();
 }
 
-template <int T, int OUTMODE, int NCB = 4, int NKH = CV_KH>
+template <int T>
 static int launch_f16_dma(const ConvF16Args &a, int B, hipStream_t st)
 {
     constexpr int PWP = CV_PITCH + 12 * T;
     constexpr size_t lds = 2 * (2 * 7 * 2048) + 2 * (size_t)((8 * PWP + 63) / 64) * 1024;
     static_assert(lds <= 160 * 1024, "LDS budget");
     static MxLdsLatch latch = {};                             // per device (common.h)
-    if (mx_set_dyn_lds(latch, (const void *)conv_f16x3_dma_kernel<T, OUTMODE, NCB, NKH>, lds) != MX_OK) return MX_ERR_LAUNCH;
-    hipLaunchKernelGGL((conv_f16x3_dma_kernel<T, OUTMODE, NCB, NKH>), dim3(a.H / 2, B), dim3(256), lds, st, a);
+    if (mx_set_dyn_lds(latch, (const void *)conv_f16x3_dma_kernel<T>, lds) != MX_OK) return MX_ERR_LAUNCH;
+    hipLaunchKernelGGL((conv_f16x3_dma_kernel<T>), dim3(a.H / 2, B), dim3(256), lds, st, a);
     return mx_launch_status();
 }
 
@@ -1917,29 +1463,15 @@ static int launch_f16(const ConvF16Args &a, int B, hipStream_t st)
 static int dispatch_f16(int T, int outmode, const ConvF16Args &a, int B, hipStream_t st)
 {
     if (outmode == 0) {
-        // MODEX_MFMA_SHAPE=32 selects the v_mfma_f32_32x32x16_f16 forward kernels (same-box A/B, profiles/r04)
-        static const bool shape16 = !(getenv("MODEX_MFMA_SHAPE") && atoi(getenv("MODEX_MFMA_SHAPE")) == 32);
-        if (shape16) {
-            // MODEX_PATCH_RING=0: the two 2-row patch buffers instead of the four-row ring (same-box A/B)
-            static const bool ring = !(getenv("MODEX_PATCH_RING") && atoi(getenv("MODEX_PATCH_RING")) == 0);
-            if (ring) {
-                if (T == 1) return launch_f16_dma16<1, true>(a, B, st);
-                if (T == 2) return launch_f16_dma16<2, true>(a, B, st);
-                if (T == 4) return launch_f16_dma16<4, true>(a, B, st);
-            }
-            if (T == 1) return launch_f16_dma16<1, false>(a, B, st);
-            if (T == 2) return launch_f16_dma16<2, false>(a, B, st);
-            if (T == 4) return launch_f16_dma16<4, false>(a, B, st);
-        }
-        if (T == 1) return launch_f16_dma<1, 0>(a, B, st);
-        if (T == 2) return launch_f16_dma<2, 0>(a, B, st);
-        if (T == 4) return launch_f16_dma<4, 0>(a, B, st);
+        if (T == 1) return launch_f16_dma16<1>(a, B, st);
+        if (T == 2) return launch_f16_dma16<2>(a, B, st);
+        if (T == 4) return launch_f16_dma16<4>(a, B, st);
         if (T == 8) return launch_f16<8, 0>(a, B, st);
         if (T == 16) return launch_f16<16, 0>(a, B, st);
     } else {
-        if (T == 1) return launch_f16_dma<1, 1>(a, B, st);
-        if (T == 2) return launch_f16_dma<2, 1>(a, B, st);
-        if (T == 4) return launch_f16_dma<4, 1>(a, B, st);
+        if (T == 1) return launch_f16_dma<1>(a, B, st);
+        if (T == 2) return launch_f16_dma<2>(a, B, st);
+        if (T == 4) return launch_f16_dma<4>(a, B, st);
         if (T == 8) return launch_f16<8, 1>(a, B, st);
         if (T == 16) return launch_f16<16, 1>(a, B, st);
     }
@@ -2021,7 +1553,7 @@ MX_EXPORT int mx_conv_block_dgrad_f16(const void *dz_hi, const void *dz_lo, cons
     return dispatch_f16(dilation, 1, a, (int)B, (hipStream_t)stream);
 }
 
-// ---- first block (2 input channels) on the same kernel: one K stage -------------------------------------------
+// ---- first block (2 input channels): one K stage (conv1_f16x3_tile_kernel) --------------------------------------
 // W (64,2,5,13) -> w_hi, w_lo: 13*2*64*8 halfs each
 MX_EXPORT int mx_conv_pack_weights_kvec_f16(const float *W, void *w_hi, void *w_lo, void *stream)
 {
@@ -2052,39 +1584,19 @@ MX_EXPORT int mx_conv_block1_fwd_f16(const void *xk_hi, const void *xk_lo, const
     if (B <= 0 || B > 65535 || H < 2 || (H & 1) || Wv <= 0 || Wv > CV_PITCH) return MX_ERR_UNSUPPORTED;
     ConvF16Args a{(const _Float16 *)xk_hi, (const _Float16 *)xk_lo, (const _Float16 *)w_hi, (const _Float16 *)w_lo, bias,
                   nullptr, out, out_amax, (int)H, (int)Wv, slope_out, stats_part};
-    // MODEX_BLOCK1_PERSIST=0 selects the one-row-pair-per-workgroup kernel (same-box A/B)
-    // (1: the persistent kernel with the row-exchanging epilogue; default 2: its pair-wave layout)
-    // 3 (default, round 5): the tile-outer kernel (weights in registers, the epilogue of a column tile under the next one's MFMAs)
-    static const int persist = getenv("MODEX_BLOCK1_PERSIST") ? atoi(getenv("MODEX_BLOCK1_PERSIST")) : 3;
-    if (!persist) return launch_f16_dma<1, 0, 1, 1>(a, (int)B, (hipStream_t)stream);
-    if (persist == 3) {
-        constexpr size_t lds3 = 2 * (size_t)((8 * (CV_PITCH + 12) + 63) / 64) * 1024 + 4 * 4352 + 8192 + 12 * 256 * sizeof(int);
-        static MxLdsLatch latch3 = {};
-        static MxLdsLatch latch3n = {};
-        if (mx_set_dyn_lds(latch3, (const void *)conv1_f16x3_tile_kernel<true>, lds3) != MX_OK ||
-            mx_set_dyn_lds(latch3n, (const void *)conv1_f16x3_tile_kernel<false>, lds3) != MX_OK)
-            return MX_ERR_LAUNCH;
-        const int n_tiles3 = (int)(B * (H / 2));
-        int grid3 = 1024;
-        if (grid3 > n_tiles3) grid3 = n_tiles3;
-        const int per3 = (n_tiles3 + grid3 - 1) / grid3;
-        grid3 = (n_tiles3 + per3 - 1) / per3;
-        if (stats_part) hipLaunchKernelGGL(conv1_f16x3_tile_kernel<true>, dim3((unsigned)grid3), dim3(256), lds3, (hipStream_t)stream, a, n_tiles3, per3);
-        else hipLaunchKernelGGL(conv1_f16x3_tile_kernel<false>, dim3((unsigned)grid3), dim3(256), lds3, (hipStream_t)stream, a, n_tiles3, per3);
-        return mx_launch_status();
-    }
-    constexpr size_t lds = 2 * CV_KW * 2048 + 2 * (size_t)((8 * (CV_PITCH + 12) + 63) / 64) * 1024;
+    // patch P[2] | 4 transposition images | sums | DMA descriptors (conv1_f16x3_tile_kernel)
+    constexpr size_t lds = 2 * (size_t)((8 * (CV_PITCH + 12) + 63) / 64) * 1024 + 4 * 4352 + 8192 + 12 * 256 * sizeof(int);
     static_assert(lds <= 160 * 1024, "LDS budget");
-    static MxLdsLatch latch0 = {}, latch1 = {};                 // per device (common.h)
-    if (mx_set_dyn_lds(latch0, (const void *)conv1_f16x3_persist_kernel<0>, lds) != MX_OK ||
-        mx_set_dyn_lds(latch1, (const void *)conv1_f16x3_persist_kernel<1>, lds) != MX_OK)
+    static MxLdsLatch latch_s = {}, latch_n = {};               // per device (common.h)
+    if (mx_set_dyn_lds(latch_s, (const void *)conv1_f16x3_tile_kernel<true>, lds) != MX_OK ||
+        mx_set_dyn_lds(latch_n, (const void *)conv1_f16x3_tile_kernel<false>, lds) != MX_OK)
         return MX_ERR_LAUNCH;
     const int n_tiles = (int)(B * (H / 2));
     int grid = 1024;                                            // 4 workgroups per CU over the launch: contiguous ranges, a short tail
     if (grid > n_tiles) grid = n_tiles;
     const int per = (n_tiles + grid - 1) / grid;
     grid = (n_tiles + per - 1) / per;
-    if (persist == 1) hipLaunchKernelGGL(conv1_f16x3_persist_kernel<0>, dim3((unsigned)grid), dim3(256), lds, (hipStream_t)stream, a, n_tiles, per);
-    else hipLaunchKernelGGL(conv1_f16x3_persist_kernel<1>, dim3((unsigned)grid), dim3(256), lds, (hipStream_t)stream, a, n_tiles, per);
+    if (stats_part) hipLaunchKernelGGL(conv1_f16x3_tile_kernel<true>, dim3((unsigned)grid), dim3(256), lds, (hipStream_t)stream, a, n_tiles, per);
+    else hipLaunchKernelGGL(conv1_f16x3_tile_kernel<false>, dim3((unsigned)grid), dim3(256), lds, (hipStream_t)stream, a, n_tiles, per);
     return mx_launch_status();
 }

@@ -8,14 +8,14 @@
 // here is about that latency.  Measured on the part (tools/probe/ubench_valu.hip): a wave issues one vector
 // instruction per ~4.8 cycles whatever its neighbours on the SIMD do (up to 4 waves per SIMD), and an
 // LDS write -> barrier -> read round trip costs ~250 cycles with 8 waves: a step costs
-// (instructions per wave) x 2 ns + ~100 ns.  Hence: one 512-thread workgroup (8 waves) per clip, as few
+// (instructions per wave) x 2 ns + ~100 ns.  Hence: one workgroup per clip (forward 4 waves, backward 8 + 4 helpers), as few
 // instructions per wave and step as possible, exactly ONE barrier per step.
 //
-//  forward   lane = (unit u, gate pair gp, quarter kq of the 64 h values): 2 gates x 16 k = 16 v_pk_fma_f32
-//            (both gates of the pair in one packed FMA, the h value broadcast to both halves by op_sel), four
-//            ds_read_b128 of h per lane.  The quarters are summed by two DPP quad_perm adds per gate, every lane
-//            applies ONE gate's activation (one exp + one rcp), the 8 lanes of a unit exchange i, f, g, o by DPP
-//            (row_half_mirror + quad_perm), c stays in registers, h goes to the next row of a 256-step history in
+//  forward   lane = (unit u, gate pair gp, half kq of the 64 h values): 2 gates x 32 k = 32 v_pk_fma_f32
+//            (both gates of the pair in one packed FMA, the h value broadcast to both halves by op_sel), eight
+//            ds_read_b128 of h per lane.  The halves are summed by one DPP quad_perm add per gate, every lane
+//            applies ONE gate's activation (one exp + one rcp), the 4 lanes of a unit exchange i, f, g, o by DPP
+//            (quad_perm), c stays in registers, h goes to the next row of a 256-step history in
 //            LDS -- rows never collide, hence one barrier per step.  y_t = tanh(fc h_t + b + x_t) is not on the
 //            recurrent path: it is evaluated for 256 steps at a time from the history, one step per thread.
 //  backward  (serial part) lane = (pair of hidden units, group rg of 16 gate rows): dh_prev[k] = sum_r W[r][k] dg[r]
@@ -40,7 +40,6 @@
 // tanh(x) = 2 sigmoid(2x) - 1 (absolute error ~1e-7, the recurrent path carries 1e-5 parity, tests/test_gpu_lstm.py).
 // Algorithmic HBM traffic: 12 B/sample I/O + 1536 B/sample stash (written, read once).
 #include "conv_common.h"
-#include <stdlib.h>
 #include <type_traits>
 
 #define LS_H 64
@@ -133,8 +132,8 @@ __device__ __forceinline__ void ls_barrier()      // LDS-only: outstanding globa
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 }
 
-template <int KQ>     // k-split of a gate row over lanes: 4 (512 threads, 16 k per lane) or 2 (256 threads, 32 k per lane)
-__global__ __launch_bounds__(128 * KQ) void lstm_fwd_kernel(const float *__restrict__ x, long long xs,
+#define LS_FWD_THREADS 256
+__global__ __launch_bounds__(LS_FWD_THREADS) void lstm_fwd_kernel(const float *__restrict__ x, long long xs,
                                                               const float *__restrict__ lfo, long long ls,
                                                               const float *__restrict__ w_ih,
                                                               const float *__restrict__ w_hh,
@@ -151,9 +150,10 @@ __global__ __launch_bounds__(128 * KQ) void lstm_fwd_kernel(const float *__restr
     __shared__ __attribute__((aligned(16))) float2 xl[LS_TB];                   // (lfo, x) of the block
     __shared__ float dummy[LS_THREADS + LS_FG * LS_HP];                          // sink of the lanes that hold no h (+ a group's row offsets)
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    constexpr int KQ = 2;                           // k-split of a gate row over lanes: 256 threads, 32 k per lane
     constexpr int KPL = LS_H / KQ;                  // k values per lane
     const int kq = lane & (KQ - 1), gp = (lane / KQ) & 1, u = wv * (32 / KQ) + lane / (2 * KQ);
-    const int q = 2 * gp + (kq & 1);                // the gate this lane activates (lanes kq >= 2 duplicate kq - 2)
+    const int q = 2 * gp + (kq & 1);                // the gate this lane activates
     const int ra = (2 * gp) * LS_H + u, rb = (2 * gp + 1) * LS_H + u;
     ls_f2 wp[KPL];
 #pragma unroll
@@ -171,16 +171,13 @@ __global__ __launch_bounds__(128 * KQ) void lstm_fwd_kernel(const float *__restr
     const float *xb = x + (size_t)b * xs, *lb = lfo + (size_t)b * ls;
     float *yb = y + (size_t)b * ys;
     float *sb = stash ? stash + (size_t)b * T * LS_STASH : nullptr;
-    // KQ = 4: quads gp = 0 see (i, f) in their own lanes and (o, g) mirrored: they carry c and h; quads gp = 1 compute
-    // junk.  KQ = 2: a quad holds i, f, g, o of one unit: every lane carries c and h.
-    const bool valid = KQ == 2 || gp == 0;
-    const bool writer = valid && (KQ == 2 ? (lane & 3) == 0 : true);
+    // a quad holds i, f, g, o of one unit: every lane carries c and h, its first lane writes h
+    const bool writer = (lane & 3) == 0;
     float *hw = writer ? hist + LS_HP + u : dummy + tid;         // where this lane's h goes (row 1 = step 0)
     const int hw_step = writer ? LS_HP : 0;
-    // stash slot of this lane: its gate activation; KQ = 4: the spare lanes kq = 2, 3 of the valid quads store c and h
-    // in the same instruction; KQ = 2: lanes 0 / 1 of the quad store them with a second instruction
-    const bool st_c = KQ == 4 ? valid && kq == 2 : (lane & 3) == 0, st_h = KQ == 4 ? valid && kq == 3 : (lane & 3) == 1;
-    const int st_off = KQ == 4 ? (st_c ? 256 + u : (st_h ? 320 + u : q * LS_H + u)) : q * LS_H + u;
+    // stash slot of this lane: its gate activation; lanes 0 / 1 of the quad store c and h with a second instruction
+    const bool st_c = (lane & 3) == 0, st_h = (lane & 3) == 1;
+    const int st_off = q * LS_H + u;
     const int st_off2 = st_c ? 256 + u : (st_h ? 320 + u : q * LS_H + u);
 
     for (int t0 = 0; t0 < T; t0 += LS_TB) {
@@ -212,39 +209,26 @@ __global__ __launch_bounds__(128 * KQ) void lstm_fwd_kernel(const float *__restr
                     const float2 in = xlg[j];                  // (first: the input term is then formed while the h reads are in flight)
                     const float4 h0 = *(const float4 *)(hr + j * LS_HP), h1 = *(const float4 *)(hr + j * LS_HP + 4),
                                  h2 = *(const float4 *)(hr + j * LS_HP + 8), h3 = *(const float4 *)(hr + j * LS_HP + 12);
-                    float4 h4, h5, h6, h7;
-                    if (KQ == 2) {
-                        h4 = *(const float4 *)(hr + j * LS_HP + 16); h5 = *(const float4 *)(hr + j * LS_HP + 20);
-                        h6 = *(const float4 *)(hr + j * LS_HP + 24); h7 = *(const float4 *)(hr + j * LS_HP + 28);
-                    }
+                    const float4 h4 = *(const float4 *)(hr + j * LS_HP + 16), h5 = *(const float4 *)(hr + j * LS_HP + 20),
+                                 h6 = *(const float4 *)(hr + j * LS_HP + 24), h7 = *(const float4 *)(hr + j * LS_HP + 28);
                     __builtin_amdgcn_sched_barrier(0);         // (the step's reads first; the deferred store rides in their shadow)
                     if (do_st && (g > 0 || j > 0)) {                   // (the selects live here, not between the barrier and the reads)
-                        if (KQ == 4) stg[(j - 1) * LS_STASH + st_off] = st_c ? pend_c : (st_h ? pend_h : pend_a);
-                        else {
-                            stg[(j - 1) * LS_STASH + st_off] = pend_a;
-                            stg[(j - 1) * LS_STASH + st_off2] = st_c ? pend_c : (st_h ? pend_h : pend_a);
-                        }
+                        stg[(j - 1) * LS_STASH + st_off] = pend_a;
+                        stg[(j - 1) * LS_STASH + st_off2] = st_c ? pend_c : (st_h ? pend_h : pend_a);
                     }
                     // input term as two packed FMAs (the rolled loop below keeps the unfused 4-instruction form: same value to 1 ulp)
                     ls_f2 acc;
                     asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel_hi:[1,0,1]" : "=v"(acc) : "v"(wi0), "v"(in), "v"(bias));
                     asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel:[0,1,0]" : "+v"(acc) : "v"(wi1), "v"(in));
                     LS_PK16(acc, wp, h0, h1, h2, h3);
-                    if (KQ == 2) {
-                        const ls_f2 *wq = wp + (KQ == 2 ? 16 : 0);
+                    {
+                        const ls_f2 *wq = wp + 16;
                         LS_PK16(acc, wq, h4, h5, h6, h7);
                     }
                     float pa = acc.x, pb = acc.y;
-                    pa += ls_dpp<0xB1>(pa); pb += ls_dpp<0xB1>(pb);     // quad_perm [1,0,3,2]
-                    if (KQ == 4) { pa += ls_dpp<0x4E>(pa); pb += ls_dpp<0x4E>(pb); }   // quad_perm [2,3,0,1]: all four quarters
+                    pa += ls_dpp<0xB1>(pa); pb += ls_dpp<0xB1>(pb);     // quad_perm [1,0,3,2]: both halves
                     const float a = ls_act(odd ? pb : pa, nsl2e, s, oms);
-                    float gi, gf, gg, go;
-                    if (KQ == 4) {
-                        const float m = ls_dpp<0x141>(a);               // row_half_mirror: the other gate pair of the unit
-                        gi = ls_dpp<0x00>(a); gf = ls_dpp<0x55>(a); gg = ls_dpp<0x55>(m); go = ls_dpp<0x00>(m);
-                    } else {
-                        gi = ls_dpp<0x00>(a); gf = ls_dpp<0x55>(a); gg = ls_dpp<0xAA>(a); go = ls_dpp<0xFF>(a);
-                    }
+                    const float gi = ls_dpp<0x00>(a), gf = ls_dpp<0x55>(a), gg = ls_dpp<0xAA>(a), go = ls_dpp<0xFF>(a);
                     c = fmaf(gf, c, gi * gg);
                     const float hv = go * ls_tanh(c);
                     hwp[j * LS_HP] = hv;
@@ -258,11 +242,8 @@ __global__ __launch_bounds__(128 * KQ) void lstm_fwd_kernel(const float *__restr
             }
             if (do_st) {                                       // the block's last step
                 float *stl = sb + (size_t)(t0 + cnt - 1) * LS_STASH;
-                if (KQ == 4) stl[st_off] = st_c ? pend_c : (st_h ? pend_h : pend_a);
-                else {
-                    stl[st_off] = pend_a;
-                    stl[st_off2] = st_c ? pend_c : (st_h ? pend_h : pend_a);
-                }
+                stl[st_off] = pend_a;
+                stl[st_off2] = st_c ? pend_c : (st_h ? pend_h : pend_a);
             }
           };
           if (sb && !probe) run_groups(std::true_type{});
@@ -277,46 +258,30 @@ __global__ __launch_bounds__(128 * KQ) void lstm_fwd_kernel(const float *__restr
                 h0 = *(const float4 *)hr; h1 = *(const float4 *)(hr + 4); h2 = *(const float4 *)(hr + 8);
                 h3 = *(const float4 *)(hr + 12);
             }
-            float4 h4, h5, h6, h7;
-            if (KQ == 2) {
-                h4 = *(const float4 *)(hr + 16); h5 = *(const float4 *)(hr + 20); h6 = *(const float4 *)(hr + 24);
-                h7 = *(const float4 *)(hr + 28);
-            }
+            const float4 h4 = *(const float4 *)(hr + 16), h5 = *(const float4 *)(hr + 20), h6 = *(const float4 *)(hr + 24),
+                         h7 = *(const float4 *)(hr + 28);
             const float2 in = xl[tt];
             LS_STAMP(0)                                         // LDS reads landed
             ls_f2 acc = wi1 * in.y + (wi0 * in.x + bias);
             if (!(LS_ABL & 16)) {
                 LS_PK16(acc, wp, h0, h1, h2, h3);
-                if (KQ == 2) {
-                    const ls_f2 *wq = wp + (KQ == 2 ? 16 : 0);
-                    LS_PK16(acc, wq, h4, h5, h6, h7);
-                }
+                const ls_f2 *wq = wp + 16;
+                LS_PK16(acc, wq, h4, h5, h6, h7);
             } else {
                 acc += (ls_f2){h0.x, h3.w};
             }
             float pa = acc.x, pb = acc.y;
             LS_STAMP(1)                                         // packed FMAs
-            pa += ls_dpp<0xB1>(pa); pb += ls_dpp<0xB1>(pb);     // quad_perm [1,0,3,2]
-            if (KQ == 4) { pa += ls_dpp<0x4E>(pa); pb += ls_dpp<0x4E>(pb); }   // quad_perm [2,3,0,1]: all four quarters
+            pa += ls_dpp<0xB1>(pa); pb += ls_dpp<0xB1>(pb);     // quad_perm [1,0,3,2]: both halves
             const float a = (LS_ABL & 2) ? (odd ? pb : pa) * 0.01f : ls_act(odd ? pb : pa, nsl2e, s, oms);
-            float gi, gf, gg, go;
-            if (KQ == 4) {
-                const float m = ls_dpp<0x141>(a);               // row_half_mirror: the other gate pair of the unit
-                gi = ls_dpp<0x00>(a); gf = ls_dpp<0x55>(a); gg = ls_dpp<0x55>(m); go = ls_dpp<0x00>(m);
-            } else {
-                gi = ls_dpp<0x00>(a); gf = ls_dpp<0x55>(a); gg = ls_dpp<0xAA>(a); go = ls_dpp<0xFF>(a);
-            }
+            const float gi = ls_dpp<0x00>(a), gf = ls_dpp<0x55>(a), gg = ls_dpp<0xAA>(a), go = ls_dpp<0xFF>(a);
             c = fmaf(gf, c, gi * gg);
             const float hv = go * ((LS_ABL & 2) ? c * 0.5f : ls_tanh(c));
             LS_STAMP(2)                                         // reduce, activation, exchange, cell update
             if (!(LS_ABL & 8)) *hwp = hv;
             if (sb && !probe && !(LS_ABL & 32)) {
-                if (KQ == 4) {
-                    *st = st_c ? c : (st_h ? hv : a);
-                } else {
-                    *st = a;
-                    st[st_off2 - st_off] = st_c ? c : (st_h ? hv : a);
-                }
+                *st = a;
+                st[st_off2 - st_off] = st_c ? c : (st_h ? hv : a);
                 st += LS_STASH;
             }
             hr += LS_HP;
@@ -364,17 +329,10 @@ static int lstm_fwd_launch(const float *x, int64_t x_stride, const float *lfo, i
     // 4 waves (32 k per lane, no idle lanes in the cell update, half the waves at the barrier) for both uses.  Rounds 3-5 ran
     // 8 waves (16 k per lane; the spare lanes carry c and h in the one stash store) when the BPTT stash is written: 0.349 vs
     // 0.343 ms then; with round 6's unrolled groups and the deferred stash store the 4-wave kernel is ahead with the stash
-    // too: 0.284 vs 0.305 ms per 128 clips x 1024 steps (0.260 vs 0.315 without).  MODEX_LSTM_KQ = 2 | 4 forces one (experiments).
-    static const int kq_env = getenv("MODEX_LSTM_KQ") ? atoi(getenv("MODEX_LSTM_KQ")) : 0;
-    const int kq = kq_env == 4 ? 4 : 2;
-    if (kq == 2)
-        hipLaunchKernelGGL(lstm_fwd_kernel<2>, dim3((unsigned)B), dim3(256), 0, (hipStream_t)stream, x,
-                           (long long)x_stride, lfo, (long long)lfo_stride, w_ih, w_hh, b_ih, b_hh, fc_w, fc_b, h_in, c_in,
-                           h_out, c_out, y, (long long)y_stride, stash, (int)T, probe);
-    else
-        hipLaunchKernelGGL(lstm_fwd_kernel<4>, dim3((unsigned)B), dim3(512), 0, (hipStream_t)stream, x,
-                           (long long)x_stride, lfo, (long long)lfo_stride, w_ih, w_hh, b_ih, b_hh, fc_w, fc_b, h_in, c_in,
-                           h_out, c_out, y, (long long)y_stride, stash, (int)T, probe);
+    // too: 0.284 vs 0.305 ms per 128 clips x 1024 steps (0.260 vs 0.315 without), and the 8-wave layout was retired.
+    hipLaunchKernelGGL(lstm_fwd_kernel, dim3((unsigned)B), dim3(LS_FWD_THREADS), 0, (hipStream_t)stream, x,
+                       (long long)x_stride, lfo, (long long)lfo_stride, w_ih, w_hh, b_ih, b_hh, fc_w, fc_b, h_in, c_in,
+                       h_out, c_out, y, (long long)y_stride, stash, (int)T, probe);
     return mx_launch_status();
 }
 
@@ -413,6 +371,8 @@ __device__ __forceinline__ int ls_dg_slot(int r)   // LDS slot of gate row r: [1
 #ifndef LSB_ABL
 #define LSB_ABL 0    // diagnostic builds only (tools/exp_lstm_bwd.py; wrong results): bit 0 helper waves idle, 1 no prefetch reads of the
 #endif               // stash values, 2 no slab staging after the first slab
+// Two instances are launched: <false, true> (the training step) and <true, false> (the gate-gradient variant, which does not fit the
+// 168 registers a wave has in a 12-wave workgroup and keeps the weight-gradient products in its recurrence waves).
 template <bool DGOUT, bool HELP>    // DGOUT: also write the gate gradients (B, T, 256) -- the input of mx_lstm_dlfo (an UNFROZEN LFO model, lightning.py:258,361)
 __global__ __launch_bounds__(LS_THREADS + (HELP ? 64 * LS_HELP_WAVES : 0)) void lstm_bwd_kernel(const float *__restrict__ x, long long xs,
                                                               const float *__restrict__ lfo, long long ls,
@@ -801,12 +761,10 @@ static int lstm_bwd_l1_launch(const float *x, int64_t x_stride, const float *lfo
         return MX_ERR_ARG;
     if (T >= (1ll << 30)) return MX_ERR_UNSUPPORTED;
     const size_t lds = (size_t)LS_BWD_LDS_FLOATS * sizeof(float);
-    // MODEX_LSTM_HELPERS=0: the round-5 kernel (weight-gradient matrix instructions inside the recurrence waves); default: on helper waves
-    static const bool help = !(getenv("MODEX_LSTM_HELPERS") && atoi(getenv("MODEX_LSTM_HELPERS")) == 0);
-    static MxLdsLatch latch[2][2] = {};                       // per device (common.h), per (DGOUT, HELP) instance
+    static MxLdsLatch latch[2] = {};                          // per device (common.h), per DGOUT instance
 #define LS_BWD_LAUNCH(DG, HP)                                                                                                       \
     {                                                                                                                               \
-        if (mx_set_dyn_lds(latch[DG][HP], (const void *)lstm_bwd_kernel<DG, HP>, lds) != MX_OK) return MX_ERR_LAUNCH;               \
+        if (mx_set_dyn_lds(latch[DG], (const void *)lstm_bwd_kernel<DG, HP>, lds) != MX_OK) return MX_ERR_LAUNCH;                   \
         hipLaunchKernelGGL((lstm_bwd_kernel<DG, HP>), dim3((unsigned)B), dim3(LS_THREADS + (HP ? 64 * LS_HELP_WAVES : 0)), lds,    \
                            (hipStream_t)stream, x, (long long)x_stride, lfo, (long long)lfo_stride, y, (long long)y_stride, wet,   \
                            (long long)wet_stride, stash, w_hh, fc_w, h_init, c_init, loss_scale, dy, (long long)dy_stride, part,   \
@@ -814,7 +772,7 @@ static int lstm_bwd_l1_launch(const float *x, int64_t x_stride, const float *lfo
         return mx_launch_status();                                                                                                  \
     }
     if (dgate) LS_BWD_LAUNCH(true, false)     // (168 registers per wave are not enough for this variant: it stays fused)
-    if (help) LS_BWD_LAUNCH(false, true) else LS_BWD_LAUNCH(false, false)
+    LS_BWD_LAUNCH(false, true)                // weight-gradient matrix instructions on helper waves
 #undef LS_BWD_LAUNCH
 }
 

@@ -66,6 +66,18 @@ def test_product_never_imports_oracle():
                 assert "liboracle_ref" not in src, f
 
 
+def test_library_reads_no_environment():
+    """abi.hip: every entry point is a function of its arguments and the stream -- no source of the library calls getenv."""
+    csrc = os.path.join(ROOT, "mod_extraction_amd", "csrc")
+    seen = 0
+    for d, _, files in os.walk(csrc):
+        for f in files:
+            if f.endswith((".hip", ".h")):
+                seen += 1
+                assert "getenv" not in open(os.path.join(d, f)).read(), f
+    assert seen >= 10
+
+
 def test_entry_points_reject_bad_arguments_before_touching_the_device(so_path):
     """Every entry point validates its arguments first and returns MX_ERR_ARG / MX_ERR_UNSUPPORTED (never throws, never
     launches): NULL pointers and non-positive sizes are refused here on a box without a GPU."""

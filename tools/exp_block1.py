@@ -1,9 +1,9 @@
-"""Ablation harness for the first block's forward kernel (conv1_f16x3_persist_kernel in conv_f16.hip): build -D variants
+"""Ablation harness for the first block's forward kernel (conv1_f16x3_tile_kernel in conv_f16.hip): build -D variants
 here, time mx_conv_block1_fwd_f16 on the GPU box with random operands at the headline size.
 
-    python tools/exp_block1.py build name1:-DC1_ABL=1 name2:...      (CPU container)
+    python tools/exp_block1.py build name1:-DC1T_ABL=1 name2:...     (CPU container)
     python tools/exp_block1.py run [B]                               (GPU box; every _lib/expb1_*.so)
-C1_ABL bits (wrong results): 1 = no epilogue, 2 = no matrix instructions, 4 = epilogue without its global stores,
+C1T_ABL bits (wrong results): 1 = no epilogue, 2 = no matrix instructions, 4 = epilogue without its global stores,
 8 = no LDS-DMA inside the loop (the prologue's patch is reused).
 """
 import ctypes
@@ -51,8 +51,6 @@ def run(B=256, H=256):
     for so in sorted(glob.glob(os.path.join(LIB, "expb1_*.so"))):
         lib = ctypes.CDLL(so)
         name = os.path.basename(so)[6:-3]
-        # the library reads the variable once (static): a variant whose name ends in "p1" runs the row-exchanging layout
-        os.environ["MODEX_BLOCK1_PERSIST"] = "1" if name.endswith("p1") else "3" if name.endswith("p3") else "2"
 
         def call():
             return lib.mx_conv_block1_fwd_f16(vp(x_hi.data_ptr()), vp(x_lo.data_ptr()), vp(w_hi[0].data_ptr()),
@@ -71,16 +69,7 @@ def run(B=256, H=256):
             e1.record()
             torch.cuda.synchronize()
             times.append(e0.elapsed_time(e1) / 10)
-        if hasattr(lib, "mx_diag_c1"):
-            buf = (ctypes.c_uint64 * 8)()
-            lib.mx_diag_c1(buf, 1)
-            call()
-            torch.cuda.synchronize()
-            lib.mx_diag_c1(buf, 0)
-            n = B * (H // 2)
-            print("   cycles per row pair (wave 0): head %.0f  taps %.0f  dma wait %.0f  epilogue (rest) %.0f | head barrier %.0f  five tiles %.0f  "
-                  "mid barrier %.0f  mid tile %.0f" % tuple(buf[i] / n for i in range(8)))
-        print(f"{name:24s} persist={os.environ['MODEX_BLOCK1_PERSIST']} {min(times):8.3f} ms  chk={float(out.float().abs().mean()):.6g}", flush=True)
+        print(f"{name:24s} {min(times):8.3f} ms  chk={float(out.float().abs().mean()):.6g}", flush=True)
 
 
 if __name__ == "__main__":
