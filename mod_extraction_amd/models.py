@@ -12,7 +12,7 @@ and state-dict keys; every forward/backward runs hand-written HIP kernels throug
 import logging
 import math
 import os
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 from torch import Tensor as T, nn
@@ -21,13 +21,13 @@ from . import _hip
 
 log = logging.getLogger(__name__)
 
-import os as _os
-
 # Arithmetic of the 64->64 channel convolutions (forward + data gradient):
 #   "f16x3"  fp16 matrix cores on split operands (hi + lo pairs, 3 MFMAs per product group) -- fp32-equivalent
 #            accuracy (csrc/conv_f16.hip), 5.3x the fp32 MFMA rate;   "f32"  exact fp32 MFMA (csrc/conv2d.hip).
-CONV_PRECISION = _os.environ.get("MODEX_CONV_PRECISION", "f16x3")
-DEBUG_TAP = None       # set to a dict to capture backward intermediates (tools/debug_cnn_bwd.py)
+CONV_PRECISION = os.environ.get("MODEX_CONV_PRECISION", "f16x3")
+# set to a dict to capture the backward's intermediates: G{l} (fp32 dL/dp of block l, where it exists), amax{l}, p{l}, dxhat{l}
+# (oracle.models.forward_routed replays the recorded decisions; tests/test_gpu_cnn.py, __graft_entry__.smoke)
+DEBUG_TAP = None
 PITCH = 352            # activation row pitch (floats); 345 frames + pad (csrc/conv_common.h)
 LN_EPS = 1e-5          # torch.nn.LayerNorm default
 
@@ -113,21 +113,6 @@ def specaugment_bounds(size: int, mask_param: int) -> Tuple[int, int]:
 # ---------------------------------------------------------------------------------------------
 # the CNN stack as one autograd node
 # ---------------------------------------------------------------------------------------------
-def _pack(w: T, flip: int) -> T:
-    out = torch.empty(w.numel(), device=w.device, dtype=torch.float32)
-    _hip.call("mx_conv_pack_weights", _hip.ptr(w.contiguous()), w.size(0), w.size(1), flip, _hip.ptr(out),
-              _hip.stream())
-    return out
-
-
-def _pack_f16(w: T, flip: int) -> Tuple[T, T]:
-    n = 4 * 5 * 13 * 64 * 16
-    hi = torch.empty(n, device=w.device, dtype=torch.float16)
-    lo = torch.empty(n, device=w.device, dtype=torch.float16)
-    _hip.call("mx_conv_pack_weights_f16", _hip.ptr(w.contiguous()), flip, _hip.ptr(hi), _hip.ptr(lo), _hip.stream())
-    return hi, lo
-
-
 # first block on the fp16 pipes too (MODEX_BLOCK1=f32 keeps it on the exact-fp32 MFMA kernel; A/B knob)
 BLOCK1_F16 = os.environ.get("MODEX_BLOCK1", "f16x3") != "f32"
 # weight gradient of the 64-channel blocks: sparse (2:4 along the pooling pair) or dense matrix instruction
@@ -144,14 +129,51 @@ LN_FUSED = os.environ.get("MODEX_LN", "fused") != "sweep"      # LayerNorm-backw
 # from the bound on max|G|) instead of fp32 values that the weight gradient scales / splits while staging ("0": round-4 route)
 BLOCK1_PAIR = os.environ.get("MODEX_BLOCK1_PAIR", "1") != "0"
 
+# workspace sizes in elements; KH / KW / TAPS / CO are CV_KH / CV_KW / CV_TAPS / CV_CO of csrc/conv_common.h
+KH, KW, TAPS, CO = 5, 13, 65, 64
+W_F16_ELEMS = 4 * KH * KW * CO * 16              # [ci / 16][kh][kw][khalf][co][8]: pack_weights_f16_kernel (csrc/conv_f16.hip)
+W_KVEC_ELEMS = KW * 2 * CO * 8                   # [kw][khalf][co][8], k = 2 kh + ci: pack_weights_kvec_f16_kernel (csrc/conv_f16.hip)
+W_SP_ELEMS = 4 * 3 * 2 * KW * 2 * 64 * 16        # [cb][m][r][kwf][ci tile][lane][16]: pack_weights_sp_f16_kernel (csrc/dgrad_sp_f16.hip)
+KVEC_PART_ELEMS = KW * CO * 16                   # per slab, (tap column, co, k): wgrad_kvec_f16_kernel (csrc/wgrad_kvec_f16.hip)
+WS_ROW_KS = 22                                   # WS_ROW_KS of csrc/wgrad_sp_f16.hip: index words per pooled row of 352 positions
 
-def _use_f16(cin: int, precision: str) -> bool:
-    return precision == "f16x3" and cin == 64
+
+def _wgrad_part(n_slabs: int, cin: int, dev) -> T:
+    """Per-slab partial sums (TAPS, CO, cin) of the 5 x 13 weight-gradient kernels (csrc/wgrad*.hip), reduced in fp64 by them."""
+    return torch.empty(n_slabs * TAPS * CO * cin, device=dev, dtype=torch.float32)
+
+
+def _slabs(rows: int, n_target: int) -> Tuple[int, int]:
+    """(rows per slab, slabs) when a weight gradient deals `rows` rows to about n_target workgroups per kernel row."""
+    rps = max(1, -(-rows // n_target))
+    return rps, -(-rows // rps)
+
+
+def _f16_pair(dev, *shape: int) -> Tuple[T, T]:
+    """The (hi, lo) halves of an f16x3 operand."""
+    return (torch.empty(shape, device=dev, dtype=torch.float16), torch.empty(shape, device=dev, dtype=torch.float16))
+
+
+def _f32(dev, *shape: int) -> T:
+    return torch.empty(shape, device=dev, dtype=torch.float32)
+
+
+def _pack(w: T, flip: int) -> T:
+    out = _f32(w.device, w.numel())
+    _hip.call("mx_conv_pack_weights", _hip.ptr(w.contiguous()), w.size(0), w.size(1), flip, _hip.ptr(out),
+              _hip.stream())
+    return out
+
+
+def _pack_f16(w: T, flip: int) -> Tuple[T, T]:
+    hi, lo = _f16_pair(w.device, W_F16_ELEMS)
+    _hip.call("mx_conv_pack_weights_f16", _hip.ptr(w.contiguous()), flip, _hip.ptr(hi), _hip.ptr(lo), _hip.stream())
+    return hi, lo
 
 
 def _reduce_rows(part: T, rows: int, cols: int, out: Optional[T] = None) -> T:
     if out is None:
-        out = torch.empty(cols, device=part.device, dtype=torch.float32)
+        out = _f32(part.device, cols)
     _hip.call("mx_reduce_rows", _hip.ptr(part), rows, cols, 0, _hip.ptr(out), _hip.stream())
     return out
 
@@ -183,91 +205,340 @@ def _direct_grad_views(params) -> Optional[List[T]]:
     return views
 
 
-def _pooled_only(l: int, cin: int, dilations, precision: str, n_frames: int) -> bool:
-    """Block l (0-based) consumes its gradient only as the pooled channels-last pair: f16x3, both gradients sparse."""
-    return (l > 0 and _use_f16(cin, precision) and WGRAD_SPARSE and DGRAD_SPARSE
-            and int(dilations[l]) <= WGRAD_SPARSE_MAX_T and n_frames <= PITCH - 1)
+# ---------------------------------------------------------------------------------------------
+# the route table: which kernels each block runs and what it receives from the block above
+# ---------------------------------------------------------------------------------------------
+class BlockRoute(NamedTuple):
+    """Everything the forward and the backward of one block branch on.  plan_stack() is the only place that reads the knobs."""
+    fwd: str                 # "f16x3": mx_conv_block_fwd_f16 | "kvec": mx_conv_block1_fwd_f16 (first block) | "f32": mx_conv_block_fwd
+    stats: str               # LayerNorm statistics: "sweep" (mx_plane_stats) | "epilogue" (mx_plane_stats_finish of the block above's sums)
+    leaves_stats: bool       # this block's forward epilogue leaves the sums for the next block's statistics
+    g_in: str                # gradient arriving from above: "f32" | "f32+gmax" (max|G| cell ready) | "pooled" (channels-last pair,
+    #                          dL/dp never in fp32) | "pair" (f16x3 pairs in place of the fp32 values, first block only)
+    operand: Optional[str]   # the forward's f16 operand pair in the backward: "kept" by the forward | "rederived" | None (not used)
+    wgrad: str               # "sparse" | "dense" (64-channel f16x3) | "kvec_pair" | "kvec_scaled" (first block) | "f32"
+    routed_pair: bool        # the full-resolution routed gradient pair is built (a dense f16x3 kernel consumes it)
+    dgrad: Optional[str]     # "sparse+ln" (epilogue leaves the LayerNorm-backward statistics) | "sparse" | "dense" | "f32" | None (block 0)
+    ln_bwd: Optional[str]    # gradient for the block below: "gpool" (mx_ln_prelu_bwd_gpool_f16) | "pair" (mx_ln_prelu_bwd_pair) |
+    #                          "plain+gmax" | "plain" (mx_ln_prelu_bwd with / without the max|G| cell; it takes ln_part iff
+    #                          dgrad == "sparse+ln") | None (block 0)
+
+    @property
+    def dgrad_sparse(self) -> bool:
+        return self.dgrad in ("sparse", "sparse+ln")
+
+
+def plan_stack(cin0: int, dilations: Sequence[int], precision: str, n_frames: int,
+               operands_kept: bool = True) -> Tuple[BlockRoute, ...]:
+    """The route of every block, from the configuration and the module knobs as they are NOW; touches no tensor.
+    operands_kept=False plans a backward that finds the forward's operand pairs gone (_CNNStack.backward)."""
+    n = len(dilations)
+    fits = n_frames <= PITCH - 1                # the sparse kernels take at most PITCH - 1 frames; the full pitch goes dense
+    blocks = []                                 # per block, without what depends on its neighbours
+    for l, t in enumerate(int(t) for t in dilations):
+        if precision == "f16x3" and (cin0 if l == 0 else CO) == 64:
+            # sparse matrix instruction: the pooled gradient is the compressed operand, the argmax its index bits.  Weight
+            # gradient: dilations <= 4 (for >= 8 the taps share no fragment blocks: dense kernel on the routed full-resolution
+            # pair); data gradient: every dilation
+            sp_w = WGRAD_SPARSE and t <= WGRAD_SPARSE_MAX_T and fits
+            sp_d = DGRAD_SPARSE and fits
+            dgrad = ("sparse+ln" if LN_FUSED else "sparse") if sp_d else "dense"
+            blocks.append(dict(fwd="f16x3", operand="kept" if operands_kept else "rederived", wgrad="sparse" if sp_w else "dense",
+                               routed_pair=not sp_w or (l > 0 and not sp_d), dgrad=dgrad if l > 0 else None))
+        elif precision == "f16x3" and l == 0 and cin0 == 2 and BLOCK1_F16 and t == 1:
+            # (the k-vector kernel is built for the undilated first block of every shipped config; a dilated one is "f32")
+            blocks.append(dict(fwd="kvec", operand=None, wgrad="f32", routed_pair=False, dgrad=None))
+        else:
+            blocks.append(dict(fwd="f32", operand=None, wgrad="f32", routed_pair=False, dgrad="f32" if l > 0 else None))
+    for l, b in enumerate(blocks):
+        b["stats"] = "epilogue" if l > 0 and blocks[l - 1]["leaves_stats"] else "sweep"
+        b["leaves_stats"] = STATS_FUSED and l + 1 < n and b["fwd"] != "f32"     # (the head takes the last block's output as it is)
+    # the gradient chain, from the head down: how block l's LayerNorm / PReLU backward hands dL/dp to block l - 1
+    blocks[-1]["g_in"] = "f32+gmax" if blocks[-1]["fwd"] == "f16x3" else "f32"     # mx_head_bwd takes max|G| while it writes G
+    kvec_kept = blocks[0]["fwd"] == "kvec" and operands_kept
+    for l in range(n - 1, 0, -1):
+        b, below = blocks[l], blocks[l - 1]
+        pooled_only = l > 1 and below["wgrad"] == "sparse" and below["dgrad"] in ("sparse", "sparse+ln")
+        if b["dgrad"] == "sparse+ln" and GPOOL_FUSED and pooled_only:
+            b["ln_bwd"], below["g_in"] = "gpool", "pooled"
+        elif b["dgrad"] == "sparse+ln" and BLOCK1_PAIR and l == 1 and kvec_kept:
+            b["ln_bwd"], below["g_in"] = "pair", "pair"
+        elif below["fwd"] == "f16x3" or (l == 1 and kvec_kept):
+            b["ln_bwd"], below["g_in"] = "plain+gmax", "f32+gmax"
+        else:
+            b["ln_bwd"], below["g_in"] = "plain", "f32"
+    blocks[0]["ln_bwd"] = None
+    if kvec_kept and blocks[0]["g_in"] != "f32":          # the k-vector weight gradient consumes the forward's own operand
+        blocks[0].update(operand="kept", wgrad="kvec_pair" if blocks[0]["g_in"] == "pair" else "kvec_scaled")
+    return tuple(BlockRoute(**b) for b in blocks)
+
+
+# ---------------------------------------------------------------------------------------------
+# the CNN stack as one autograd node: step functions, one per launch group, then the node
+# ---------------------------------------------------------------------------------------------
+class _Act(NamedTuple):
+    """What a block's forward hands to the next one."""
+    p: T                                  # (B, C, H, PITCH) pooled pre-activation (the log-mel planes for the first block)
+    slope: Optional[T] = None             # PReLU slope applied to p by its consumer
+    bias: Optional[T] = None              # the statistics sums below are taken of PReLU(out) - PReLU(bias)
+    stats_part: Optional[T] = None        # {sum, sum of squares} per pooled row from the forward epilogue (leaves_stats)
+
+
+class _Grad(NamedTuple):
+    """What the head / a block's LayerNorm backward hands to the block below, in the form that block's route.g_in names."""
+    G: Optional[T] = None                 # fp32 dL/dp ("f32", "f32+gmax"), or the f16x3 pairs written in its place ("pair")
+    gmax: Optional[T] = None              # the atomic-max cell holding max|G| bits ("f32+gmax")
+    pooled: Optional[tuple] = None        # (gc_hi, gc_lo, gc_idx, gidx, scale) ("pooled")
+    pair_scale: Optional[T] = None        # ("pair")
+    bsum: Optional[T] = None              # bias-gradient partials (B, 64); the head leaves none
+
+
+class _Split(NamedTuple):
+    """What a block's weight-gradient step leaves for its data gradient."""
+    G: Optional[T] = None                 # fp32 gradient (dgrad "f32")
+    dz: Tuple[Optional[T], Optional[T]] = (None, None)      # routed full-resolution pair (dgrad "dense")
+    gc: Tuple[Optional[T], ...] = (None, None, None)        # pooled channels-last pair + index words (dgrad "sparse*")
+    scale: Optional[T] = None
+    x16: Tuple[Optional[T], Optional[T]] = (None, None)     # the forward operand, read again by the "sparse+ln" epilogue
+
+
+class _ParamGrads:
+    """Where parameter gradients go: straight into the .grad views (direct) or into fresh tensors handed to autograd."""
+
+    def __init__(self, n: int, direct: Optional[List[T]]) -> None:
+        self.direct, self.grads = direct, [None] * n
+
+    def weight(self, i: int, w: T) -> T:
+        self.grads[i] = self.direct[i] if self.direct is not None else torch.empty_like(w)
+        return self.grads[i]
+
+    def reduce(self, i: int, part: T, rows: int, cols: int) -> None:
+        self.grads[i] = _reduce_rows(part, rows, cols, self.direct[i].view(-1) if self.direct is not None else None)
+
+    def for_autograd(self) -> List[Optional[T]]:
+        return [None] * len(self.grads) if self.direct is not None else self.grads     # in place: nothing to accumulate
+
+
+def _block_fwd(r: BlockRoute, x: _Act, w: T, b: T, a: T, n_frames: int, t: int, first: bool):
+    """LayerNorm statistics -> (operand prep) -> convolution + max-pool.  Returns (the next block's input, what the backward
+    saves, the f16 operand pair or None)."""
+    B, cin, H, _ = x.p.shape
+    dev, st = x.p.device, _hip.stream()
+    stats = _f32(dev, B, cin, 2)
+    if r.stats == "epilogue":
+        _hip.call("mx_plane_stats_finish", _hip.ptr(x.stats_part), _hip.ptr(x.bias), _hip.ptr(x.slope), B, cin, H,
+                  n_frames, LN_EPS, _hip.ptr(stats), st)
+    else:
+        _hip.call("mx_plane_stats", _hip.ptr(x.p), _hip.ptr(x.slope), B, cin, H, n_frames, LN_EPS, _hip.ptr(stats), st)
+    a_out = a.contiguous()
+    p = _f32(dev, B, 64, H // 2, PITCH)
+    amax = torch.empty((B, 64, H // 2, PITCH), device=dev, dtype=torch.uint8)
+    stats_part = _f32(dev, B, H // 2, 64, 2) if r.leaves_stats else None
+    operand = None
+    if r.fwd == "f16x3":
+        operand = _f16_pair(dev, B, H, 4, PITCH, 16)
+        _hip.call("mx_conv_prep_fwd_f16", _hip.ptr(x.p), _hip.ptr(stats), _hip.ptr(x.slope), B, H, n_frames,
+                  _hip.ptr(operand[0]), _hip.ptr(operand[1]), st)
+        w_hi, w_lo = _pack_f16(w, 0)
+        _hip.call("mx_conv_block_fwd_f16", _hip.ptr(operand[0]), _hip.ptr(operand[1]), _hip.ptr(w_hi), _hip.ptr(w_lo),
+                  _hip.ptr(b.contiguous()), B, H, n_frames, t, _hip.ptr(p), _hip.ptr(amax),
+                  _hip.ptr(a_out) if r.leaves_stats else None, _hip.ptr(stats_part), st)
+    elif r.fwd == "kvec":
+        # first block: (kernel row, channel) pairs are the operand's 16 channels; one K stage
+        operand = _f16_pair(dev, B, H, 1, PITCH, 16)
+        _hip.call("mx_conv_prep_fwd_kvec_f16", _hip.ptr(x.p), _hip.ptr(stats), B, H, n_frames, _hip.ptr(operand[0]),
+                  _hip.ptr(operand[1]), st)
+        wk_hi, wk_lo = _f16_pair(dev, W_KVEC_ELEMS)
+        _hip.call("mx_conv_pack_weights_kvec_f16", _hip.ptr(w.detach().contiguous()), _hip.ptr(wk_hi), _hip.ptr(wk_lo), st)
+        _hip.call("mx_conv_block1_fwd_f16", _hip.ptr(operand[0]), _hip.ptr(operand[1]), _hip.ptr(wk_hi), _hip.ptr(wk_lo),
+                  _hip.ptr(b.contiguous()), B, H, n_frames, _hip.ptr(p), _hip.ptr(amax),
+                  _hip.ptr(a_out) if r.leaves_stats else None, _hip.ptr(stats_part), st)
+    else:
+        wt = _pack(w, 0)
+        _hip.call("mx_conv_block_fwd", _hip.ptr(x.p), _hip.ptr(stats), _hip.ptr(x.slope), _hip.ptr(wt),
+                  _hip.ptr(b.contiguous()), B, cin, H, n_frames, t, 1 if first else 0, _hip.ptr(p), _hip.ptr(amax), st)
+    return _Act(p, a_out, b.contiguous(), stats_part), (x.p, stats, amax), operand
+
+
+def _head_bwd(r_last: BlockRoute, p_last: T, slope_last: T, wout: T, latent: T, out: T, d_out: T, d_latent: Optional[T],
+              n_frames: int, gmax_cell: T, pg: _ParamGrads, i_wout: int, i_slope: int) -> _Grad:
+    """Head backward: dL/dp of the last block (with max|G| for its f16x3 scale, taken while G is written: no sweep) and the
+    gradients of the head's weight and bias and of the last PReLU slope."""
+    B, L, Hl, dev = out.size(0), out.size(1), p_last.size(2), out.device
+    G = torch.empty_like(p_last)
+    dw_part, db_part, ds_part = _f32(dev, B, L * 64), _f32(dev, B, L), _f32(dev, B, 64)
+    gmax = gmax_cell if r_last.g_in == "f32+gmax" else None
+    _hip.call("mx_head_bwd", _hip.ptr(p_last), _hip.ptr(slope_last), _hip.ptr(wout.contiguous()),
+              _hip.ptr(latent), _hip.ptr(out), _hip.ptr(d_out), _hip.ptr(d_latent), B, 64, Hl, n_frames, L,
+              _hip.ptr(G), _hip.ptr(dw_part), _hip.ptr(db_part), _hip.ptr(ds_part), _hip.ptr(gmax), _hip.stream())
+    pg.reduce(i_wout, dw_part, B, L * 64)
+    pg.grads[i_wout] = pg.grads[i_wout].view_as(wout)
+    pg.reduce(i_wout + 1, db_part, B, L)
+    pg.reduce(i_slope, ds_part, B, 64)
+    return _Grad(G=G, gmax=gmax)
+
+
+def _wgrad_f16x3(r: BlockRoute, l: int, g: _Grad, kept: dict, x_in: T, stats: T, amax: T, slope_prev: Optional[T],
+                 n_frames: int, t: int, dW: T) -> _Split:
+    """Weight gradient of a 64-channel f16x3 block: gradient operands (unless they arrive pooled), the forward's operand pair
+    (kept, or derived again), then the sparse kernel on the pooled pair or the dense one on the routed pair."""
+    B, _, H, _ = x_in.shape
+    Hp, dev, st = H // 2, x_in.device, _hip.stream()
+    dz = _f16_pair(dev, B, H, 4, PITCH, 16) if r.routed_pair else (None, None)
+    if r.g_in == "pooled":
+        gc_hi, gc_lo, gc_idx, gidx, scale = g.pooled         # made by the LayerNorm backward of the block above
+    else:
+        ready = r.g_in == "f32+gmax"
+        ws = g.gmax if ready else torch.empty(1, device=dev, dtype=torch.int32)
+        scale = _f32(dev, 2)
+        _hip.call("mx_conv_prep_dgrad_f16", _hip.ptr(g.G), _hip.ptr(amax), B, H, n_frames, _hip.ptr(ws),
+                  1 if ready else 0, _hip.ptr(scale), _hip.ptr(dz[0]), _hip.ptr(dz[1]), st)
+        gc_hi = gc_lo = gc_idx = gidx = None
+        if r.wgrad == "sparse" or r.dgrad_sparse:
+            # one pass over G: the channels-last pooled pair both sparse kernels read, the data gradient's index
+            # words and (for the weight gradient) the planar ones
+            gc_hi, gc_lo = _f16_pair(dev, B, Hp, 4, PITCH, 16)
+            gc_idx = torch.empty((B, Hp, 4, PITCH), device=dev, dtype=torch.int32)
+            if r.wgrad == "sparse":
+                gidx = torch.empty((B, 64, Hp, WS_ROW_KS, 2), device=dev, dtype=torch.int16)
+            _hip.call("mx_conv_prep_gpool_cl_f16", _hip.ptr(g.G), _hip.ptr(amax), _hip.ptr(scale), B, H, n_frames,
+                      _hip.ptr(gc_hi), _hip.ptr(gc_lo), _hip.ptr(gc_idx), _hip.ptr(gidx), st)
+    if r.operand == "kept":
+        x_hi, x_lo = kept.pop(l)              # released when its last consumer (this step, or the data gradient) has been launched
+    else:
+        x_hi, x_lo = _f16_pair(dev, B, H, 4, PITCH, 16)
+        _hip.call("mx_conv_prep_fwd_f16", _hip.ptr(x_in), _hip.ptr(stats), _hip.ptr(slope_prev), B, H, n_frames,
+                  _hip.ptr(x_hi), _hip.ptr(x_lo), st)
+    # 256 slabs x 5 kernel rows = 5 full rounds of 256 workgroups
+    rps, n_slabs = _slabs(B * Hp if r.wgrad == "sparse" else B * H, 256)
+    part = _wgrad_part(n_slabs, 64, dev)
+    if r.wgrad == "sparse":
+        _hip.call("mx_conv_block_wgrad_sp_f16", _hip.ptr(gc_hi), _hip.ptr(gc_lo), _hip.ptr(gidx), _hip.ptr(x_hi),
+                  _hip.ptr(x_lo), _hip.ptr(scale), B, H, n_frames, t, rps, _hip.ptr(part), _hip.ptr(dW), st)
+    else:
+        _hip.call("mx_conv_block_wgrad_f16", _hip.ptr(dz[0]), _hip.ptr(dz[1]), _hip.ptr(x_hi), _hip.ptr(x_lo),
+                  _hip.ptr(scale), B, H, t, rps, _hip.ptr(part), _hip.ptr(dW), st)
+    return _Split(dz=dz if r.dgrad == "dense" else (None, None), gc=(gc_hi, gc_lo, gc_idx), scale=scale,
+                  x16=(x_hi, x_lo) if r.dgrad == "sparse+ln" else (None, None))
+
+
+def _weight_grad(r: BlockRoute, l: int, g: _Grad, kept: dict, x_in: T, stats: T, amax: T, slope_prev: Optional[T],
+                 n_frames: int, t: int, dW: T) -> _Split:
+    if r.fwd == "f16x3":
+        return _wgrad_f16x3(r, l, g, kept, x_in, stats, amax, slope_prev, n_frames, t, dW)
+    B, cin, H, _ = x_in.shape
+    dev, st = x_in.device, _hip.stream()
+    if r.wgrad in ("kvec_pair", "kvec_scaled"):
+        # first block on the fp16 pipes: the kept k-vector operand; the gradient is routed while staging and arrives either as
+        # f16x3 pairs (mx_ln_prelu_bwd_pair) or in fp32 with its max|G| cell (then scaled / split on the fly too)
+        xk_hi, xk_lo = kept.pop(l)
+        rps, n_slabs = _slabs(B * H, 2048)
+        part = _f32(dev, n_slabs * KVEC_PART_ELEMS)
+        if r.wgrad == "kvec_pair":
+            _hip.call("mx_conv_block1_wgrad_pair_f16", _hip.ptr(g.G), _hip.ptr(amax), _hip.ptr(g.pair_scale), _hip.ptr(xk_hi),
+                      _hip.ptr(xk_lo), B, H, n_frames, rps, _hip.ptr(part), _hip.ptr(dW), st)
+        else:
+            scale1 = _f32(dev, 2)
+            _hip.call("mx_conv_block1_wgrad_f16", _hip.ptr(g.G), _hip.ptr(amax), _hip.ptr(g.gmax), _hip.ptr(xk_hi),
+                      _hip.ptr(xk_lo), B, H, n_frames, rps, _hip.ptr(scale1), _hip.ptr(part), _hip.ptr(dW), st)
+    else:
+        rps, n_slabs = _slabs(B * H, 256 if cin == 64 else 1024)
+        part = _wgrad_part(n_slabs, cin, dev)
+        _hip.call("mx_conv_block_wgrad", _hip.ptr(g.G), _hip.ptr(amax), _hip.ptr(x_in), _hip.ptr(stats),
+                  _hip.ptr(slope_prev), B, cin, H, n_frames, t, rps, _hip.ptr(part), _hip.ptr(dW), st)
+    return _Split(G=g.G)
+
+
+def _data_grad(r: BlockRoute, l: int, d: _Split, w: T, amax: T, B: int, H: int, n_frames: int, t: int, zws: T):
+    """dL/dxhat of block l > 0.  Returns (dxhat, ln_part, gx_bits): with dgrad "sparse+ln" the epilogue also leaves the plane
+    statistics of the LayerNorm backward below (x = xhat) and, when that pass needs its scale before it runs ("gpool",
+    "pair"), max|dxhat| / max|xhat| in the block's first two atomic-max cells."""
+    dev, st = w.device, _hip.stream()
+    dxhat = _f32(dev, B, 64, H, PITCH)
+    ln_part = gx_bits = None
+    if r.dgrad_sparse:
+        # sparse matrix instruction, transposed tiles: pooled channels-last gradient x fragment-packed weights
+        ws_hi, ws_lo = _f16_pair(dev, W_SP_ELEMS)
+        _hip.call("mx_conv_pack_weights_sp_f16", _hip.ptr(w.detach().contiguous()), _hip.ptr(ws_hi), _hip.ptr(ws_lo), st)
+        if r.dgrad == "sparse+ln":
+            ln_part = _f32(dev, B, 64, H, 2, 2)
+            gx_bits = zws[4 * l:4 * l + 2] if r.ln_bwd in ("gpool", "pair") else None
+        _hip.call("mx_conv_block_dgrad_sp_f16", _hip.ptr(d.gc[0]), _hip.ptr(d.gc[1]), _hip.ptr(d.gc[2]),
+                  _hip.ptr(ws_hi), _hip.ptr(ws_lo), _hip.ptr(d.scale), B, H, n_frames, t,
+                  _hip.ptr(dxhat), _hip.ptr(d.x16[0]), _hip.ptr(d.x16[1]), _hip.ptr(ln_part), _hip.ptr(gx_bits), st)
+    elif r.dgrad == "dense":
+        w_hi, w_lo = _pack_f16(w, 1)
+        _hip.call("mx_conv_block_dgrad_f16", _hip.ptr(d.dz[0]), _hip.ptr(d.dz[1]), _hip.ptr(w_hi), _hip.ptr(w_lo),
+                  _hip.ptr(d.scale), B, H, n_frames, t, _hip.ptr(dxhat), st)
+    else:
+        wt_f = _pack(w, 1)
+        _hip.call("mx_conv_block_dgrad", _hip.ptr(d.G), _hip.ptr(amax), _hip.ptr(wt_f), B, H, n_frames, t, _hip.ptr(dxhat), st)
+    if DEBUG_TAP is not None:
+        DEBUG_TAP[f"dxhat{l}"] = dxhat.clone()
+    return dxhat, ln_part, gx_bits
+
+
+def _ln_prelu_bwd(r: BlockRoute, l: int, x_in: T, dxhat: T, ln_part: Optional[T], gx_bits: Optional[T], stats: T,
+                  slope_prev: T, amax_below: T, n_frames: int, zws: T) -> Tuple[_Grad, T]:
+    """LayerNorm / PReLU backward of block l > 0: dL/dp of block l - 1 in the form r.ln_bwd names, with that block's bias-gradient
+    partials, and the partials of d loss / d slope (returned beside it)."""
+    B, _, H, _ = x_in.shape
+    dev, st = x_in.device, _hip.stream()
+    ds_part, bsum = _f32(dev, B, 64), _f32(dev, B, 64)
+    if r.ln_bwd in ("gpool", "pair"):
+        # the f16x3 scale must be known before the pass: from a bound on max|G| (csrc/dgrad_sp_f16.hip)
+        m12, scale_n = _f32(dev, B, 64, 2), _f32(dev, 2)
+        bound_ws = torch.empty(1, device=dev, dtype=torch.int32)
+        _hip.call("mx_ln_bwd_finish", _hip.ptr(ln_part), _hip.ptr(stats), _hip.ptr(slope_prev), _hip.ptr(gx_bits),
+                  B, 64, H, n_frames, _hip.ptr(m12), _hip.ptr(bound_ws), _hip.ptr(scale_n), st)
+    if r.ln_bwd == "gpool":
+        # dL/dp of the block below never exists in fp32: LayerNorm / PReLU backward -> scale -> split -> channels-last
+        # pooled pair + index words, one pass
+        gn_hi, gn_lo = _f16_pair(dev, B, H, 4, PITCH, 16)
+        gn_idx = torch.empty((B, H, 4, PITCH), device=dev, dtype=torch.int32)
+        gn_pidx = torch.empty((B, 64, H, WS_ROW_KS, 2), device=dev, dtype=torch.int16)
+        part2 = _f32(dev, B, 64, H, 6, 2)
+        _hip.call("mx_ln_prelu_bwd_gpool_f16", _hip.ptr(x_in), _hip.ptr(dxhat), _hip.ptr(amax_below),
+                  _hip.ptr(stats), _hip.ptr(slope_prev), _hip.ptr(m12), _hip.ptr(scale_n), B, H, n_frames,
+                  _hip.ptr(gn_hi), _hip.ptr(gn_lo), _hip.ptr(gn_idx), _hip.ptr(gn_pidx), _hip.ptr(part2),
+                  _hip.ptr(ds_part), _hip.ptr(bsum), st)
+        return _Grad(pooled=(gn_hi, gn_lo, gn_idx, gn_pidx, scale_n), bsum=bsum), ds_part
+    if r.ln_bwd == "pair":
+        # the first block's gradient as f16x3 pairs, written in place of dxhat
+        _hip.call("mx_ln_prelu_bwd_pair", _hip.ptr(x_in), _hip.ptr(dxhat), _hip.ptr(stats), _hip.ptr(slope_prev),
+                  B, 64, H, n_frames, _hip.ptr(ds_part), _hip.ptr(bsum), _hip.ptr(ln_part), _hip.ptr(scale_n), st)
+        return _Grad(G=dxhat, pair_scale=scale_n, bsum=bsum), ds_part
+    gmax = zws[4 * l + 2:4 * l + 3] if r.ln_bwd == "plain+gmax" else None
+    _hip.call("mx_ln_prelu_bwd", _hip.ptr(x_in), _hip.ptr(dxhat), _hip.ptr(stats), _hip.ptr(slope_prev),
+              B, 64, H, n_frames, _hip.ptr(ds_part), _hip.ptr(bsum), _hip.ptr(gmax), _hip.ptr(ln_part), st)
+    return _Grad(G=dxhat, gmax=gmax, bsum=bsum), ds_part
 
 
 class _CNNStack(torch.autograd.Function):
     """logmel (B,Cin,H,PITCH) -> (sigmoid output (B,L,W), latent (B,64,W)).
-    params: [w1,b1,a1, ..., w6,b6,a6, wout, bout]."""
+    params: [w1,b1,a1, ..., w6,b6,a6, wout, bout].  Which kernels run is read off plan_stack()'s table, nowhere else."""
 
     @staticmethod
     def forward(ctx, logmel: T, n_frames: int, dilations: Tuple[int, ...], precision: str, *params: T):
         n_blocks = len(dilations)
-        B, cin, H, _ = logmel.shape
-        dev = logmel.device
-        st = _hip.stream()
-        cur, slope = logmel, None
-        stats_part = None                 # {sum, sum of squares} per pooled row left by the previous block's forward epilogue
-        prev_bias = None                  # ... taken of PReLU(out) - PReLU(bias): the finish pass needs that bias
-        saved: List[T] = []
-        # the fp16 operand pairs of the 64-channel blocks are kept for the weight gradient when a backward pass
-        # will follow (5.9 GB at 256 clips x 2 s: cheaper than re-deriving them from the saved activations)
-        keep_splits = any(ctx.needs_input_grad)
-        ctx.splits = {}
-        for l in range(n_blocks):
-            w, b, a = params[3 * l], params[3 * l + 1], params[3 * l + 2]
-            stats = torch.empty((B, cin, 2), device=dev, dtype=torch.float32)
-            if stats_part is not None:
-                _hip.call("mx_plane_stats_finish", _hip.ptr(stats_part), _hip.ptr(prev_bias), _hip.ptr(slope), B, cin, H,
-                          n_frames, LN_EPS, _hip.ptr(stats), st)
-            else:
-                _hip.call("mx_plane_stats", _hip.ptr(cur), _hip.ptr(slope), B, cin, H, n_frames, LN_EPS,
-                          _hip.ptr(stats), st)
-            stats_part = None
-            fuse_stats = STATS_FUSED and l + 1 < n_blocks          # (the head takes the last block's output as it is)
-            a_out = a.contiguous()
-            p = torch.empty((B, 64, H // 2, PITCH), device=dev, dtype=torch.float32)
-            amax = torch.empty((B, 64, H // 2, PITCH), device=dev, dtype=torch.uint8)
-            if _use_f16(cin, precision):
-                x_hi = torch.empty((B, H, 4, PITCH, 16), device=dev, dtype=torch.float16)
-                x_lo = torch.empty((B, H, 4, PITCH, 16), device=dev, dtype=torch.float16)
-                _hip.call("mx_conv_prep_fwd_f16", _hip.ptr(cur), _hip.ptr(stats), _hip.ptr(slope), B, H, n_frames,
-                          _hip.ptr(x_hi), _hip.ptr(x_lo), st)
-                w_hi, w_lo = _pack_f16(w, 0)
-                if fuse_stats:
-                    stats_part = torch.empty((B, H // 2, 64, 2), device=dev, dtype=torch.float32)
-                _hip.call("mx_conv_block_fwd_f16", _hip.ptr(x_hi), _hip.ptr(x_lo), _hip.ptr(w_hi), _hip.ptr(w_lo),
-                          _hip.ptr(b.contiguous()), B, H, n_frames, int(dilations[l]), _hip.ptr(p), _hip.ptr(amax),
-                          _hip.ptr(a_out) if fuse_stats else None, _hip.ptr(stats_part), st)
-                if keep_splits:
-                    ctx.splits[l] = (x_hi, x_lo)
-                del x_hi, x_lo
-            elif precision == "f16x3" and l == 0 and cin == 2 and BLOCK1_F16 and int(dilations[0]) == 1:
-                # first block: (kernel row, channel) pairs are the operand's 16 channels; one K stage (the kernel is built for
-                # the undilated first block of every shipped config; a dilated one takes the exact-fp32 kernel below)
-                xk_hi = torch.empty((B, H, 1, PITCH, 16), device=dev, dtype=torch.float16)
-                xk_lo = torch.empty((B, H, 1, PITCH, 16), device=dev, dtype=torch.float16)
-                _hip.call("mx_conv_prep_fwd_kvec_f16", _hip.ptr(cur), _hip.ptr(stats), B, H, n_frames, _hip.ptr(xk_hi),
-                          _hip.ptr(xk_lo), st)
-                wk_hi = torch.empty(13 * 2 * 64 * 8, device=dev, dtype=torch.float16)
-                wk_lo = torch.empty(13 * 2 * 64 * 8, device=dev, dtype=torch.float16)
-                _hip.call("mx_conv_pack_weights_kvec_f16", _hip.ptr(w.detach().contiguous()), _hip.ptr(wk_hi),
-                          _hip.ptr(wk_lo), st)
-                if fuse_stats:
-                    stats_part = torch.empty((B, H // 2, 64, 2), device=dev, dtype=torch.float32)
-                _hip.call("mx_conv_block1_fwd_f16", _hip.ptr(xk_hi), _hip.ptr(xk_lo), _hip.ptr(wk_hi), _hip.ptr(wk_lo),
-                          _hip.ptr(b.contiguous()), B, H, n_frames, _hip.ptr(p), _hip.ptr(amax),
-                          _hip.ptr(a_out) if fuse_stats else None, _hip.ptr(stats_part), st)
-                if keep_splits:
-                    ctx.splits[l] = (xk_hi, xk_lo)              # the weight gradient consumes the same operand
-                del xk_hi, xk_lo
-            else:
-                wt = _pack(w, 0)
-                _hip.call("mx_conv_block_fwd", _hip.ptr(cur), _hip.ptr(stats), _hip.ptr(slope), _hip.ptr(wt),
-                          _hip.ptr(b.contiguous()), B, cin, H, n_frames, int(dilations[l]), 1 if l == 0 else 0,
-                          _hip.ptr(p), _hip.ptr(amax), st)
-            saved += [cur, stats, amax]
-            cur, slope, cin, H, prev_bias = p, a_out, 64, H // 2, b.contiguous()
+        routes = plan_stack(logmel.size(1), dilations, precision, n_frames)
+        # the fp16 operand pairs the weight gradients consume are kept when a backward pass will follow (5.9 GB at
+        # 256 clips x 2 s: cheaper than re-deriving them from the saved activations)
+        keep = any(ctx.needs_input_grad)
+        ctx.operands = {}
+        x, saved = _Act(logmel), []
+        for l, r in enumerate(routes):
+            x, for_bwd, operand = _block_fwd(r, x, *params[3 * l:3 * l + 3], n_frames, int(dilations[l]), l == 0)
+            saved += for_bwd
+            if keep and r.operand == "kept":
+                ctx.operands[l] = operand
+            del operand
         wout, bout = params[3 * n_blocks], params[3 * n_blocks + 1]
-        L = wout.size(0)
-        latent = torch.empty((B, 64, n_frames), device=dev, dtype=torch.float32)
-        out = torch.empty((B, L, n_frames), device=dev, dtype=torch.float32)
-        _hip.call("mx_head_fwd", _hip.ptr(cur), _hip.ptr(slope), _hip.ptr(wout.contiguous()),
-                  _hip.ptr(bout.contiguous()), B, 64, H, n_frames, L, _hip.ptr(latent), _hip.ptr(out), st)
-        ctx.save_for_backward(*saved, cur, latent, out, *params)
+        B, H, L, dev = logmel.size(0), x.p.size(2), wout.size(0), logmel.device
+        latent, out = _f32(dev, B, 64, n_frames), _f32(dev, B, L, n_frames)
+        _hip.call("mx_head_fwd", _hip.ptr(x.p), _hip.ptr(x.slope), _hip.ptr(wout.contiguous()),
+                  _hip.ptr(bout.contiguous()), B, 64, H, n_frames, L, _hip.ptr(latent), _hip.ptr(out), _hip.stream())
+        ctx.save_for_backward(*saved, x.p, latent, out, *params)
         ctx.param_objs = params               # the Parameter objects themselves: their .grad views are looked up in backward
         ctx.meta = (n_frames, tuple(dilations), n_blocks, precision)
         return out, latent
@@ -276,230 +547,50 @@ class _CNNStack(torch.autograd.Function):
     def backward(ctx, d_out: Optional[T], d_latent: Optional[T]):
         n_frames, dilations, n_blocks, precision = ctx.meta
         tensors = ctx.saved_tensors
-        saved, p_last, latent, out = tensors[:3 * n_blocks], tensors[3 * n_blocks], tensors[3 * n_blocks + 1], \
-            tensors[3 * n_blocks + 2]
-        params = tensors[3 * n_blocks + 3:]
-        dev = out.device
-        st = _hip.stream()
-        B, L = out.size(0), out.size(1)
-        wout = params[3 * n_blocks]
-        grads: List[Optional[T]] = [None] * len(params)
-        direct = _direct_grad_views(ctx.param_objs) if DIRECT_GRADS else None
-
-        def gout(i: int) -> Optional[T]:          # where parameter i's gradient is written: its .grad view, or a fresh tensor
-            return direct[i].view(-1) if direct is not None else None
-        if d_out is None:
-            d_out = torch.zeros_like(out)
-        d_out = d_out.contiguous()
+        saved, (p_last, latent, out), params = tensors[:3 * n_blocks], tensors[3 * n_blocks:3 * n_blocks + 3], \
+            tensors[3 * n_blocks + 3:]
+        # Kept-operand rule: the first backward consumes the operand pairs the forward kept and releases each one as soon as its
+        # last consumer has been launched.  A second backward through a retained graph finds them gone: it is planned with
+        # operands_kept=False, i.e. the 64-channel blocks derive their operands again (mx_conv_prep_fwd_f16) and block 0 takes
+        # the exact-fp32 weight gradient (mx_conv_block_wgrad), with the gradient handed to it in plain fp32.
+        kept, ctx.operands = ctx.operands, None
+        routes = plan_stack(saved[0].size(1), dilations, precision, n_frames, operands_kept=kept is not None)
+        B, dev = out.size(0), out.device
+        pg = _ParamGrads(len(params), _direct_grad_views(ctx.param_objs) if DIRECT_GRADS else None)
+        d_out = (d_out if d_out is not None else torch.zeros_like(out)).contiguous()
         d_latent = d_latent.contiguous() if d_latent is not None else None
-        Hl = p_last.size(2)
-        G = torch.empty_like(p_last)
-        dw_part = torch.empty((B, L * 64), device=dev, dtype=torch.float32)
-        db_part = torch.empty((B, L), device=dev, dtype=torch.float32)
-        ds_part = torch.empty((B, 64), device=dev, dtype=torch.float32)
-        slope_last = params[3 * (n_blocks - 1) + 2].contiguous()
-        # max|G| of the last block's gradient for its f16x3 scale: taken while G is written (no sweep)
         # one zeroed workspace for every atomic-max cell of this backward pass (each used to be its own fill launch): cells
-        # 4 l .. 4 l + 3 belong to block l
+        # 4 l .. 4 l + 3 belong to block l, cell 4 n_blocks to the head
         zws = torch.zeros(4 * (n_blocks + 1), device=dev, dtype=torch.int32)
-        pair_scale, pair1 = None, False   # the first block's gradient as f16x3 pairs (BLOCK1_PAIR)
-        gmax_ws = zws[4 * n_blocks:4 * n_blocks + 1] if _use_f16(saved[3 * (n_blocks - 1)].size(1), precision) else None
-        _hip.call("mx_head_bwd", _hip.ptr(p_last), _hip.ptr(slope_last), _hip.ptr(wout.contiguous()),
-                  _hip.ptr(latent), _hip.ptr(out), _hip.ptr(d_out), _hip.ptr(d_latent), B, 64, Hl, n_frames, L,
-                  _hip.ptr(G), _hip.ptr(dw_part), _hip.ptr(db_part), _hip.ptr(ds_part), _hip.ptr(gmax_ws), st)
-        grads[3 * n_blocks] = _reduce_rows(dw_part, B, L * 64, gout(3 * n_blocks)).view_as(wout)
-        grads[3 * n_blocks + 1] = _reduce_rows(db_part, B, L, gout(3 * n_blocks + 1))
-        grads[3 * (n_blocks - 1) + 2] = _reduce_rows(ds_part, B, 64, gout(3 * (n_blocks - 1) + 2))
-        bsum = None                      # by-product of mx_ln_prelu_bwd for the block below: bias partials (gmax_ws: max|G| bits)
-        pooled = None                    # (gc_hi, gc_lo, gc_idx, gidx, scale) left for the block below by the fused LN backward
+        g = _head_bwd(routes[-1], p_last, params[3 * (n_blocks - 1) + 2].contiguous(), params[3 * n_blocks], latent, out,
+                      d_out, d_latent, n_frames, zws[4 * n_blocks:4 * n_blocks + 1], pg, 3 * n_blocks, 3 * (n_blocks - 1) + 2)
         for l in range(n_blocks - 1, -1, -1):
-            x_in, stats, amax = saved[3 * l], saved[3 * l + 1], saved[3 * l + 2]
-            w = params[3 * l]
-            cin, H = x_in.size(1), x_in.size(2)
+            r, t = routes[l], int(dilations[l])
+            x_in, stats, amax = saved[3 * l:3 * l + 3]
+            H = x_in.size(2)
             slope_prev = params[3 * (l - 1) + 2].contiguous() if l > 0 else None
-            # bias gradient: sum of G over (b, h, w)
             if DEBUG_TAP is not None:
-                if G is not None and pair_scale is None:   # (with the fused LayerNorm backward dL/dp of blocks 2-4 never exists in fp32)
-                    DEBUG_TAP[f"G{l}"] = G.clone()
+                if r.g_in in ("f32", "f32+gmax"):      # (G{l} is absent where dL/dp never exists in fp32)
+                    DEBUG_TAP[f"G{l}"] = g.G.clone()
                 DEBUG_TAP[f"amax{l}"] = amax.clone()
                 DEBUG_TAP[f"p{l}"] = (p_last if l == n_blocks - 1 else saved[3 * (l + 1)]).clone()
+            # bias gradient: sum of G over (b, h, w), a by-product of the LayerNorm backward above (the head leaves none)
+            bsum = g.bsum
             if bsum is None:
-                assert G is not None
-                bsum = torch.empty((B, 64), device=dev, dtype=torch.float32)
-                _hip.call("mx_plane_sum", _hip.ptr(G), B * 64, H // 2, n_frames, _hip.ptr(bsum), st)
-            grads[3 * l + 1] = _reduce_rows(bsum, B, 64, gout(3 * l + 1))
-            bsum = None
-            # weight gradient (+ data gradient below) -- f16x3 path: both share the prepared operand pairs
-            rows = B * H
-            f16 = _use_f16(cin, precision)
-            dW = direct[3 * l] if direct is not None else torch.empty_like(w)
-            if f16:
-                dz_hi = dz_lo = None
-                ready = gmax_ws is not None
-                ws = gmax_ws if ready else torch.empty(1, device=dev, dtype=torch.int32)
-                gmax_ws = None
-                scale = torch.empty(2, device=dev, dtype=torch.float32)
-                # sparse matrix instruction: the pooled gradient is the compressed operand, the argmax its index bits.
-                # Weight gradient: dilations <= 4 (for >= 8 the taps share no fragment blocks: dense kernel on the routed
-                # full-resolution pair); data gradient: every dilation.
-                sparse = WGRAD_SPARSE and int(dilations[l]) <= WGRAD_SPARSE_MAX_T and n_frames <= PITCH - 1
-                sparse_d = DGRAD_SPARSE and l > 0 and n_frames <= PITCH - 1
-                gidx = gc_hi = gc_lo = gc_idx = None
-                Hp = H // 2
-                need_routed = (not sparse) or (l > 0 and not sparse_d)   # a dense kernel consumes the routed full-resolution pair
-                if need_routed:
-                    dz_hi = torch.empty((B, H, 4, PITCH, 16), device=dev, dtype=torch.float16)
-                    dz_lo = torch.empty((B, H, 4, PITCH, 16), device=dev, dtype=torch.float16)
-                if pooled is not None:
-                    gc_hi, gc_lo, gc_idx, gidx, scale = pooled       # made by the LayerNorm backward of the block above
-                    pooled = None
-                else:
-                    _hip.call("mx_conv_prep_dgrad_f16", _hip.ptr(G), _hip.ptr(amax), B, H, n_frames, _hip.ptr(ws),
-                              1 if ready else 0, _hip.ptr(scale), _hip.ptr(dz_hi), _hip.ptr(dz_lo), st)
-                if gc_hi is None and (sparse or sparse_d):
-                    # one pass over G: the channels-last pooled pair both sparse kernels read, the data gradient's index
-                    # words and (for the weight gradient) the planar ones
-                    gc_hi = torch.empty((B, Hp, 4, PITCH, 16), device=dev, dtype=torch.float16)
-                    gc_lo = torch.empty((B, Hp, 4, PITCH, 16), device=dev, dtype=torch.float16)
-                    gc_idx = torch.empty((B, Hp, 4, PITCH), device=dev, dtype=torch.int32)
-                    if sparse:
-                        gidx = torch.empty((B, 64, Hp, 22, 2), device=dev, dtype=torch.int16)
-                    _hip.call("mx_conv_prep_gpool_cl_f16", _hip.ptr(G), _hip.ptr(amax), _hip.ptr(scale), B, H, n_frames,
-                              _hip.ptr(gc_hi), _hip.ptr(gc_lo), _hip.ptr(gc_idx), _hip.ptr(gidx), st)
-                if l in ctx.splits:
-                    x_hi, x_lo = ctx.splits.pop(l)
-                else:
-                    x_hi = torch.empty((B, H, 4, PITCH, 16), device=dev, dtype=torch.float16)
-                    x_lo = torch.empty((B, H, 4, PITCH, 16), device=dev, dtype=torch.float16)
-                    _hip.call("mx_conv_prep_fwd_f16", _hip.ptr(x_in), _hip.ptr(stats), _hip.ptr(slope_prev), B, H,
-                              n_frames, _hip.ptr(x_hi), _hip.ptr(x_lo), st)
-                if sparse:
-                    prow = B * Hp
-                    rps = max(1, -(-prow // 256))           # 256 slabs x 5 kernel rows = 5 full rounds of 256 workgroups
-                    n_slabs = -(-prow // rps)
-                    part = torch.empty(n_slabs * 65 * 64 * 64, device=dev, dtype=torch.float32)
-                    _hip.call("mx_conv_block_wgrad_sp_f16", _hip.ptr(gc_hi), _hip.ptr(gc_lo), _hip.ptr(gidx), _hip.ptr(x_hi),
-                              _hip.ptr(x_lo), _hip.ptr(scale), B, H, n_frames, int(dilations[l]), rps, _hip.ptr(part),
-                              _hip.ptr(dW), st)
-                    del gidx
-                else:
-                    rps = max(1, -(-rows // 256))            # 256 slabs x 5 kernel rows = 5 full rounds of 256 workgroups
-                    n_slabs = -(-rows // rps)
-                    part = torch.empty(n_slabs * 65 * 64 * 64, device=dev, dtype=torch.float32)
-                    _hip.call("mx_conv_block_wgrad_f16", _hip.ptr(dz_hi), _hip.ptr(dz_lo), _hip.ptr(x_hi), _hip.ptr(x_lo),
-                              _hip.ptr(scale), B, H, int(dilations[l]), rps, _hip.ptr(part), _hip.ptr(dW), st)
-                del part
-                if not (sparse_d and LN_FUSED):
-                    del x_hi, x_lo
-            elif l == 0 and 0 in ctx.splits and pair_scale is not None:
-                # first block on the fp16 pipes, gradient already in f16x3 pairs (mx_ln_prelu_bwd_pair): routed while staging
-                xk_hi, xk_lo = ctx.splits.pop(0)
-                rps = max(1, -(-rows // 2048))
-                n_slabs = -(-rows // rps)
-                part = torch.empty(n_slabs * 13 * 64 * 16, device=dev, dtype=torch.float32)
-                _hip.call("mx_conv_block1_wgrad_pair_f16", _hip.ptr(G), _hip.ptr(amax), _hip.ptr(pair_scale), _hip.ptr(xk_hi),
-                          _hip.ptr(xk_lo), B, H, n_frames, rps, _hip.ptr(part), _hip.ptr(dW), st)
-                pair_scale = None
-                del part, xk_hi, xk_lo
-            elif l == 0 and 0 in ctx.splits and gmax_ws is not None:
-                # first block on the fp16 pipes: the kept k-vector operand, gradient routed / scaled / split on the fly
-                xk_hi, xk_lo = ctx.splits.pop(0)
-                rps = max(1, -(-rows // 2048))
-                n_slabs = -(-rows // rps)
-                part = torch.empty(n_slabs * 13 * 64 * 16, device=dev, dtype=torch.float32)
-                scale1 = torch.empty(2, device=dev, dtype=torch.float32)
-                _hip.call("mx_conv_block1_wgrad_f16", _hip.ptr(G), _hip.ptr(amax), _hip.ptr(gmax_ws), _hip.ptr(xk_hi),
-                          _hip.ptr(xk_lo), B, H, n_frames, rps, _hip.ptr(scale1), _hip.ptr(part), _hip.ptr(dW), st)
-                gmax_ws = None
-                del part, xk_hi, xk_lo
-            else:
-                rps = max(1, -(-rows // (256 if cin == 64 else 1024)))
-                n_slabs = -(-rows // rps)
-                part = torch.empty(n_slabs * 65 * 64 * cin, device=dev, dtype=torch.float32)
-                _hip.call("mx_conv_block_wgrad", _hip.ptr(G), _hip.ptr(amax), _hip.ptr(x_in), _hip.ptr(stats),
-                          _hip.ptr(slope_prev), B, cin, H, n_frames, int(dilations[l]), rps, _hip.ptr(part),
-                          _hip.ptr(dW), st)
-                del part
-            grads[3 * l] = dW
-            if l > 0:
-                dxhat = torch.empty((B, 64, H, PITCH), device=dev, dtype=torch.float32)
-                ln_part, fuse_g, pair1 = None, False, False
-                if f16 and sparse_d:
-                    # sparse matrix instruction, transposed tiles: pooled channels-last gradient x fragment-packed weights
-                    ws_hi = torch.empty(4 * 3 * 2 * 13 * 2 * 64 * 16, device=dev, dtype=torch.float16)
-                    ws_lo = torch.empty(4 * 3 * 2 * 13 * 2 * 64 * 16, device=dev, dtype=torch.float16)
-                    _hip.call("mx_conv_pack_weights_sp_f16", _hip.ptr(w.detach().contiguous()), _hip.ptr(ws_hi),
-                              _hip.ptr(ws_lo), st)
-                    if LN_FUSED:
-                        # the epilogue also leaves the plane statistics of the LayerNorm backward below (x = xhat) and, when
-                        # that pass writes the block below's pooled operand itself, max|dxhat| / max|xhat| for its scale
-                        ln_part = torch.empty((B, 64, H, 2, 2), device=dev, dtype=torch.float32)
-                        fuse_g = GPOOL_FUSED and _pooled_only(l - 1, saved[3 * (l - 1)].size(1), dilations, precision, n_frames)
-                        pair1 = BLOCK1_PAIR and l == 1 and 0 in ctx.splits and not fuse_g
-                        gx_bits = zws[4 * l:4 * l + 2] if (fuse_g or pair1) else None
-                        _hip.call("mx_conv_block_dgrad_sp_f16", _hip.ptr(gc_hi), _hip.ptr(gc_lo), _hip.ptr(gc_idx),
-                                  _hip.ptr(ws_hi), _hip.ptr(ws_lo), _hip.ptr(scale), B, H, n_frames, int(dilations[l]),
-                                  _hip.ptr(dxhat), _hip.ptr(x_hi), _hip.ptr(x_lo), _hip.ptr(ln_part), _hip.ptr(gx_bits), st)
-                        del x_hi, x_lo
-                    else:
-                        _hip.call("mx_conv_block_dgrad_sp_f16", _hip.ptr(gc_hi), _hip.ptr(gc_lo), _hip.ptr(gc_idx),
-                                  _hip.ptr(ws_hi), _hip.ptr(ws_lo), _hip.ptr(scale), B, H, n_frames, int(dilations[l]),
-                                  _hip.ptr(dxhat), None, None, None, None, st)
-                    del gc_hi, gc_lo, gc_idx
-                elif f16:
-                    w_hi, w_lo = _pack_f16(w, 1)
-                    _hip.call("mx_conv_block_dgrad_f16", _hip.ptr(dz_hi), _hip.ptr(dz_lo), _hip.ptr(w_hi), _hip.ptr(w_lo),
-                              _hip.ptr(scale), B, H, n_frames, int(dilations[l]), _hip.ptr(dxhat), st)
-                    del dz_hi, dz_lo
-                else:
-                    wt_f = _pack(w, 1)
-                    _hip.call("mx_conv_block_dgrad", _hip.ptr(G), _hip.ptr(amax), _hip.ptr(wt_f), B, H, n_frames,
-                              int(dilations[l]), _hip.ptr(dxhat), st)
-                if DEBUG_TAP is not None:
-                    DEBUG_TAP[f"dxhat{l}"] = dxhat.clone()
-                ds_part = torch.empty((B, 64), device=dev, dtype=torch.float32)
-                bsum = torch.empty((B, 64), device=dev, dtype=torch.float32)
-                if fuse_g:
-                    # dL/dp of the block below never exists in fp32: LayerNorm / PReLU backward -> scale from a bound on
-                    # max|G| -> split -> channels-last pooled pair + index words, one pass (csrc/dgrad_sp_f16.hip)
-                    m12 = torch.empty((B, 64, 2), device=dev, dtype=torch.float32)
-                    bound_ws = torch.empty(1, device=dev, dtype=torch.int32)
-                    scale_n = torch.empty(2, device=dev, dtype=torch.float32)
-                    _hip.call("mx_ln_bwd_finish", _hip.ptr(ln_part), _hip.ptr(stats), _hip.ptr(slope_prev), _hip.ptr(gx_bits),
-                              B, 64, H, n_frames, _hip.ptr(m12), _hip.ptr(bound_ws), _hip.ptr(scale_n), st)
-                    gn_hi = torch.empty((B, H, 4, PITCH, 16), device=dev, dtype=torch.float16)
-                    gn_lo = torch.empty((B, H, 4, PITCH, 16), device=dev, dtype=torch.float16)
-                    gn_idx = torch.empty((B, H, 4, PITCH), device=dev, dtype=torch.int32)
-                    gn_pidx = torch.empty((B, 64, H, 22, 2), device=dev, dtype=torch.int16)
-                    part2 = torch.empty((B, 64, H, 6, 2), device=dev, dtype=torch.float32)
-                    _hip.call("mx_ln_prelu_bwd_gpool_f16", _hip.ptr(x_in), _hip.ptr(dxhat), _hip.ptr(saved[3 * (l - 1) + 2]),
-                              _hip.ptr(stats), _hip.ptr(slope_prev), _hip.ptr(m12), _hip.ptr(scale_n), B, H, n_frames,
-                              _hip.ptr(gn_hi), _hip.ptr(gn_lo), _hip.ptr(gn_idx), _hip.ptr(gn_pidx), _hip.ptr(part2),
-                              _hip.ptr(ds_part), _hip.ptr(bsum), st)
-                    pooled = (gn_hi, gn_lo, gn_idx, gn_pidx, scale_n)
-                    gmax_ws, G = None, None
-                    del part2, m12, dxhat
-                elif pair1:
-                    # the first block's gradient as f16x3 pairs, in place: scale from the bound on max|G| (known before the pass)
-                    m12 = torch.empty((B, 64, 2), device=dev, dtype=torch.float32)
-                    bound_ws = torch.empty(1, device=dev, dtype=torch.int32)
-                    pair_scale = torch.empty(2, device=dev, dtype=torch.float32)
-                    _hip.call("mx_ln_bwd_finish", _hip.ptr(ln_part), _hip.ptr(stats), _hip.ptr(slope_prev), _hip.ptr(gx_bits),
-                              B, 64, H, n_frames, _hip.ptr(m12), _hip.ptr(bound_ws), _hip.ptr(pair_scale), st)
-                    _hip.call("mx_ln_prelu_bwd_pair", _hip.ptr(x_in), _hip.ptr(dxhat), _hip.ptr(stats), _hip.ptr(slope_prev),
-                              B, 64, H, n_frames, _hip.ptr(ds_part), _hip.ptr(bsum), _hip.ptr(ln_part), _hip.ptr(pair_scale), st)
-                    G, gmax_ws = dxhat, None
-                    del m12
-                else:
-                    want_gmax = _use_f16(saved[3 * (l - 1)].size(1), precision) or (l == 1 and 0 in ctx.splits)
-                    gmax_ws = zws[4 * l + 2:4 * l + 3] if want_gmax else None
-                    _hip.call("mx_ln_prelu_bwd", _hip.ptr(x_in), _hip.ptr(dxhat), _hip.ptr(stats), _hip.ptr(slope_prev),
-                              B, 64, H, n_frames, _hip.ptr(ds_part), _hip.ptr(bsum), _hip.ptr(gmax_ws), _hip.ptr(ln_part), st)
-                    G = dxhat
-                grads[3 * (l - 1) + 2] = _reduce_rows(ds_part, B, 64, gout(3 * (l - 1) + 2))
-        if direct is not None:                      # already in place: autograd has nothing to accumulate
-            grads = [None] * len(params)
-        return (None, None, None, None, *grads)
+                bsum = _f32(dev, B, 64)
+                _hip.call("mx_plane_sum", _hip.ptr(g.G), B * 64, H // 2, n_frames, _hip.ptr(bsum), _hip.stream())
+            pg.reduce(3 * l + 1, bsum, B, 64)
+            d = _weight_grad(r, l, g, kept, x_in, stats, amax, slope_prev, n_frames, t, pg.weight(3 * l, params[3 * l]))
+            del g, bsum                          # (these releases decide the peak of a 256-clip step)
+            if l == 0:
+                break
+            dxhat, ln_part, gx_bits = _data_grad(r, l, d, params[3 * l], amax, B, H, n_frames, t, zws)
+            del d                                # operand pairs: gone before the LayerNorm backward allocates the next ones
+            g, ds_part = _ln_prelu_bwd(r, l, x_in, dxhat, ln_part, gx_bits, stats, slope_prev, saved[3 * (l - 1) + 2],
+                                       n_frames, zws)
+            del dxhat, ln_part
+            pg.reduce(3 * (l - 1) + 2, ds_part, B, 64)
+        return (None, None, None, None, *pg.for_autograd())
 
 
 class Spectral2DCNN(nn.Module):

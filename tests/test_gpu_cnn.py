@@ -117,11 +117,14 @@ def test_cnn_forward_backward(dev, n_samples, n_mels, B, precision):
     run_pair(dev, ref, mine, audio(B, n_samples), (3, 11, 20, 41))
 
 
-@pytest.mark.parametrize("knob", ["GPOOL_FUSED", "STATS_FUSED", "LN_FUSED"])
+@pytest.mark.parametrize("knob", ["GPOOL_FUSED", "STATS_FUSED", "LN_FUSED", "WGRAD_SPARSE", "DGRAD_SPARSE", "BLOCK1_PAIR",
+                                  "BLOCK1_F16"])
 def test_cnn_forward_backward_with_a_fusion_switched_off(dev, knob, monkeypatch):
     """The unfused routes stay available as A/B knobs (MODEX_GPOOL=split: LayerNorm backward and pooled-operand pass as two
     kernels with the exact max|G| scale; MODEX_STATS=sweep: LayerNorm statistics by a sweep over the plane; MODEX_LN=sweep: the
-    LayerNorm backward's own statistics sweep) and meet the same tolerances."""
+    LayerNorm backward's own statistics sweep; MODEX_WGRAD=dense / MODEX_DGRAD=dense: the dense f16x3 gradient kernels on the routed
+    pair; MODEX_BLOCK1_PAIR=0: the first block's weight gradient scaling fp32 G while staging; MODEX_BLOCK1=f32: the first block on
+    the exact-fp32 kernels) and meet the same tolerances."""
     from mod_extraction_amd import models as amodels
     monkeypatch.setattr(amodels, knob, False)
     ref, mine = make_pair(dev, n_samples=22272, n_mels=64)
