@@ -771,6 +771,31 @@ int mx_adamw_step_clip(float *param, const float *grad, float *exp_avg, float *e
                        float beta1, float beta2, float eps, float weight_decay, float grad_scale, int32_t clip_mode,
                        float clip_val, double *stat, void *stream);
 
+/* ---- K16: learned effect parameters of the audio-loss step (csrc/fx_params.hip) -- no counterpart in the reference, whose
+ * steps read every effect parameter from the batch.  P <= 16 shared scalars raw (P,) fp32, one per learned (kind, name) pair:
+ *   s = sigmoid(raw_gain * raw[e]);  value = lo + (hi - lo) s,  or with the log flag  exp(log lo + (log hi - log lo) s),
+ * in fp64.  The table: tab_f (2, P) fp64 = the rows lo, hi; tab_i (3, P) int32 = the rows log flag, slot, kind.  Slots, in
+ * this order: lfo_scale 0, min_delay 1, feedback 2, depth 3, mix 4, centre_frequency_hz 5.  Kinds: flanger 0, chorus 1,
+ * phaser 2, tremolo 3, dry 4; row_kind (B,) int32 gives every row's.  max_lfo_delay / max_min_delay (B,) fp32: the per-row
+ * sample counts the lfo_scale / min_delay slots are scaled with.  NULL table / raw / row_kind, P <= 0, B <= 0: MX_ERR_ARG;
+ * P > 16: MX_ERR_UNSUPPORTED; all before any launch.
+ *
+ * mx_fx_params_expand: every entry writes (float)value into the rows of its kind of its slot's (B,) fp32 vector (one thread
+ * per row); lfo_scale / min_delay are then multiplied with the row's sample count in fp32, one_minus_mix = 1 - mix in fp32
+ * wherever mix is written.  Rows and slots without an entry are not written; a NULL output skips its slot (an lfo_scale /
+ * min_delay output without its count vector: MX_ERR_ARG).  values (P,) fp32, optional: the mapped values. */
+int mx_fx_params_expand(const float *raw, const double *tab_f, const int32_t *tab_i, int64_t P, double raw_gain,
+                        const int32_t *row_kind, const float *max_lfo_delay, const float *max_min_delay, int64_t B,
+                        float *lfo_scale, float *min_delay, float *feedback, float *depth, float *mix, float *one_minus_mix,
+                        float *centre_frequency_hz, float *values, void *stream);
+/* d_raw (P,) fp32 = scale * d loss / d raw from grads (6, B) fp64, row s = the per-clip d loss / d (slot s) the effect
+ * adjoints write: per entry (one workgroup each) the rows of its kind, times the sample count where the slot has one, summed
+ * in fp64 in a fixed order, times d value / d raw and scale in fp64, rounded once.  Rows of other kinds are not read.  No
+ * atomics, no workspace: deterministic.  Both count vectors are required. */
+int mx_fx_params_grad(const double *grads, const float *raw, const double *tab_f, const int32_t *tab_i, int64_t P,
+                      double raw_gain, const int32_t *row_kind, const float *max_lfo_delay, const float *max_min_delay,
+                      int64_t B, double scale, float *d_raw, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

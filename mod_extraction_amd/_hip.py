@@ -131,6 +131,8 @@ SIGNATURES = {
     "mx_reduce_rows_adamw_step": [_P, _I64, _P, _P, _P, _P, _I64, _I64, _F32, _F32, _F32, _F32, _F32, _F32, _P],
     "mx_grad_sumsq": [_P, _I64, _P, _P, _P],
     "mx_adamw_step_clip": [_P, _P, _P, _P, _I64, _I64, _F32, _F32, _F32, _F32, _F32, _F32, _I32, _F32, _P, _P],
+    "mx_fx_params_expand": [_P, _P, _P, _I64, _F64, _P, _P, _P, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+    "mx_fx_params_grad": [_P, _P, _P, _P, _I64, _F64, _P, _P, _P, _I64, _F64, _P, _P],
 }
 
 # measurement twins (same signatures): the dependent chain of the sample-recurrent kernels without global traffic

@@ -145,12 +145,13 @@ def tremolo_forward(x: T, mod_sig: T, consts: Dict[str, T], rows: Optional[T] = 
 
 def tremolo_backward(dy: T, x: T, mod_sig: T, consts: Dict[str, T], rows: Optional[T] = None, need_dx: bool = True,
                      need_dmod: bool = True, need_dmix: bool = True,
-                     dmod: Optional[T] = None) -> Tuple[Optional[T], Optional[T], Optional[T]]:
+                     dmod: Optional[T] = None, dmix: Optional[T] = None) -> Tuple[Optional[T], Optional[T], Optional[T]]:
     """Launch mx_tremolo_bwd: the adjoint of fx.py:13-22 behind the in-kernel resampling.  dy, x: (B,N) views with
     contiguous rows; mod_sig (B,n_mod) as the forward was given.  Returns dx (B,N) fp32, dmod (B,n_mod) fp32 and dmix (B,)
     fp64 (the one_minus_mix path included), each None unless asked for; rows not listed in ``rows`` hold zeros.  dmod: an
     optional (B,n_mod) dense output (e.g. a gradient shared with other effects) whose listed rows are written and whose
-    other rows are not touched."""
+    other rows are not touched.  dmix: likewise an optional (B,) fp64 output (e.g. the mix row of the step's (6, B) parameter
+    gradients); the kernel writes, it does not add, so the rows not listed keep what they held."""
     B, N = x.shape
     dev = x.device
     n_mod = mod_sig.size(1)
@@ -164,7 +165,11 @@ def tremolo_backward(dy: T, x: T, mod_sig: T, consts: Dict[str, T], rows: Option
     elif dmod is None:
         dmod = new((B, n_mod), device=dev, dtype=torch.float32)
     assert dmod is None or (dmod.shape == (B, n_mod) and dmod.dtype == torch.float32)
-    dmix = torch.zeros((B,), device=dev, dtype=torch.float64) if need_dmix else None
+    if not need_dmix:
+        dmix = None
+    elif dmix is None:
+        dmix = torch.zeros((B,), device=dev, dtype=torch.float64)
+    assert dmix is None or (dmix.shape == (B,) and dmix.dtype == torch.float64)
     dxp, dxs = _rows_view(dx) if need_dx else (None, 0)
     _hip.call("mx_tremolo_bwd", *_rows_view(dy), *_rows_view(x), _hip.ptr(mod_sig), n_mod, _hip.ptr(consts["mix"]),
               _hip.ptr(consts["one_minus_mix"]), *_rows_arg(rows), B, N, dxp, dxs, _hip.ptr(dmod), _hip.ptr(dmix),
@@ -208,15 +213,29 @@ PARAM_GRADS = ("lfo_scale", "min_delay", "feedback", "depth", "mix")
 FLANGER_MAX_DELAY_SAMPLES = 34784      # csrc/flanger_common.h FL_MAX_M: delay line + a resampled LFO row, in LDS
 
 
+def _param_grad_outputs(names: Tuple[str, ...], given: Optional[Dict[str, T]], B: int, dev) -> Dict[str, T]:
+    """The (B,) fp64 outputs of an adjoint's parameter gradients: the caller's where given, else fresh zeros."""
+    out = {}
+    for k in names:
+        g = None if given is None else given.get(k)
+        if g is None:
+            g = torch.zeros((B,), device=dev, dtype=torch.float64)
+        assert g.shape == (B,) and g.dtype == torch.float64 and g.is_contiguous(), k
+        out[k] = g
+    return out
+
+
 def flanger_backward(dy: T, x: T, mod_sig: T, stash: T, consts: Dict[str, T], max_delay: T, max_delay_max: int,
                      rows: Optional[T] = None, need_dx: bool = True, need_dmod: bool = True,
                      params: Tuple[str, ...] = PARAM_GRADS, dx: Optional[T] = None,
-                     dmod: Optional[T] = None) -> Tuple[Optional[T], Optional[T], Dict[str, T]]:
+                     dmod: Optional[T] = None,
+                     grads: Optional[Dict[str, T]] = None) -> Tuple[Optional[T], Optional[T], Dict[str, T]]:
     """Launch mx_flanger_bwd (mod_sig at full rate) or mx_flanger_bwd_lr (a shorter mod_sig, as the stash forward was
     given): the adjoint of fx.py:72-119 (the gradient the DESIGN K-table row defines).
     dy, x: (B,N) views with contiguous rows; stash (B,N) and mod_sig (B,n_mod) dense.  Returns dx (B,N), dmod (B,n_mod)
     (None unless asked for) and the per-clip fp64 gradients of the constants named in ``params`` (d mix includes the
-    one_minus_mix path)."""
+    one_minus_mix path).  grads: optional (B,) fp64 outputs by name for (some of) ``params`` (e.g. rows of the step's (6, B)
+    parameter gradients) instead of fresh zeros; the kernel writes, it does not add, so rows not listed keep what they held."""
     B, N = x.shape
     dev = x.device
     n_mod = mod_sig.size(1)
@@ -230,7 +249,7 @@ def flanger_backward(dy: T, x: T, mod_sig: T, stash: T, consts: Dict[str, T], ma
     assert not need_dmod or dmod.size(1) == n_mod
     dxp, dxs = _rows_view(dx) if need_dx else (None, 0)
     dmp, dms = _rows_view(dmod) if need_dmod else (None, 0)
-    grads = {k: torch.zeros((B,), device=dev, dtype=torch.float64) for k in params}
+    grads = _param_grad_outputs(params, grads, B, dev)
     ws = torch.empty((B, N), device=dev, dtype=torch.float32)
     entry = ("mx_flanger_bwd", ()) if n_mod == N else ("mx_flanger_bwd_lr", (n_mod,))
     _hip.call(entry[0], *_rows_view(dy), *_rows_view(x), _hip.ptr(mod_sig), *entry[1], _hip.ptr(stash),
@@ -438,13 +457,15 @@ def phaser_forward_stash(src: T, params: Dict[str, T], lead: Optional[T], sr: fl
 def phaser_backward(dy: T, src: T, stash: T, params: Dict[str, T], lead: Optional[T], sr: float, n_samples: int,
                     rows: Optional[T] = None, need_dx: bool = True, need_dmod: bool = True,
                     params_wanted: Tuple[str, ...] = PHASER_PARAM_GRADS, dx: Optional[T] = None,
-                    dmod: Optional[T] = None) -> Tuple[Optional[T], Optional[T], Dict[str, T]]:
+                    dmod: Optional[T] = None,
+                    grads: Optional[Dict[str, T]] = None) -> Tuple[Optional[T], Optional[T], Dict[str, T]]:
     """Launch mx_phaser_bwd: the adjoint of the phaser recurrence (the gradient the DESIGN K3b row defines).
     dy (B, n_samples) and src (B, W) views with contiguous rows; stash from ``phaser_forward_stash`` on the same src, params,
     lead.  Returns dx (B, W): the gradient with respect to every processed source sample, the lead included, zeros beyond
     lead + n_samples; dmod (B, ceil(W / 4)): with respect to the external LFO (with the built-in oscillator: with respect to
     (1 - osc) / 2) (both None unless asked for); and the per-clip fp64 gradients of the parameters named in
-    ``params_wanted``.  There is no gradient with respect to rate_hz."""
+    ``params_wanted``.  There is no gradient with respect to rate_hz.  grads: optional (B,) fp64 outputs by name, as in
+    ``flanger_backward`` (written, not added to)."""
     B, W = src.shape
     dev = src.device
     if dy.stride(-1) != 1 or dy.stride(0) < n_samples:      # e.g. the expanded ones of y.sum().backward()
@@ -462,7 +483,7 @@ def phaser_backward(dy: T, src: T, stash: T, params: Dict[str, T], lead: Optiona
     assert not need_dmod or dmod.size(1) >= n_mod                 # every group of the longest possible clip
     sg, row = phaser_stash_shape(W)
     assert stash.shape == (B, row)
-    grads = {k: torch.zeros((B,), device=dev, dtype=torch.float64) for k in params_wanted}
+    grads = _param_grad_outputs(params_wanted, grads, B, dev)
     _hip.call("mx_phaser_bwd", *_rows_view(dy), *_rows_view(src), W, _hip.ptr(stash), sg, row, _hip.ptr(params["depth"]),
               _hip.ptr(params["centre_frequency_hz"]), _hip.ptr(params["feedback"]), _hip.ptr(params["mix"]),
               _hip.ptr(lead), *_rows_arg(rows), B, n_samples, float(sr), dxp, dxs,
@@ -538,19 +559,20 @@ def phaser_forward_stash_lr(src: T, params: Dict[str, T], lead: Optional[T], sr:
 
 def phaser_backward_lr(dy: T, src: T, stash: T, params: Dict[str, T], lead: Optional[T], sr: float, n_samples: int,
                        n_mod: int, need_dx: bool = True, params_wanted: Tuple[str, ...] = PHASER_PARAM_GRADS,
-                       rows: Optional[T] = None, dmod: Optional[T] = None) -> Tuple[Optional[T], T, Dict[str, T]]:
+                       rows: Optional[T] = None, dmod: Optional[T] = None,
+                       grads: Optional[Dict[str, T]] = None) -> Tuple[Optional[T], T, Dict[str, T]]:
     """The adjoint of ``phaser_forward_stash_lr``: ``phaser_backward`` (dmod at group rate), then ``phaser_dmod_gather``.
     Returns (dx (B, W) or None, dmod_lr (B, n_mod), the per-clip fp64 parameter gradients named in ``params_wanted``).
     rows: the list the forward was given, through both launches; dmod: an optional (B, n_mod) dense output whose listed
     rows are written and whose other rows are not touched (without it they are uninitialised, as are those of dx); an
-    empty list launches nothing."""
+    empty list launches nothing.  grads: as in ``phaser_backward``."""
     if rows is not None and rows.numel() == 0:
         B, W = src.shape
         dx = torch.empty((B, W), device=src.device, dtype=torch.float32) if need_dx else None
         out = dmod if dmod is not None else torch.empty((B, n_mod), device=src.device, dtype=torch.float32)
-        return dx, out, {k: torch.zeros((B,), device=src.device, dtype=torch.float64) for k in params_wanted}
+        return dx, out, _param_grad_outputs(params_wanted, grads, B, src.device)
     dx, dmod_g, grads = phaser_backward(dy, src, stash, params, lead, sr, n_samples, rows=rows, need_dx=need_dx,
-                                        need_dmod=True, params_wanted=params_wanted)
+                                        need_dmod=True, params_wanted=params_wanted, grads=grads)
     return dx, phaser_dmod_gather(dmod_g, lead, n_samples, n_mod, rows=rows, out=dmod), grads
 
 
@@ -799,3 +821,166 @@ class TremoloModule(nn.Module):
             xr, mr, consts, shape = self._prepare(x, mod_sig, mix)
             y = tremolo_forward(xr, mr, {k: _per_row(v, shape[1]) for k, v in consts.items()})
         return y.view(shape)
+
+
+# ---- learned effect parameters (csrc/fx_params.hip, DESIGN K16) ------------------------------------------------------
+FX_KINDS = ("flanger", "chorus", "phaser", "tremolo", "dry")       # the kind codes of the kernels' row_kind vector
+FX_SLOTS = ("lfo_scale", "min_delay", "feedback", "depth", "mix", "centre_frequency_hz")   # rows of the (6, B) gradients
+FX_CONSTS = ("lfo_scale", "min_delay", "feedback", "depth", "mix", "one_minus_mix", "centre_frequency_hz")
+# the parameter names of every kind, in the canonical order of ``LearnedFxParams.names``, and the slot each one fills
+FX_PARAM_NAMES = {"flanger": ("feedback", "min_delay_width", "width", "depth", "mix"),
+                  "chorus": ("feedback", "min_delay_width", "width", "depth", "mix"),
+                  "tremolo": ("mix",),
+                  "phaser": ("depth", "centre_frequency_hz", "feedback", "mix")}
+FX_NAME_SLOT = {"width": "lfo_scale", "min_delay_width": "min_delay", "feedback": "feedback", "depth": "depth", "mix": "mix",
+                "centre_frequency_hz": "centre_frequency_hz"}
+FX_MAX_LEARNED = 16                                                 # FXP_MAX_ENTRIES of csrc/fx_params.hip
+
+
+def _fx_param_range(kind: str, name: str) -> Tuple[float, float, bool, bool]:
+    """(lo, hi, lo_open, hi_open): what ``_check_param`` / ``derive_phaser_params(check=True)`` accept for a parameter."""
+    if name == "centre_frequency_hz":
+        return 0.0, float("inf"), True, False
+    if name == "feedback":
+        return (-1.0, 1.0, True, True) if kind == "phaser" else (0.0, 1.0, False, True)
+    return 0.0, 1.0, False, False
+
+
+def fx_params_expand(raw: T, tab_f: T, tab_i: T, raw_gain: float, row_kind: T, max_lfo_delay: Optional[T],
+                     max_min_delay: Optional[T], consts: Dict[str, T], values: Optional[T] = None) -> T:
+    """Launch mx_fx_params_expand: the P mapped values of ``raw`` (P,) fp32 written into the rows of their kind of the (B,)
+    fp32 vectors of ``consts`` (keys out of ``FX_CONSTS``; a missing key skips its slot), in place; rows and slots without
+    an entry keep what they hold.  tab_f (2, P) fp64 and tab_i (3, P) int32 as ``LearnedFxParams`` builds them; row_kind (B,)
+    int32 (``FX_KINDS`` codes).  Returns values (P,) fp32."""
+    P, B = raw.numel(), row_kind.numel()
+    assert raw.dtype == torch.float32 and tab_f.shape == (2, P) and tab_f.dtype == torch.float64
+    assert tab_i.shape == (3, P) and tab_i.dtype == torch.int32 and row_kind.dtype == torch.int32
+    for k, v in consts.items():
+        assert k in FX_CONSTS and v.shape == (B,) and v.dtype == torch.float32, k
+    for v in (max_lfo_delay, max_min_delay):
+        assert v is None or (v.shape == (B,) and v.dtype == torch.float32)
+    if values is None:
+        values = torch.empty((P,), device=raw.device, dtype=torch.float32)
+    assert values.shape == (P,) and values.dtype == torch.float32
+    _hip.call("mx_fx_params_expand", _hip.ptr(raw), _hip.ptr(tab_f), _hip.ptr(tab_i), P, float(raw_gain), _hip.ptr(row_kind),
+              _hip.ptr(max_lfo_delay), _hip.ptr(max_min_delay), B, *[_hip.ptr(consts.get(k)) for k in FX_CONSTS],
+              _hip.ptr(values), _hip.stream())
+    return values
+
+
+def fx_params_grad(grads: T, raw: T, tab_f: T, tab_i: T, raw_gain: float, row_kind: T, max_lfo_delay: T, max_min_delay: T,
+                   scale: float = 1.0) -> T:
+    """Launch mx_fx_params_grad: scale * d loss / d raw (P,) fp32 from grads (6, B) fp64, the per-clip gradients of the
+    constants in ``FX_SLOTS`` order as the effect adjoints write them (rows of kinds without an entry for a slot are not
+    read and may be uninitialised).  Deterministic."""
+    P, B = raw.numel(), row_kind.numel()
+    assert grads.shape == (len(FX_SLOTS), B) and grads.dtype == torch.float64
+    assert raw.dtype == torch.float32 and tab_f.shape == (2, P) and tab_i.shape == (3, P)
+    assert max_lfo_delay.shape == max_min_delay.shape == (B,) and max_lfo_delay.dtype == max_min_delay.dtype == torch.float32
+    d_raw = torch.empty((P,), device=raw.device, dtype=torch.float32)
+    _hip.call("mx_fx_params_grad", _hip.ptr(grads), _hip.ptr(raw), _hip.ptr(tab_f), _hip.ptr(tab_i), P, float(raw_gain),
+              _hip.ptr(row_kind), _hip.ptr(max_lfo_delay), _hip.ptr(max_min_delay), B, float(scale), _hip.ptr(d_raw),
+              _hip.stream())
+    return d_raw
+
+
+class LearnedFxParams(nn.Module):
+    """Effect parameters fitted together with the LFO extractor (``lightning.LFOExtractionThroughEffect(learned_fx=...)``):
+    ONE shared value per (kind, name), not one per clip.  ``spec``: a dict keyed by kind (``flanger``, ``chorus``,
+    ``tremolo``, ``phaser``); under each kind a parameter name maps to ``{min, max, init[, scale: lin | log]}`` = learned, or
+    to a bare number = fixed (not learned, but it overrides the batch's value on the rows of that kind).
+
+    One parameter ``raw`` (P,) fp32, 1 <= P <= 16; ``names`` lists its entries as ``"flanger.feedback"``: the kinds in spec
+    order, under each kind the names in the order of ``FX_PARAM_NAMES``.  value = min + (max - min) sigmoid(raw_gain raw); with
+    ``scale: log`` (the default of ``centre_frequency_hz``) the same map between log min and log max.  raw starts at
+    logit(init) / raw_gain.  ``raw_gain``: Adam's step does not depend on the gradient's scale, so a gain k makes the step in
+    the mapped domain k times longer at the learning rate the fitted scalars share with the network.
+
+    Every learned range lies inside what the effect accepts, ends included where a value rounded onto an end is still legal:
+    feedback of the flanger / chorus max < 1, of the phaser -1 < min and max < 1, centre_frequency_hz min > 0.  ValueError
+    for anything else: unknown kinds or names, min < init < max violated, a log scale with min <= 0, no or more than 16
+    learned entries.
+
+    ``values()``: the P mapped values in fp64 by torch (any device).  The step's path is ``expand`` / ``grad``: the
+    ``mx_fx_params_expand`` / ``mx_fx_params_grad`` launches."""
+
+    def __init__(self, spec: Dict[str, Dict[str, object]], raw_gain: float = 1.0) -> None:
+        super().__init__()
+        import math
+        if not isinstance(spec, dict) or not spec:
+            raise ValueError("learned_fx: a dict keyed by effect kind")
+        if not (isinstance(raw_gain, (int, float)) and math.isfinite(raw_gain) and raw_gain > 0):
+            raise ValueError(f"raw_gain {raw_gain!r}: a positive number")
+        self.raw_gain = float(raw_gain)
+        self.names, self.fixed = [], {}
+        lo, hi, is_log, slot, kind_code, init_raw = [], [], [], [], [], []
+        for kind, params in spec.items():
+            if kind not in FX_PARAM_NAMES:
+                raise ValueError(f"learned_fx: unknown kind '{kind}' (supported: {tuple(FX_PARAM_NAMES)})")
+            if not isinstance(params, dict):
+                raise ValueError(f"learned_fx.{kind}: a dict of parameter names")
+            for name in params:
+                if name not in FX_PARAM_NAMES[kind]:
+                    raise ValueError(f"learned_fx: '{kind}' has no parameter '{name}' (it has {FX_PARAM_NAMES[kind]})")
+            for name in FX_PARAM_NAMES[kind]:
+                if name not in params:
+                    continue
+                entry, full = params[name], f"{kind}.{name}"
+                a, b, a_open, b_open = _fx_param_range(kind, name)
+                if not isinstance(entry, dict):
+                    v = float(entry)
+                    if not ((v > a if a_open else v >= a) and (v < b if b_open else v <= b)):
+                        raise ValueError(f"learned_fx.{full} = {v}: outside the effect's range")
+                    self.fixed[(kind, name)] = v
+                    continue
+                unknown = set(entry) - {"min", "max", "init", "scale"}
+                if unknown or not {"min", "max", "init"} <= set(entry):
+                    raise ValueError(f"learned_fx.{full}: keys min, max, init and optionally scale (got {sorted(entry)})")
+                mn, mx, init = float(entry["min"]), float(entry["max"]), float(entry["init"])
+                scale = entry.get("scale", "log" if name == "centre_frequency_hz" else "lin")
+                if scale not in ("lin", "log"):
+                    raise ValueError(f"learned_fx.{full}: scale '{scale}' (lin or log)")
+                if not all(math.isfinite(v) for v in (mn, mx, init)) or not mn < init < mx:
+                    raise ValueError(f"learned_fx.{full}: min < init < max does not hold ({mn}, {init}, {mx})")
+                if not ((mn > a if a_open else mn >= a) and (mx < b if b_open else mx <= b)):
+                    raise ValueError(f"learned_fx.{full}: the range [{mn}, {mx}] must lie inside "
+                                     f"{'(' if a_open else '['}{a}, {b}{')' if b_open else ']'}")
+                if scale == "log" and mn <= 0:
+                    raise ValueError(f"learned_fx.{full}: a log scale needs min > 0")
+                s = (math.log(init / mn) / math.log(mx / mn)) if scale == "log" else (init - mn) / (mx - mn)
+                self.names.append(full)
+                lo.append(mn), hi.append(mx), is_log.append(int(scale == "log"))
+                slot.append(FX_SLOTS.index(FX_NAME_SLOT[name])), kind_code.append(FX_KINDS.index(kind))
+                init_raw.append(math.log(s / (1.0 - s)) / self.raw_gain)
+        if not 1 <= len(self.names) <= FX_MAX_LEARNED:
+            raise ValueError(f"learned_fx: {len(self.names)} learned entries (1 .. {FX_MAX_LEARNED} are supported)")
+        self.kinds = tuple(spec)
+        self.raw = nn.Parameter(torch.tensor(init_raw, dtype=torch.float64).float())
+        # the kernels' table; not part of the state dict (the spec rebuilds it)
+        self.register_buffer("tab_f", torch.tensor([lo, hi], dtype=torch.float64), persistent=False)
+        self.register_buffer("tab_i", torch.tensor([is_log, slot, kind_code], dtype=torch.int32), persistent=False)
+
+    def learned(self, kind: str) -> Tuple[str, ...]:
+        """The learned parameter names of a kind."""
+        return tuple(n.split(".", 1)[1] for n in self.names if n.split(".", 1)[0] == kind)
+
+    def covers(self, kind: str, name: str) -> bool:
+        return (kind, name) in self.fixed or f"{kind}.{name}" in self.names
+
+    def values(self) -> T:
+        """The P mapped values, fp64, by torch expressions (differentiable with respect to ``raw``)."""
+        s = torch.sigmoid(self.raw_gain * self.raw.double())
+        lo, hi = self.tab_f[0], self.tab_f[1]
+        log = self.tab_i[0] != 0
+        lo_l, hi_l = torch.where(log, lo, torch.ones_like(lo)).log(), torch.where(log, hi, torch.ones_like(hi)).log()
+        return torch.where(log, torch.exp(lo_l + (hi_l - lo_l) * s), lo + (hi - lo) * s)
+
+    def expand(self, consts: Dict[str, T], row_kind: T, max_lfo_delay: Optional[T], max_min_delay: Optional[T]) -> T:
+        """``fx_params_expand`` with this module's table: writes into ``consts`` in place, returns values (P,) fp32."""
+        return fx_params_expand(self.raw.detach(), self.tab_f, self.tab_i, self.raw_gain, row_kind, max_lfo_delay,
+                                max_min_delay, consts)
+
+    def grad(self, grads: T, row_kind: T, max_lfo_delay: T, max_min_delay: T, scale: float = 1.0) -> T:
+        """``fx_params_grad`` with this module's table: d loss / d raw (P,) fp32."""
+        return fx_params_grad(grads, self.raw.detach(), self.tab_f, self.tab_i, self.raw_gain, row_kind, max_lfo_delay,
+                              max_min_delay, scale)

@@ -201,7 +201,7 @@ class LFOExtraction(BaseLightingModule):
 
 class _EffectAudioLossFn(torch.autograd.Function):
     """loss = sum_k w_k loss_k(effect(dry, mod_sig_hat), wet) as ONE autograd node for every ``effect``: ``forward(ctx,
-    mod_sig_hat, step, dry, wet, consts, terms)`` returns (loss, wet_hat (B, N)) and fills ``terms`` with the unweighted
+    mod_sig_hat, raw, step, dry, wet, consts, terms)`` returns (loss, wet_hat (B, N)) and fills ``terms`` with the unweighted
     value of every weighted loss.  Every family renders its rows into one wet_hat (``step._render_rows``), the
     value-and-gradient kernels of the weighted losses run once (``effect_loss_grad``), and every family's adjoint writes its
     rows of one (B, n_frames) gradient at once (``step._adjoint_rows``).  Only that gradient is kept for the backward, which
@@ -209,26 +209,39 @@ class _EffectAudioLossFn(torch.autograd.Function):
     call."""
 
     @staticmethod
-    def forward(ctx, mod_sig_hat, step, dry, wet, consts, terms):
+    def forward(ctx, mod_sig_hat, raw, step, dry, wet, consts, terms):
+        """``raw``: ``step.learned_fx.raw`` (the second differentiable input; ``consts`` already hold its mapped values) or
+        None.  With it every family's adjoint is also asked for the per-clip fp64 gradients of its learned slots, rows of one
+        (6, B) buffer, which ``mx_fx_params_grad`` reduces to d loss / d raw; without it the launches are those of the step
+        without learned parameters."""
         from .effect_losses import effect_loss_grad, effect_loss_terms
         mod = mod_sig_hat.detach().float().contiguous()
         wet_hat, stashes = step._render_rows(dry, mod, consts, stash=True)
         a, t = wet_hat.unsqueeze(1), wet.unsqueeze(1)
         weighted: Dict[str, T] = {}
         dy = effect_loss_grad(a, t, step.audio_loss_dict, values=weighted, **step._grad_modules())
-        dmod = step._adjoint_rows(dy, dry, mod, consts, stashes)
+        if raw is None:
+            dmod = step._adjoint_rows(dy, dry, mod, consts, stashes)
+            ctx.save_for_backward(dmod)
+        else:
+            m = step._mixed_rows(dry.size(0), dry.device)
+            # the adjoints write (they do not add) the rows of their family, and the reduction reads only those: no zeros
+            gbuf = torch.empty((6, dry.size(0)), device=dry.device, dtype=torch.float64)
+            dmod = step._adjoint_rows(dy, dry, mod, consts, stashes, gbuf=gbuf)
+            d_raw = step.learned_fx.grad(gbuf, m["row_kind"], m["max_lfo_delay"], m["max_min_delay"])
+            ctx.save_for_backward(dmod, d_raw)
         w = {k: v for k, v in step.audio_loss_dict.items() if v > 0}
         terms.update({k: v / w[k] for k, v in weighted.items()})
         if any(k in w for k in ("l1", "mse", "esr", "dc")):
             terms.update({k: v for k, v in effect_loss_terms(a, t).items() if k in w})
-        ctx.save_for_backward(dmod)
         ctx.mark_non_differentiable(wet_hat)
         return step.weighted_sum(terms, step.audio_loss_dict), wet_hat
 
     @staticmethod
     def backward(ctx, g, _g_wet_hat):
-        (dmod,) = ctx.saved_tensors
-        return dmod * g, None, None, None, None, None
+        dmod = ctx.saved_tensors[0]
+        d_raw = ctx.saved_tensors[1] * g if len(ctx.saved_tensors) > 1 and ctx.needs_input_grad[1] else None
+        return (dmod * g if ctx.needs_input_grad[0] else None), d_raw, None, None, None, None, None
 
 
 EFFECTS = ("flanger", "tremolo", "phaser")              # what a string ``effect`` may name
@@ -273,6 +286,17 @@ class LFOExtractionThroughEffect(BaseLightingModule):
     * ``audio_loss_dict``: names from ``effect_losses.GRAD_NAMES``; zero-weight names are only logged.
     * ``pre_emph_filter_cfs`` / ``pre_emph_low_pass``: the filter of the "esr_pre" loss (``losses.PreEmphESRLoss``; 1 .. 16
       taps), ignored without that name.
+    * ``learned_fx`` (optional): a spec dict or an ``fx.LearnedFxParams`` -- effect parameters fitted together with the
+      extractor, ONE shared value per (kind, name), each mapped onto its valid range; a bare number in the spec fixes a
+      parameter.  A learned or fixed (kind, name) overrides the batch's ``fx_params`` on the rows of that kind, every other
+      name is read from the batch; a name that a present kind needs and nobody supplies raises a ``ValueError`` naming it,
+      so with every name covered the step trains on ``(dry, wet, None, None)`` batches (recorded pairs).  The mapped
+      values are written into the per-row constants by ``mx_fx_params_expand`` and d loss / d raw comes from the adjoints'
+      per-clip parameter gradients through ``mx_fx_params_grad``; ``learned_fx.raw`` is an ordinary parameter (optimizer,
+      DDP, checkpoints), AdamW's weight decay pulls a value towards the middle of its range, and every training step logs
+      ``fx/<kind>.<name>``.  ``render`` and validation use the learned values.  The default adds no parameter and leaves
+      the step's launches as they are.  What a fit cannot tell apart (``width`` and the LFO's amplitude, ``min_delay_width``
+      and its offset, the flanger's ``mix * depth``): DESIGN section 7.
     * ``loss_dict`` (optional, default none): an LFO-domain term (lightning.py:33-62) added to the loss when the batch carries
       ``mod_sig``; it is logged as ``{prefix}/lfo_{name}``.
     The LFO enters the effect at the extractor's own rate (n_frames points, resampled in-kernel exactly as the data path
@@ -312,7 +336,8 @@ class LFOExtractionThroughEffect(BaseLightingModule):
                  chorus_max_min_delay_ms: Optional[float] = None,
                  chorus_max_lfo_delay_ms: Optional[float] = None,
                  pre_emph_filter_cfs: Sequence[float] = (-0.95, 1.0),
-                 pre_emph_low_pass: bool = False) -> None:
+                 pre_emph_low_pass: bool = False,
+                 learned_fx=None) -> None:
         super().__init__({} if loss_dict is None else loss_dict)
         self._set_pre_emph(pre_emph_filter_cfs, pre_emph_low_pass)
         from . import fx
@@ -376,6 +401,19 @@ class LFOExtractionThroughEffect(BaseLightingModule):
         self.lfo_loss_dict = self.loss_dict
         self.loss_dict = dict(audio_loss_dict, **{f"lfo_{k}": w for k, w in self.lfo_loss_dict.items()})
         self._mixed = None
+        if isinstance(learned_fx, dict):
+            learned_fx = fx.LearnedFxParams(learned_fx)
+        if learned_fx is not None:
+            if not isinstance(learned_fx, fx.LearnedFxParams):
+                raise ValueError("learned_fx: a spec dict or an fx.LearnedFxParams")
+            for k in learned_fx.kinds:
+                if k not in self._kinds:
+                    raise ValueError(f"learned_fx names the kind '{k}', which is not among this step's kinds {self._kinds}")
+        self.learned_fx = learned_fx                                # None registers nothing: the parameters are the model's
+        self._fixed_plan = None
+        self._fx_values: Optional[T] = None
+        # the scalars ``common_step`` logs per training step beside the losses (trainer.metric_names)
+        self.step_metric_names = [] if learned_fx is None else [f"fx/{n}" for n in learned_fx.names]
 
     def _mixed_rows(self, bs: int, device) -> Dict[str, object]:
         """The row plan of a batch of ``bs`` rows on ``device`` (cached): the int32 row list of every launch family, the
@@ -398,6 +436,10 @@ class LFOExtractionThroughEffect(BaseLightingModule):
                  "dry_idx": torch.tensor(lists["dry"], dtype=torch.int64, device=device)}
             for name in ("delay", "tremolo", "phaser"):
                 m[name] = torch.tensor(lists[name], dtype=torch.int32, device=device)
+            if self.learned_fx is not None:                         # the kind code of every row (fx.FX_KINDS)
+                from . import fx
+                m["kinds"] = kinds
+                m["row_kind"] = torch.tensor([fx.FX_KINDS.index(k) for k in kinds], dtype=torch.int32, device=device)
             self._mixed = m
         return m
 
@@ -415,6 +457,12 @@ class LFOExtractionThroughEffect(BaseLightingModule):
         fp32 and one_minus_mix is 1 - mix in fp32; a python float meets them in double and is rounded once.  So a re-render
         from the label reproduces ``wet``.  Only what the kinds present need is read from ``fx_params``."""
         from . import fx
+        if self.learned_fx is not None:
+            return self._learned_constants(fx_params, bs, device)
+        missing = self.missing_fx_params(fx_params, bs)
+        if missing:
+            raise ValueError(f"fx_params lacks {missing}: the re-render needs them from the batch, or learned / fixed through "
+                             f"learned_fx")
         m = self._mixed_rows(bs, device)
         lists = m["lists"]
 
@@ -454,6 +502,93 @@ class LFOExtractionThroughEffect(BaseLightingModule):
             consts["centre_frequency_hz"] = vec("centre_frequency_hz")
         return consts
 
+    def missing_fx_params(self, fx_params, bs: int) -> List[str]:
+        """The "<kind>.<name>" a batch of ``bs`` rows needs for its re-render and has from nowhere: not in ``fx_params`` (which
+        may be None: a dry / wet pair of a recording) and neither learned nor fixed by ``learned_fx``."""
+        from . import fx
+        out = []
+        for kind in dict.fromkeys(self._kinds[i % len(self._kinds)] for i in range(bs)):
+            for name in fx.FX_PARAM_NAMES.get(kind, ()):
+                if (fx_params is None or name not in fx_params) and not (self.learned_fx is not None
+                                                                         and self.learned_fx.covers(kind, name)):
+                    out.append(f"{kind}.{name}")
+        return out
+
+    def _learned_constants(self, fx_params, bs: int, device) -> Dict[str, T]:
+        """``clip_constants`` of a step with ``learned_fx``.  Precedence per (kind, name): learned or fixed by ``learned_fx``
+        on the rows of that kind, else the batch's ``fx_params`` as in ``clip_constants`` (a ValueError names what neither has).
+        The fixed numbers meet their row's sample count in double and are rounded once (the rule of a python float), per
+        (B, device) once; the learned values are written over their rows by ``mx_fx_params_expand`` (fp64 map, rounded once,
+        then the rule of a tensor parameter).  Without ``fx_params`` the vectors are the cached ones, rewritten in place on
+        every step: no launch but the one.  Keeps the (P,) fp32 values for ``common_step`` to log."""
+        from . import fx
+        lf = self.learned_fx
+        missing = self.missing_fx_params(fx_params, bs)
+        if missing:
+            raise ValueError(f"the re-render needs {missing}: neither in the batch's fx_params nor learned / fixed by learned_fx")
+        m = self._mixed_rows(bs, device)
+        lists, kinds = m["lists"], m["kinds"]
+        if self.check_fx_params:                                    # what is still read from the batch, on the rows that read it
+            for kind in dict.fromkeys(kinds):
+                rows = [i for i in range(bs) if kinds[i] == kind]
+                for name in fx.FX_PARAM_NAMES.get(kind, ()):
+                    if not lf.covers(kind, name):
+                        p = fx_params[name]
+                        fx._check_range(p[rows] if isinstance(p, T) else p, len(rows), *fx._fx_param_range(kind, name))
+        plan = self._fixed_plan
+        if plan is None or plan["bs"] != bs or plan["device"] != device:
+            mm, ml = m["max_min_delay"].double().cpu(), m["max_lfo_delay"].double().cpu()
+            vals = {k: torch.zeros(bs, dtype=torch.float64) for k in fx.FX_CONSTS}
+            mask = {k: torch.zeros(bs, dtype=torch.bool) for k in fx.FX_CONSTS}
+            for (kind, name), v in lf.fixed.items():
+                slot = fx.FX_NAME_SLOT[name]
+                for i in (i for i in range(bs) if kinds[i] == kind):
+                    vals[slot][i] = v * float(ml[i]) if name == "width" else v * float(mm[i]) if name == "min_delay_width" else v
+                    mask[slot][i] = True
+                    if name == "mix":
+                        vals["one_minus_mix"][i], mask["one_minus_mix"][i] = 1.0 - v, True
+            plan = {"bs": bs, "device": device, "vals": {k: v.float().to(device) for k, v in vals.items()},
+                    "mask": {k: (v.to(device) if bool(v.any()) else None) for k, v in mask.items()}}
+            self._fixed_plan = plan
+        learned_slots = {fx.FX_NAME_SLOT[n.split(".", 1)[1]] for n in lf.names}
+        if "mix" in learned_slots:
+            learned_slots.add("one_minus_mix")
+        source = {"lfo_scale": ("width", lambda v: v * m["max_lfo_delay"]), "min_delay": ("min_delay_width", lambda v: v * m["max_min_delay"]),
+                  "feedback": ("feedback", None), "depth": ("depth", None), "mix": ("mix", None),
+                  "one_minus_mix": ("mix", lambda v: 1.0 - v), "centre_frequency_hz": ("centre_frequency_hz", None)}
+        wanted = []
+        if lists["delay"] or lists["tremolo"] or lists["phaser"]:
+            wanted.append("mix")
+        if lists["delay"] or lists["tremolo"]:
+            wanted.append("one_minus_mix")
+        if lists["delay"] or lists["phaser"]:
+            wanted += ["feedback", "depth"]
+        if lists["delay"]:
+            wanted += ["lfo_scale", "min_delay"]
+        if lists["phaser"]:
+            wanted.append("centre_frequency_hz")
+        consts = {}
+        for key in wanted:
+            name, f = source[key]
+            p = None if fx_params is None else fx_params.get(name)
+            if p is None:                                           # learned / fixed on every row that reads it
+                consts[key] = plan["vals"][key]
+                continue
+            if isinstance(p, T):
+                assert p.shape == (bs,), f"fx_params['{name}']: a ({bs},) tensor or a python float"
+                v = p.to(device=device, dtype=torch.float32)
+                v = f(v) if f is not None else v
+            else:
+                v = torch.full((bs,), float(p), device=device, dtype=torch.float64)
+                v = (f(v) if f is not None else v).float()
+            if plan["mask"][key] is not None:
+                v = torch.where(plan["mask"][key], plan["vals"][key], v)
+            elif key in learned_slots and isinstance(p, T) and v.data_ptr() == p.data_ptr():
+                v = v.clone()                                       # the launch below writes: not into the batch's own tensor
+            consts[key] = v.contiguous()
+        self._fx_values = lf.expand(consts, m["row_kind"], m["max_lfo_delay"], m["max_min_delay"])
+        return consts
+
     def _render_rows(self, dry: T, mod: T, consts: Dict[str, T], stash: bool):
         """wet_hat (B, N), every family through its row list (``_launch_rows``) into the one buffer: flanger + chorus rows
         ``mx_flanger_fwd`` (``stash``: ``mx_flanger_fwd_stash``, the same bits), tremolo rows ``mx_tremolo_fwd``, phaser rows
@@ -481,24 +616,39 @@ class LFOExtractionThroughEffect(BaseLightingModule):
                 stashes["phaser"] = st
         return wet_hat, stashes
 
-    def _adjoint_rows(self, dy: T, dry: T, mod: T, consts: Dict[str, T], stashes: Dict[str, T]) -> T:
+    def _adjoint_rows(self, dy: T, dry: T, mod: T, consts: Dict[str, T], stashes: Dict[str, T],
+                      gbuf: Optional[T] = None) -> T:
         """d loss / d LFO (B, n_frames) from d loss / d wet_hat (B, N): every family's adjoint, asked for dmod alone, writes
         its rows of one zero-initialised buffer through the forward's row list (``mx_flanger_bwd_lr``; ``mx_tremolo_bwd``;
         ``mx_phaser_bwd`` + ``mx_phaser_dmod_gather``).  Dry rows keep the zeros.  A family that owns every row writes every
-        row: no zeros then, its wrapper's own ``torch.empty``."""
+        row: no zeros then, its wrapper's own ``torch.empty``.  ``gbuf`` (6, B) fp64 (a step with ``learned_fx``): every family
+        is also asked for the per-clip gradients of the slots its kinds have learned entries for, written into its rows of
+        ``gbuf`` (slot order ``fx.FX_SLOTS``); without it nothing but dmod is asked for."""
         from . import fx
         B, N = dry.shape
         m = self._mixed_rows(B, dry.device)
         dmod = None if m["all_rows"] else torch.zeros((B, mod.size(1)), device=dry.device, dtype=torch.float32)
+
+        def wanted(*kinds: str) -> Dict[str, T]:                    # slot name -> its row of gbuf, for the kinds' learned names
+            if gbuf is None:
+                return {}
+            slots = {fx.FX_NAME_SLOT[n] for k in kinds for n in self.learned_fx.learned(k)}
+            return {s: gbuf[i] for i, s in enumerate(fx.FX_SLOTS) if s in slots}
+
         if m["delay"].numel():
+            g = wanted("flanger", "chorus")
             dmod = fx.flanger_backward(dy, dry, mod, stashes["delay"], consts, m["max_delay"], m["max_delay_max"],
-                                       rows=self._launch_rows(m, "delay"), need_dx=False, params=(), dmod=dmod)[1]
+                                       rows=self._launch_rows(m, "delay"), need_dx=False,
+                                       params=tuple(k for k in fx.PARAM_GRADS if k in g), dmod=dmod, grads=g)[1]
         if m["tremolo"].numel():
+            g = wanted("tremolo")
             dmod = fx.tremolo_backward(dy, dry, mod, consts, rows=self._launch_rows(m, "tremolo"), need_dx=False,
-                                       need_dmix=False, dmod=dmod)[1]
+                                       need_dmix="mix" in g, dmod=dmod, dmix=g.get("mix"))[1]
         if m["phaser"].numel():
+            g = wanted("phaser")
             dmod = fx.phaser_backward_lr(dy, dry, stashes["phaser"], consts, None, self.sr, N, mod.size(1), need_dx=False,
-                                         params_wanted=(), rows=self._launch_rows(m, "phaser"), dmod=dmod)[1]
+                                         params_wanted=tuple(k for k in fx.PHASER_PARAM_GRADS if k in g),
+                                         rows=self._launch_rows(m, "phaser"), dmod=dmod, grads=g)[1]
         return dmod
 
     @staticmethod
@@ -523,10 +673,11 @@ class LFOExtractionThroughEffect(BaseLightingModule):
         from .effect_losses import effect_loss_terms
         dry_r, wet_r = self._rows(dry), self._rows(wet)
         terms: Dict[str, T] = {}
-        if torch.is_grad_enabled() and mod_sig_hat.requires_grad:
+        raw = None if self.learned_fx is None else self.learned_fx.raw
+        if torch.is_grad_enabled() and (mod_sig_hat.requires_grad or (raw is not None and raw.requires_grad)):
             with torch.no_grad():
                 consts = self.clip_constants(fx_params, dry_r.size(0), dry_r.device)
-            loss, wet_hat = _EffectAudioLossFn.apply(mod_sig_hat, self, dry_r, wet_r, consts, terms)
+            loss, wet_hat = _EffectAudioLossFn.apply(mod_sig_hat, raw, self, dry_r, wet_r, consts, terms)
             wet_hat = wet_hat.unsqueeze(1)
         else:
             wet_hat, loss = self.render(dry, mod_sig_hat, fx_params), None
@@ -548,7 +699,10 @@ class LFOExtractionThroughEffect(BaseLightingModule):
     def common_step(self, batch, is_training: bool):
         prefix = "train" if is_training else "val"
         dry, wet, mod_sig, fx_params = batch
-        assert dry is not None and fx_params is not None, "the re-render needs the dry clip and the effect parameters"
+        assert dry is not None, "the re-render needs the dry clip"
+        missing = self.missing_fx_params(fx_params, dry.size(0))
+        if missing:
+            raise ValueError(f"the re-render needs {missing}: neither in the batch's fx_params nor learned / fixed by learned_fx")
         mod_sig_hat, _ = self.model(stack_dry_wet(dry, wet) if self.use_dry else wet)
         mod_sig_hat = mod_sig_hat.squeeze(1)
         if mod_sig is not None:
@@ -572,6 +726,9 @@ class LFOExtractionThroughEffect(BaseLightingModule):
             if lfo_term is not None:
                 loss = loss + lfo_term
         self.log(f"{prefix}/loss", loss)
+        if is_training and self.learned_fx is not None:             # views of the launch's values vector: no host sync
+            for i, name in enumerate(self.step_metric_names):
+                self.log(name, self._fx_values[i])
         data_dict = {"dry": dry.detach(), "wet": wet.detach(), "wet_hat": wet_hat.detach(),
                      "mod_sig_hat": mod_sig_hat.detach()}
         if mod_sig is not None:

@@ -117,8 +117,10 @@ def reduce_metrics(logged: Dict[str, List[torch.Tensor]], world_size: int,
 
 
 def metric_names(module, prefix: str) -> List[str]:
-    """The scalars a BaseLightingModule logs per step under ``prefix`` (lightning.py:33-62)."""
-    return [f"{prefix}/{k}" for k in getattr(module, "loss_dict", {})] + [f"{prefix}/loss"]
+    """The scalars a BaseLightingModule logs per step under ``prefix`` (lightning.py:33-62); a training step may log more
+    under names of its own (``step_metric_names``: the learned effect parameters, ``fx/<kind>.<name>``)."""
+    extra = list(getattr(module, "step_metric_names", ())) if prefix == "train" else []
+    return [f"{prefix}/{k}" for k in getattr(module, "loss_dict", {})] + [f"{prefix}/loss"] + extra
 
 
 def _limit(n: int, limit) -> int:
