@@ -302,7 +302,11 @@ int mx_conv_block_dgrad(const float *G, const uint8_t *amax, const float *wt_fli
  * an fp16 pair hi + lo, products are hi*hi + hi*lo + lo*hi accumulated in fp32; 3 MFMAs at 16x the fp32 MFMA
  * rate).  Same reference semantics as mx_conv_block_fwd / mx_conv_block_dgrad (models.py:183-195) for the
  * 64->64 channel blocks.  Operands are prepared once per layer as channels-last fp16 pairs:
- *   w_hi, w_lo : 4*5*13*64*16 halfs each ([ci/16][kh][kw][co][16], weights * 256; flip = 1 for the data gradient)
+ *   w_hi, w_lo : 4*5*13*64*16 halfs each, [cb][kh][kw][khalf][out][8] of weights * 256: the 16 input channels of block cb
+ *                lie in two planes of 8, input channel = 16 cb + 8 khalf + j (j = the last index).  flip = 0 (forward):
+ *                element = W[co = out][ci = 16 cb + 8 khalf + j][kh][kw] * 256.  flip = 1 (data gradient): the roles of the
+ *                channels are exchanged and the taps mirrored, element = W[co = 16 cb + 8 khalf + j][ci = out][4 - kh][12 - kw]
+ *                * 256, so that the same kernel computes the transposed convolution
  *   x_hi, x_lo : (B, H, 4, 352, 16) halfs (channel-block major): forward = split of (prelu(x) - mean) * rstd;
  *                dgrad = split of the max-pool routed gradient * S_dz, S_dz = 2^k chosen from max|G|
  *                (scale (2,) device floats receives {S_dz, 1/S_dz}; amax_ws = one uint32 workspace, or with
@@ -363,10 +367,13 @@ int mx_conv_block_wgrad(const float *G, const uint8_t *amax, const float *x, con
  * (position, row of the pooling pair) the routed gradient is 2:4 structured sparse -- its compressed form is the pooled
  * gradient G itself, its index bits are the pooling argmax -- so one instruction covers both rows of a pooling pair
  * (half the matrix instructions of mx_conv_block_wgrad_f16; identical results up to fp32 summation order).
- * g_hi, g_lo (B,H/2,4,352,16) halfs = the channels-last split of G * S and gidx (B,64,H/2,22,2) uint16 index words, both
+ * g_hi, g_lo (B,H/2,4,352,16) halfs = the channels-last split of G * S and gidx (B,64,H/2,22,2) uint16 index words (word of
+ * (k-step ks of 16 positions, lane half hh): field j = 2 gq + e, j = 0..7, in bits [2 j, 2 j + 2) = 2 e + (amax & 1) at
+ * position 16 ks + 8 (gq >> 1) + 4 hh + 2 (gq & 1) + e), both
  * from mx_conv_prep_gpool_cl_f16 below (the pair is the operand of the sparse data gradient as well; its [position]
  * [channel] rows become the A fragments through transposing LDS reads).  rows_per_slab counts POOLED rows;
- * Wv <= 351 (MX_ERR_UNSUPPORTED otherwise: the zero pad column of the x operand is the kernel's halo source);
+ * Wv <= 351 (MX_ERR_UNSUPPORTED otherwise: the zero pad column of the x operand is the kernel's halo source); H even, >= 2
+ * (MX_ERR_UNSUPPORTED otherwise, as mx_conv_block_fwd_f16 and both data gradients);
  * part: ceil(B*(H/2)/rows_per_slab)*65*64*64 floats. */
 int mx_conv_block_wgrad_sp_f16(const void *g_hi, const void *g_lo, const void *gidx, const void *x_hi, const void *x_lo,
                                const float *scale, int64_t B, int64_t H, int64_t Wv, int32_t dilation,
@@ -376,9 +383,19 @@ int mx_conv_block_wgrad_sp_f16(const void *g_hi, const void *g_lo, const void *g
  * transposed ([position][ci]) with K = (output channel, row of the pooling pair): compressed A = the pooled gradient
  * in channels-last form, B = the weights of the two kernel rows the pair meets, packed in fragment order and read
  * from global memory; 12 K stages instead of 20.  Same results as mx_conv_block_dgrad_f16 up to summation order.
- *   mx_conv_pack_weights_sp_f16: W (64,64,5,13) -> w_hi, w_lo: 4*3*2*13*2*64*16 halfs each
+ *   mx_conv_pack_weights_sp_f16: W (64,64,5,13) -> w_hi, w_lo: 4*3*2*13*2*64*16 halfs each, [cb][m][r][kwf][ci tile][lane][16]
+ *                              of weights * 256 in fragment order: for output row h = 2 hp + r the pooling pair hp + m - 1
+ *                              (m = 0, 1, 2) and the position w + (kwf - 6) * dilation; lane l holds column n = l & 31 and
+ *                              k half s = l >> 5, its element j is k = 16 s + j: output channel co = 16 cb + (k >> 1), row
+ *                              of the pair = k & 1, hence kernel row kh = 4 + r - 2 m - (k & 1) (element = 0 where kh is
+ *                              outside 0..4), kernel column kw = 12 - kwf, input channel ci = 32 (ci tile) + n:
+ *                              element = W[co][ci][kh][kw] * 256
  *   mx_conv_prep_gpool_cl_f16: G, amax (B,64,H/2,352), scale {S, 1/S} -> g_hi, g_lo (B,H/2,4,352,16) halfs,
- *                              g_idx (B,H/2,4,352) uint32 index words of the data gradient; gidx (or NULL):
+ *                              g_idx (B,H/2,4,352) uint32 index words of the data gradient: the word of (clip, pooled
+ *                              row, channel block cb, position) holds sixteen 2-bit fields, field j (j = 0..7) of lane half
+ *                              hf (0, 1) in bits [16 hf + 2 j, 16 hf + 2 j + 2) = 2 (j & 1) + (amax & 1) of output channel
+ *                              16 cb + (j < 4 ? 4 hf + j : 8 + 4 hf + j - 4); every one of the 352 positions has a word
+ *                              (from amax as it stands there), while g_hi, g_lo are +0 at positions >= Wv; gidx (or NULL):
  *                              (B,64,H/2,22,2) uint16 index words of mx_conv_block_wgrad_sp_f16 from the same pass
  *                              (mx_conv_prep_dgrad_f16 with dz_hi = dz_lo = NULL then only computes the scale pair)
  *   mx_conv_block_dgrad_sp_f16: dxhat (B,64,H,352); Wv <= 351 (zero pad column = halo source).  x_hi, x_lo, ln_part

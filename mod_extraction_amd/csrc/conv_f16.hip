@@ -18,7 +18,7 @@
 //                11 KB run of full cache lines (with the 64 channels of a position adjacent, every stage would touch
 //                a quarter of each line of the row and the row would be pulled from HBM once per block: measured 16x
 //                the algorithmic traffic)
-//   W_hi, W_lo : [ci/16][kh][kw][co][16]  weights * 256
+//   W_hi, W_lo : [ci/16][kh][kw][khalf][co][8]  weights * 256 (pack_weights_f16_kernel)
 // so that the conv kernel stages plain 16-byte vectors and every MFMA fragment (8 consecutive channels of
 // one position / one output channel) is ONE aligned ds_read_b128.
 //
@@ -43,13 +43,16 @@ __device__ __forceinline__ floatx16 mfma16(half8 a, half8 b, floatx16 c)
 
 // ---- operand preparation -----------------------------------------------------------------------------
 // scale[0] = S (power of two with max|x| * S in [512, 1024)), scale[1] = 1 / S; amax_bits = bit pattern of max|x|
-__global__ void absmax_kernel(const float *__restrict__ x, long long n4, unsigned *__restrict__ amax_bits)
+// (over the Wv valid columns of the 352-float rows only: what the pad columns hold must not reach the scale)
+__global__ void absmax_kernel(const float *__restrict__ x, long long n4, int Wv, unsigned *__restrict__ amax_bits)
 {
     float m = 0.0f;
     const floatx4 *p = reinterpret_cast<const floatx4 *>(x);
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) {
         floatx4 v = p[i];
-        m = fmaxf(m, fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3]))));
+        const int w0 = (int)(i % (CV_PITCH / 4)) * 4;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) m = fmaxf(m, w0 + e < Wv ? fabsf(v[e]) : 0.0f);
     }
     m = wave_max_f32(m);
     if ((threadIdx.x & 63) == 0) atomicMax(amax_bits, __float_as_uint(m));   // order of non-negative floats = order of bits
@@ -1520,7 +1523,7 @@ MX_EXPORT int mx_conv_prep_dgrad_f16(const float *G, const uint8_t *amax, int64_
     if (!amax_ready) {          // otherwise *amax_ws already holds the bits of max|G| (mx_ln_prelu_bwd's gmax_bits)
         if (hipMemsetAsync(amax_ws, 0, sizeof(uint32_t), st) != hipSuccess) return MX_ERR_LAUNCH;
         const long long n4 = (long long)B * 64 * (H / 2) * CV_PITCH / 4;
-        hipLaunchKernelGGL(absmax_kernel, dim3(2048), dim3(256), 0, st, G, n4, amax_ws);
+        hipLaunchKernelGGL(absmax_kernel, dim3(2048), dim3(256), 0, st, G, n4, (int)Wv, amax_ws);
     }
     hipLaunchKernelGGL(pow2_scale_kernel, dim3(1), dim3(1), 0, st, amax_ws, scale);
     if (!dz_hi) return mx_launch_status();

@@ -541,9 +541,9 @@ MX_EXPORT int mx_conv_block_wgrad_sp_f16(const void *gp_hi, const void *gp_lo, c
                                          const void *x_lo, const float *scale, int64_t B, int64_t H, int64_t Wv,
                                          int32_t dilation, int64_t rows_per_slab, float *part, float *dW, void *stream)
 {
-    if (!gp_hi || !gp_lo || !gidx || !x_hi || !x_lo || !scale || !part || !dW || B <= 0 || H < 2 || (H & 1) ||
-        rows_per_slab <= 0 || Wv <= 0)
+    if (!gp_hi || !gp_lo || !gidx || !x_hi || !x_lo || !scale || !part || !dW || B <= 0 || rows_per_slab <= 0 || Wv <= 0)
         return MX_ERR_ARG;
+    if (H < 2 || (H & 1)) return MX_ERR_UNSUPPORTED;       // whole pooling pairs, as the forward and data-gradient entry points
     if (Wv > CV_PITCH - 1) return MX_ERR_UNSUPPORTED;      // the kernel reads operand column 351 as its zero source
     const int64_t n_slabs = (B * (H / 2) + rows_per_slab - 1) / rows_per_slab;
     if (n_slabs > 1000000) return MX_ERR_UNSUPPORTED;
