@@ -816,4 +816,6 @@ int mx_fx_params_grad(const double *grads, const float *raw, const double *tab_f
 #ifdef __cplusplus
 }
 #endif
+/* K17, the per-clip effect-parameter head (csrc/fx_head.hip): two more entry points, declared in a file of their own */
+#include "modex_fx_head.h"
 #endif /* MODEX_HIP_H */

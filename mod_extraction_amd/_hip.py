@@ -135,6 +135,13 @@ SIGNATURES = {
     "mx_fx_params_grad": [_P, _P, _P, _P, _I64, _F64, _P, _P, _P, _I64, _F64, _P, _P],
 }
 
+# name -> argtypes of what include/modex_fx_head.h declares (K17, the per-clip effect-parameter head): a table of its own,
+# as the declarations have a header of their own; ``load`` binds both tables
+HEAD_SIGNATURES = {
+    "mx_fx_head_fwd": [_P, _I64, _I64, _I64, _P, _P, _P, _P, _I64, _F64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+    "mx_fx_head_bwd": [_P, _P, _P, _P, _P, _P, _I64, _F64, _P, _P, _P, _I64, _I64, _I64, _F64, _P, _P, _P, _P, _P],
+}
+
 # measurement twins (same signatures): the dependent chain of the sample-recurrent kernels without global traffic
 PROBE_TWINS = ("mx_flanger_fwd", "mx_phaser_fwd", "mx_lstm_fwd", "mx_lstm_bwd_l1")
 for _name in PROBE_TWINS:
@@ -155,7 +162,7 @@ def load() -> ctypes.CDLL:
                 f"{SO_PATH} not found: build it with `python -m mod_extraction_amd.build` "
                 "(there is no CPU fallback)")
         lib = ctypes.CDLL(SO_PATH)
-        for name, argtypes in SIGNATURES.items():
+        for name, argtypes in list(SIGNATURES.items()) + list(HEAD_SIGNATURES.items()):
             fn = getattr(lib, name)          # AttributeError if the .so lacks a declared symbol
             fn.argtypes = argtypes
             fn.restype = ctypes.c_int

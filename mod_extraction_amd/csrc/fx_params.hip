@@ -16,40 +16,7 @@
 //     butterfly, the four waves in order), times d value / d raw and the scale in fp64, rounded once.  No atomics, no
 //     workspace: the same inputs give the same bits.  Rows of other kinds are never read (they may be uninitialised).
 // Both are launch-latency kernels: a few hundred bytes of traffic each.
-#include "common.h"
-
-#define FXP_MAX_ENTRIES 16
-#define FXP_LFO_SCALE 0
-#define FXP_MIN_DELAY 1
-#define FXP_FEEDBACK 2
-#define FXP_DEPTH 3
-#define FXP_MIX 4
-#define FXP_CENTRE 5
-#define FXP_SLOTS 6
-#define FXP_THREADS 256
-
-struct FxpOut { float *v[FXP_SLOTS]; float *one_minus_mix; };
-
-__device__ __forceinline__ double fxp_sigmoid(double z)
-{
-    if (z >= 0.0) return 1.0 / (1.0 + exp(-z));
-    const double e = exp(z);
-    return e / (1.0 + e);
-}
-// the mapped value and its derivative with respect to raw
-__device__ __forceinline__ double fxp_value(double raw, double gain, double lo, double hi, int is_log, double *dv)
-{
-    const double s = fxp_sigmoid(gain * raw);
-    const double ds = gain * s * (1.0 - s);
-    if (is_log) {
-        const double l0 = log(lo), span = log(hi) - l0;
-        const double v = exp(l0 + span * s);
-        if (dv) *dv = v * span * ds;
-        return v;
-    }
-    if (dv) *dv = (hi - lo) * ds;
-    return lo + (hi - lo) * s;
-}
+#include "fx_params_common.h"
 
 __global__ __launch_bounds__(FXP_THREADS) void fx_params_expand_kernel(
     const float *__restrict__ raw, const double *__restrict__ tab_f, const int *__restrict__ tab_i, int P, double gain,

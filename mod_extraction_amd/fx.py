@@ -834,7 +834,7 @@ FX_PARAM_NAMES = {"flanger": ("feedback", "min_delay_width", "width", "depth", "
                   "phaser": ("depth", "centre_frequency_hz", "feedback", "mix")}
 FX_NAME_SLOT = {"width": "lfo_scale", "min_delay_width": "min_delay", "feedback": "feedback", "depth": "depth", "mix": "mix",
                 "centre_frequency_hz": "centre_frequency_hz"}
-FX_MAX_LEARNED = 16                                                 # FXP_MAX_ENTRIES of csrc/fx_params.hip
+FX_MAX_LEARNED = 16                                                 # FXP_MAX_ENTRIES of csrc/fx_params_common.h
 
 
 def _fx_param_range(kind: str, name: str) -> Tuple[float, float, bool, bool]:
@@ -884,7 +884,83 @@ def fx_params_grad(grads: T, raw: T, tab_f: T, tab_i: T, raw_gain: float, row_ki
     return d_raw
 
 
-class LearnedFxParams(nn.Module):
+class _FxParamTable(nn.Module):
+    """What ``LearnedFxParams`` and ``FxParamHead`` share: the ``spec`` grammar and its checks, ``names`` / ``kinds`` / ``fixed``
+    and the kernels' table.  ``_parse`` returns raw's initial values, logit(init) / raw_gain per entry; ``what`` names the
+    argument in the error messages."""
+
+    def _parse(self, spec: Dict[str, Dict[str, object]], raw_gain: float, what: str) -> T:
+        import math
+        if not isinstance(spec, dict) or not spec:
+            raise ValueError(f"{what}: a dict keyed by effect kind")
+        if not (isinstance(raw_gain, (int, float)) and math.isfinite(raw_gain) and raw_gain > 0):
+            raise ValueError(f"raw_gain {raw_gain!r}: a positive number")
+        self.raw_gain = float(raw_gain)
+        self.names, self.fixed = [], {}
+        lo, hi, is_log, slot, kind_code, init_raw = [], [], [], [], [], []
+        for kind, params in spec.items():
+            if kind not in FX_PARAM_NAMES:
+                raise ValueError(f"{what}: unknown kind '{kind}' (supported: {tuple(FX_PARAM_NAMES)})")
+            if not isinstance(params, dict):
+                raise ValueError(f"{what}.{kind}: a dict of parameter names")
+            for name in params:
+                if name not in FX_PARAM_NAMES[kind]:
+                    raise ValueError(f"{what}: '{kind}' has no parameter '{name}' (it has {FX_PARAM_NAMES[kind]})")
+            for name in FX_PARAM_NAMES[kind]:
+                if name not in params:
+                    continue
+                entry, full = params[name], f"{kind}.{name}"
+                a, b, a_open, b_open = _fx_param_range(kind, name)
+                if not isinstance(entry, dict):
+                    v = float(entry)
+                    if not ((v > a if a_open else v >= a) and (v < b if b_open else v <= b)):
+                        raise ValueError(f"{what}.{full} = {v}: outside the effect's range")
+                    self.fixed[(kind, name)] = v
+                    continue
+                unknown = set(entry) - {"min", "max", "init", "scale"}
+                if unknown or not {"min", "max", "init"} <= set(entry):
+                    raise ValueError(f"{what}.{full}: keys min, max, init and optionally scale (got {sorted(entry)})")
+                mn, mx, init = float(entry["min"]), float(entry["max"]), float(entry["init"])
+                scale = entry.get("scale", "log" if name == "centre_frequency_hz" else "lin")
+                if scale not in ("lin", "log"):
+                    raise ValueError(f"{what}.{full}: scale '{scale}' (lin or log)")
+                if not all(math.isfinite(v) for v in (mn, mx, init)) or not mn < init < mx:
+                    raise ValueError(f"{what}.{full}: min < init < max does not hold ({mn}, {init}, {mx})")
+                if not ((mn > a if a_open else mn >= a) and (mx < b if b_open else mx <= b)):
+                    raise ValueError(f"{what}.{full}: the range [{mn}, {mx}] must lie inside "
+                                     f"{'(' if a_open else '['}{a}, {b}{')' if b_open else ']'}")
+                if scale == "log" and mn <= 0:
+                    raise ValueError(f"{what}.{full}: a log scale needs min > 0")
+                s = (math.log(init / mn) / math.log(mx / mn)) if scale == "log" else (init - mn) / (mx - mn)
+                self.names.append(full)
+                lo.append(mn), hi.append(mx), is_log.append(int(scale == "log"))
+                slot.append(FX_SLOTS.index(FX_NAME_SLOT[name])), kind_code.append(FX_KINDS.index(kind))
+                init_raw.append(math.log(s / (1.0 - s)) / self.raw_gain)
+        if not 1 <= len(self.names) <= FX_MAX_LEARNED:
+            raise ValueError(f"{what}: {len(self.names)} learned entries (1 .. {FX_MAX_LEARNED} are supported)")
+        self.kinds = tuple(spec)
+        # the kernels' table; not part of the state dict (the spec rebuilds it)
+        self.register_buffer("tab_f", torch.tensor([lo, hi], dtype=torch.float64), persistent=False)
+        self.register_buffer("tab_i", torch.tensor([is_log, slot, kind_code], dtype=torch.int32), persistent=False)
+        return torch.tensor(init_raw, dtype=torch.float64).float()
+
+    def learned(self, kind: str) -> Tuple[str, ...]:
+        """The learned parameter names of a kind."""
+        return tuple(n.split(".", 1)[1] for n in self.names if n.split(".", 1)[0] == kind)
+
+    def covers(self, kind: str, name: str) -> bool:
+        return (kind, name) in self.fixed or f"{kind}.{name}" in self.names
+
+    def _map(self, raw: T) -> T:
+        """The mapped values of raw (..., P), fp64, by torch expressions."""
+        s = torch.sigmoid(self.raw_gain * raw.double())
+        lo, hi = self.tab_f[0], self.tab_f[1]
+        log = self.tab_i[0] != 0
+        lo_l, hi_l = torch.where(log, lo, torch.ones_like(lo)).log(), torch.where(log, hi, torch.ones_like(hi)).log()
+        return torch.where(log, torch.exp(lo_l + (hi_l - lo_l) * s), lo + (hi - lo) * s)
+
+
+class LearnedFxParams(_FxParamTable):
     """Effect parameters fitted together with the LFO extractor (``lightning.LFOExtractionThroughEffect(learned_fx=...)``):
     ONE shared value per (kind, name), not one per clip.  ``spec``: a dict keyed by kind (``flanger``, ``chorus``,
     ``tremolo``, ``phaser``); under each kind a parameter name maps to ``{min, max, init[, scale: lin | log]}`` = learned, or
@@ -906,74 +982,11 @@ class LearnedFxParams(nn.Module):
 
     def __init__(self, spec: Dict[str, Dict[str, object]], raw_gain: float = 1.0) -> None:
         super().__init__()
-        import math
-        if not isinstance(spec, dict) or not spec:
-            raise ValueError("learned_fx: a dict keyed by effect kind")
-        if not (isinstance(raw_gain, (int, float)) and math.isfinite(raw_gain) and raw_gain > 0):
-            raise ValueError(f"raw_gain {raw_gain!r}: a positive number")
-        self.raw_gain = float(raw_gain)
-        self.names, self.fixed = [], {}
-        lo, hi, is_log, slot, kind_code, init_raw = [], [], [], [], [], []
-        for kind, params in spec.items():
-            if kind not in FX_PARAM_NAMES:
-                raise ValueError(f"learned_fx: unknown kind '{kind}' (supported: {tuple(FX_PARAM_NAMES)})")
-            if not isinstance(params, dict):
-                raise ValueError(f"learned_fx.{kind}: a dict of parameter names")
-            for name in params:
-                if name not in FX_PARAM_NAMES[kind]:
-                    raise ValueError(f"learned_fx: '{kind}' has no parameter '{name}' (it has {FX_PARAM_NAMES[kind]})")
-            for name in FX_PARAM_NAMES[kind]:
-                if name not in params:
-                    continue
-                entry, full = params[name], f"{kind}.{name}"
-                a, b, a_open, b_open = _fx_param_range(kind, name)
-                if not isinstance(entry, dict):
-                    v = float(entry)
-                    if not ((v > a if a_open else v >= a) and (v < b if b_open else v <= b)):
-                        raise ValueError(f"learned_fx.{full} = {v}: outside the effect's range")
-                    self.fixed[(kind, name)] = v
-                    continue
-                unknown = set(entry) - {"min", "max", "init", "scale"}
-                if unknown or not {"min", "max", "init"} <= set(entry):
-                    raise ValueError(f"learned_fx.{full}: keys min, max, init and optionally scale (got {sorted(entry)})")
-                mn, mx, init = float(entry["min"]), float(entry["max"]), float(entry["init"])
-                scale = entry.get("scale", "log" if name == "centre_frequency_hz" else "lin")
-                if scale not in ("lin", "log"):
-                    raise ValueError(f"learned_fx.{full}: scale '{scale}' (lin or log)")
-                if not all(math.isfinite(v) for v in (mn, mx, init)) or not mn < init < mx:
-                    raise ValueError(f"learned_fx.{full}: min < init < max does not hold ({mn}, {init}, {mx})")
-                if not ((mn > a if a_open else mn >= a) and (mx < b if b_open else mx <= b)):
-                    raise ValueError(f"learned_fx.{full}: the range [{mn}, {mx}] must lie inside "
-                                     f"{'(' if a_open else '['}{a}, {b}{')' if b_open else ']'}")
-                if scale == "log" and mn <= 0:
-                    raise ValueError(f"learned_fx.{full}: a log scale needs min > 0")
-                s = (math.log(init / mn) / math.log(mx / mn)) if scale == "log" else (init - mn) / (mx - mn)
-                self.names.append(full)
-                lo.append(mn), hi.append(mx), is_log.append(int(scale == "log"))
-                slot.append(FX_SLOTS.index(FX_NAME_SLOT[name])), kind_code.append(FX_KINDS.index(kind))
-                init_raw.append(math.log(s / (1.0 - s)) / self.raw_gain)
-        if not 1 <= len(self.names) <= FX_MAX_LEARNED:
-            raise ValueError(f"learned_fx: {len(self.names)} learned entries (1 .. {FX_MAX_LEARNED} are supported)")
-        self.kinds = tuple(spec)
-        self.raw = nn.Parameter(torch.tensor(init_raw, dtype=torch.float64).float())
-        # the kernels' table; not part of the state dict (the spec rebuilds it)
-        self.register_buffer("tab_f", torch.tensor([lo, hi], dtype=torch.float64), persistent=False)
-        self.register_buffer("tab_i", torch.tensor([is_log, slot, kind_code], dtype=torch.int32), persistent=False)
-
-    def learned(self, kind: str) -> Tuple[str, ...]:
-        """The learned parameter names of a kind."""
-        return tuple(n.split(".", 1)[1] for n in self.names if n.split(".", 1)[0] == kind)
-
-    def covers(self, kind: str, name: str) -> bool:
-        return (kind, name) in self.fixed or f"{kind}.{name}" in self.names
+        self.raw = nn.Parameter(self._parse(spec, raw_gain, "learned_fx"))
 
     def values(self) -> T:
         """The P mapped values, fp64, by torch expressions (differentiable with respect to ``raw``)."""
-        s = torch.sigmoid(self.raw_gain * self.raw.double())
-        lo, hi = self.tab_f[0], self.tab_f[1]
-        log = self.tab_i[0] != 0
-        lo_l, hi_l = torch.where(log, lo, torch.ones_like(lo)).log(), torch.where(log, hi, torch.ones_like(hi)).log()
-        return torch.where(log, torch.exp(lo_l + (hi_l - lo_l) * s), lo + (hi - lo) * s)
+        return self._map(self.raw)
 
     def expand(self, consts: Dict[str, T], row_kind: T, max_lfo_delay: Optional[T], max_min_delay: Optional[T]) -> T:
         """``fx_params_expand`` with this module's table: writes into ``consts`` in place, returns values (P,) fp32."""
@@ -984,3 +997,107 @@ class LearnedFxParams(nn.Module):
         """``fx_params_grad`` with this module's table: d loss / d raw (P,) fp32."""
         return fx_params_grad(grads, self.raw.detach(), self.tab_f, self.tab_i, self.raw_gain, row_kind, max_lfo_delay,
                               max_min_delay, scale)
+
+
+# ---- per-clip effect parameters from a head on the extractor's latent (csrc/fx_head.hip, DESIGN K17) -------------------------
+FX_HEAD_MAX_CHANNELS = 1024                                         # FXH_MAX_C of csrc/fx_head.hip
+
+
+def fx_head_forward(latent: T, weight: T, bias: T, tab_f: T, tab_i: T, raw_gain: float, row_kind: T,
+                    max_lfo_delay: Optional[T], max_min_delay: Optional[T], consts: Dict[str, T],
+                    pooled: Optional[T] = None, raw_rows: Optional[T] = None,
+                    values: Optional[T] = None) -> Tuple[T, T, T]:
+    """Launch mx_fx_head_fwd: latent (B, C, W) fp32 dense -> pooled (B, C) = its mean over w, raw_rows (B, P) = bias + pooled
+    weight^T, values (B, P) = the map of ``fx_params_expand`` applied to raw_rows, all fp32; on the rows of an entry's kind the
+    value is also written into the (B,) fp32 vectors of ``consts`` (keys out of ``FX_CONSTS``; a missing key skips its slot),
+    in place, by the rule of ``fx_params_expand``; rows and slots without an entry keep what they hold.  weight (P, C), bias
+    (P,) fp32; the table and row_kind as there.  Returns (pooled, raw_rows, values)."""
+    assert latent.ndim == 3 and latent.dtype == torch.float32
+    B, C, W = latent.shape
+    P = bias.numel()
+    assert weight.shape == (P, C) and weight.dtype == bias.dtype == torch.float32 and bias.shape == (P,)
+    assert tab_f.shape == (2, P) and tab_f.dtype == torch.float64 and tab_i.shape == (3, P) and tab_i.dtype == torch.int32
+    assert row_kind.shape == (B,) and row_kind.dtype == torch.int32
+    for k, v in consts.items():
+        assert k in FX_CONSTS and v.shape == (B,) and v.dtype == torch.float32, k
+    for v in (max_lfo_delay, max_min_delay):
+        assert v is None or (v.shape == (B,) and v.dtype == torch.float32)
+    dev = latent.device
+    pooled = torch.empty((B, C), device=dev, dtype=torch.float32) if pooled is None else pooled
+    raw_rows = torch.empty((B, P), device=dev, dtype=torch.float32) if raw_rows is None else raw_rows
+    values = torch.empty((B, P), device=dev, dtype=torch.float32) if values is None else values
+    assert pooled.shape == (B, C) and raw_rows.shape == values.shape == (B, P)
+    assert pooled.dtype == raw_rows.dtype == values.dtype == torch.float32
+    _hip.call("mx_fx_head_fwd", _hip.ptr(latent), B, C, W, _hip.ptr(weight), _hip.ptr(bias), _hip.ptr(tab_f), _hip.ptr(tab_i), P,
+              float(raw_gain), _hip.ptr(row_kind), _hip.ptr(max_lfo_delay), _hip.ptr(max_min_delay),
+              *[_hip.ptr(consts.get(k)) for k in FX_CONSTS], _hip.ptr(pooled), _hip.ptr(raw_rows), _hip.ptr(values),
+              _hip.stream())
+    return pooled, raw_rows, values
+
+
+def fx_head_backward(grads: T, raw_rows: T, pooled: T, weight: T, tab_f: T, tab_i: T, raw_gain: float, row_kind: T,
+                     max_lfo_delay: T, max_min_delay: T, W: int, scale: float = 1.0, need_d_raw_rows: bool = False,
+                     need_d_latent: bool = True) -> Tuple[Optional[T], T, T, Optional[T]]:
+    """Launch mx_fx_head_bwd: from grads (6, B) fp64 (the per-clip gradients of the constants in ``FX_SLOTS`` order, as the
+    effect adjoints write them; rows of kinds without an entry for a slot are not read) and what ``fx_head_forward`` returned,
+    (d_raw_rows (B, P) or None, d_bias (P,), d_weight (P, C), d_latent (B, C, W) or None), all fp32, times ``scale``.  Every
+    element of d_latent is written (rows without an entry: zeros).  Deterministic."""
+    B, P = raw_rows.shape
+    C = pooled.size(1)
+    assert grads.shape == (len(FX_SLOTS), B) and grads.dtype == torch.float64
+    assert raw_rows.dtype == pooled.dtype == weight.dtype == torch.float32 and pooled.shape == (B, C) and weight.shape == (P, C)
+    assert tab_f.shape == (2, P) and tab_f.dtype == torch.float64 and tab_i.shape == (3, P) and tab_i.dtype == torch.int32
+    assert row_kind.shape == (B,) and row_kind.dtype == torch.int32 and W >= 1
+    assert max_lfo_delay.shape == max_min_delay.shape == (B,) and max_lfo_delay.dtype == max_min_delay.dtype == torch.float32
+    dev = raw_rows.device
+    d_rows = torch.empty((B, P), device=dev, dtype=torch.float32) if need_d_raw_rows else None
+    d_bias = torch.empty((P,), device=dev, dtype=torch.float32)
+    d_weight = torch.empty((P, C), device=dev, dtype=torch.float32)
+    d_latent = torch.empty((B, C, W), device=dev, dtype=torch.float32) if need_d_latent else None
+    _hip.call("mx_fx_head_bwd", _hip.ptr(grads), _hip.ptr(raw_rows), _hip.ptr(pooled), _hip.ptr(weight), _hip.ptr(tab_f),
+              _hip.ptr(tab_i), P, float(raw_gain), _hip.ptr(row_kind), _hip.ptr(max_lfo_delay), _hip.ptr(max_min_delay), B, C,
+              int(W), float(scale), _hip.ptr(d_rows), _hip.ptr(d_bias), _hip.ptr(d_weight), _hip.ptr(d_latent), _hip.stream())
+    return d_rows, d_bias, d_weight, d_latent
+
+
+class FxParamHead(_FxParamTable):
+    """Effect parameters PER CLIP, predicted from the extractor's latent (``lightning.LFOExtractionThroughEffect(fx_head=...)``):
+    raw[b] = bias + weight mean_w latent[b, :, w], then the map of ``LearnedFxParams`` entry by entry.  ``spec``, its checks
+    and ValueErrors, ``names``, ``kinds``, ``fixed``, ``learned``, ``covers``, ``raw_gain`` and the table are those of
+    ``LearnedFxParams``; a bare number fixes a parameter for every clip.
+
+    Parameters ``weight`` (P, in_ch) fp32, zeros, and ``bias`` (P,) fp32 = logit(init) / raw_gain: a fresh head predicts
+    ``init`` for every clip, with the very bits ``LearnedFxParams`` writes, and departs from it only as ``weight`` learns.
+    in_ch: the latent's channel count, 1 .. 1024 (64 for ``models.Spectral2DCNN``).
+
+    ``values(latent)``: the (B, P) mapped values in fp64 by torch expressions (any device, differentiable).  The step's path
+    is ``forward_rows`` / ``backward_rows``: the ``mx_fx_head_fwd`` / ``mx_fx_head_bwd`` launches."""
+
+    def __init__(self, spec: Dict[str, Dict[str, object]], in_ch: int = 64, raw_gain: float = 1.0) -> None:
+        super().__init__()
+        if not (isinstance(in_ch, int) and 1 <= in_ch <= FX_HEAD_MAX_CHANNELS):
+            raise ValueError(f"in_ch {in_ch!r}: 1 .. {FX_HEAD_MAX_CHANNELS} latent channels")
+        self.in_ch = in_ch
+        bias = self._parse(spec, raw_gain, "fx_head")
+        self.weight = nn.Parameter(torch.zeros((bias.numel(), in_ch), dtype=torch.float32))
+        self.bias = nn.Parameter(bias)
+
+    def values(self, latent: T) -> T:
+        """The (B, P) mapped values of latent (B, in_ch, W), fp64, by torch expressions."""
+        assert latent.ndim == 3 and latent.size(1) == self.in_ch
+        pooled = latent.double().mean(-1)
+        return self._map(self.bias.double() + pooled @ self.weight.double().t())
+
+    def forward_rows(self, latent: T, consts: Dict[str, T], row_kind: T, max_lfo_delay: Optional[T],
+                     max_min_delay: Optional[T]) -> Tuple[T, T, T]:
+        """``fx_head_forward`` with this module's parameters and table: writes into ``consts`` in place, returns (pooled,
+        raw_rows, values)."""
+        return fx_head_forward(latent, self.weight.detach(), self.bias.detach(), self.tab_f, self.tab_i, self.raw_gain,
+                               row_kind, max_lfo_delay, max_min_delay, consts)
+
+    def backward_rows(self, grads: T, raw_rows: T, pooled: T, row_kind: T, max_lfo_delay: T, max_min_delay: T, W: int,
+                      scale: float = 1.0, need_d_latent: bool = True) -> Tuple[T, T, Optional[T]]:
+        """``fx_head_backward`` with this module's weight and table: (d_bias (P,), d_weight (P, in_ch), d_latent (B, in_ch,
+        W) or None)."""
+        return fx_head_backward(grads, raw_rows, pooled, self.weight.detach(), self.tab_f, self.tab_i, self.raw_gain, row_kind,
+                                max_lfo_delay, max_min_delay, W, scale, need_d_latent=need_d_latent)[1:]

@@ -209,18 +209,30 @@ class _EffectAudioLossFn(torch.autograd.Function):
     call."""
 
     @staticmethod
-    def forward(ctx, mod_sig_hat, raw, step, dry, wet, consts, terms):
+    def forward(ctx, mod_sig_hat, raw, step, dry, wet, consts, terms, latent=None, weight=None, bias=None):
         """``raw``: ``step.learned_fx.raw`` (the second differentiable input; ``consts`` already hold its mapped values) or
         None.  With it every family's adjoint is also asked for the per-clip fp64 gradients of its learned slots, rows of one
         (6, B) buffer, which ``mx_fx_params_grad`` reduces to d loss / d raw; without it the launches are those of the step
-        without learned parameters."""
+        without learned parameters.  ``latent``, ``weight``, ``bias`` (a step with ``fx_head``; ``consts`` already hold the
+        predicted values, ``step._head_rows`` what the forward launch kept): three more differentiable inputs, whose gradients
+        ``mx_fx_head_bwd`` forms from the same (6, B) buffer."""
         from .effect_losses import effect_loss_grad, effect_loss_terms
         mod = mod_sig_hat.detach().float().contiguous()
         wet_hat, stashes = step._render_rows(dry, mod, consts, stash=True)
         a, t = wet_hat.unsqueeze(1), wet.unsqueeze(1)
         weighted: Dict[str, T] = {}
         dy = effect_loss_grad(a, t, step.audio_loss_dict, values=weighted, **step._grad_modules())
-        if raw is None:
+        ctx.head = latent is not None
+        if ctx.head:
+            m = step._mixed_rows(dry.size(0), dry.device)
+            gbuf = torch.empty((6, dry.size(0)), device=dry.device, dtype=torch.float64)
+            dmod = step._adjoint_rows(dy, dry, mod, consts, stashes, gbuf=gbuf)
+            pooled, raw_rows = step._head_rows
+            d_bias, d_weight, d_latent = step.fx_head.backward_rows(
+                gbuf, raw_rows, pooled, m["row_kind"], m["max_lfo_delay"], m["max_min_delay"], latent.size(-1),
+                need_d_latent=latent.requires_grad)
+            ctx.save_for_backward(dmod, d_latent, d_weight, d_bias)
+        elif raw is None:
             dmod = step._adjoint_rows(dy, dry, mod, consts, stashes)
             ctx.save_for_backward(dmod)
         else:
@@ -240,6 +252,10 @@ class _EffectAudioLossFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g, _g_wet_hat):
         dmod = ctx.saved_tensors[0]
+        if ctx.head:
+            need = ctx.needs_input_grad
+            head = tuple(t * g if t is not None and n else None for t, n in zip(ctx.saved_tensors[1:], need[7:10]))
+            return (dmod * g if need[0] else None, None, None, None, None, None, None) + head
         d_raw = ctx.saved_tensors[1] * g if len(ctx.saved_tensors) > 1 and ctx.needs_input_grad[1] else None
         return (dmod * g if ctx.needs_input_grad[0] else None), d_raw, None, None, None, None, None
 
@@ -297,6 +313,16 @@ class LFOExtractionThroughEffect(BaseLightingModule):
       ``fx/<kind>.<name>``.  ``render`` and validation use the learned values.  The default adds no parameter and leaves
       the step's launches as they are.  What a fit cannot tell apart (``width`` and the LFO's amplitude, ``min_delay_width``
       and its offset, the flanger's ``mix * depth``): DESIGN section 7.
+    * ``fx_head`` (optional, not together with ``learned_fx``): a spec dict (the grammar of ``learned_fx``, plus the optional
+      keys ``in_ch`` and ``raw_gain`` beside the kinds) or an ``fx.FxParamHead`` -- effect parameters PER CLIP, predicted by one
+      linear layer on the mean over time of the model's latent, the second output of ``Spectral2DCNN.forward`` (B, in_ch,
+      n_frames); a model without it raises a ``ValueError``.  Precedence, fixed values, coverage and errors are those of
+      ``learned_fx``.  ``mx_fx_head_fwd`` writes the predicted values into the per-row constants, ``mx_fx_head_bwd`` turns the
+      adjoints' per-clip parameter gradients into the gradients of ``fx_head.weight`` / ``fx_head.bias`` (ordinary
+      parameters) and of the latent, which reaches the CNN's backward beside d loss / d LFO.  A fresh head (zero weight)
+      is ``learned_fx`` at its ``init``.  Every training step logs ``fx/<kind>.<name>`` = the mean of the predicted values
+      over the rows of that kind and ``fx_std/<kind>.<name>`` = their standard deviation; ``data_dict["fx_values"]`` holds
+      them all, (B, P).  ``render(..., latent=)`` needs the latent.
     * ``loss_dict`` (optional, default none): an LFO-domain term (lightning.py:33-62) added to the loss when the batch carries
       ``mod_sig``; it is logged as ``{prefix}/lfo_{name}``.
     The LFO enters the effect at the extractor's own rate (n_frames points, resampled in-kernel exactly as the data path
@@ -337,7 +363,8 @@ class LFOExtractionThroughEffect(BaseLightingModule):
                  chorus_max_lfo_delay_ms: Optional[float] = None,
                  pre_emph_filter_cfs: Sequence[float] = (-0.95, 1.0),
                  pre_emph_low_pass: bool = False,
-                 learned_fx=None) -> None:
+                 learned_fx=None,
+                 fx_head=None) -> None:
         super().__init__({} if loss_dict is None else loss_dict)
         self._set_pre_emph(pre_emph_filter_cfs, pre_emph_low_pass)
         from . import fx
@@ -410,10 +437,35 @@ class LFOExtractionThroughEffect(BaseLightingModule):
                 if k not in self._kinds:
                     raise ValueError(f"learned_fx names the kind '{k}', which is not among this step's kinds {self._kinds}")
         self.learned_fx = learned_fx                                # None registers nothing: the parameters are the model's
+        if fx_head is not None and learned_fx is not None:
+            raise ValueError("learned_fx and fx_head are mutually exclusive: shared and per-clip entries do not mix")
+        if isinstance(fx_head, dict):
+            spec = dict(fx_head)
+            extra = {k: spec.pop(k) for k in ("in_ch", "raw_gain") if k in spec}
+            fx_head = fx.FxParamHead(spec, **extra)
+        if fx_head is not None:
+            if not isinstance(fx_head, fx.FxParamHead):
+                raise ValueError("fx_head: a spec dict or an fx.FxParamHead")
+            for k in fx_head.kinds:
+                if k not in self._kinds:
+                    raise ValueError(f"fx_head names the kind '{k}', which is not among this step's kinds {self._kinds}")
+        self.fx_head = fx_head                                      # likewise
         self._fixed_plan = None
         self._fx_values: Optional[T] = None
+        self._head_rows: Optional[Tuple[T, T]] = None               # (pooled, raw_rows) of the last mx_fx_head_fwd
         # the scalars ``common_step`` logs per training step beside the losses (trainer.metric_names)
         self.step_metric_names = [] if learned_fx is None else [f"fx/{n}" for n in learned_fx.names]
+        if fx_head is not None:
+            self.step_metric_names = [f"fx/{n}" for n in fx_head.names] + [f"fx_std/{n}" for n in fx_head.names]
+
+    @property
+    def _fxp(self):
+        """Who supplies learned / fixed effect parameters: ``learned_fx``, ``fx_head`` or None."""
+        return self.learned_fx if self.learned_fx is not None else self.fx_head
+
+    @property
+    def _fxp_name(self) -> str:
+        return "fx_head" if self.fx_head is not None else "learned_fx"
 
     def _mixed_rows(self, bs: int, device) -> Dict[str, object]:
         """The row plan of a batch of ``bs`` rows on ``device`` (cached): the int32 row list of every launch family, the
@@ -436,10 +488,14 @@ class LFOExtractionThroughEffect(BaseLightingModule):
                  "dry_idx": torch.tensor(lists["dry"], dtype=torch.int64, device=device)}
             for name in ("delay", "tremolo", "phaser"):
                 m[name] = torch.tensor(lists[name], dtype=torch.int32, device=device)
-            if self.learned_fx is not None:                         # the kind code of every row (fx.FX_KINDS)
+            if self._fxp is not None:                               # the kind code of every row (fx.FX_KINDS)
                 from . import fx
                 m["kinds"] = kinds
                 m["row_kind"] = torch.tensor([fx.FX_KINDS.index(k) for k in kinds], dtype=torch.int32, device=device)
+            if self.fx_head is not None:                            # (B, P): row b is of entry e's kind; rows per entry (>= 1)
+                mask = torch.tensor([[float(k == n.split(".", 1)[0]) for n in self.fx_head.names] for k in kinds],
+                                    dtype=torch.float32).view(bs, len(self.fx_head.names))
+                m["head_mask"], m["head_count"] = mask.to(device), mask.sum(0).clamp(min=1.0).to(device)
             self._mixed = m
         return m
 
@@ -451,14 +507,15 @@ class LFOExtractionThroughEffect(BaseLightingModule):
         (``_render_rows`` / ``_adjoint_rows`` then allocate nothing themselves)."""
         return None if m["all_rows"] == family else m[family]
 
-    def clip_constants(self, fx_params, bs: int, device) -> Dict[str, T]:
+    def clip_constants(self, fx_params, bs: int, device, latent: Optional[T] = None) -> Dict[str, T]:
         """ONE dict of (B,) fp32 constants for all families of the batch, each formed as the data path forms it
         (``SyntheticFxBatcher.render``, ``fx.derive_clip_constants``): a tensor parameter meets the per-row sample count in
         fp32 and one_minus_mix is 1 - mix in fp32; a python float meets them in double and is rounded once.  So a re-render
-        from the label reproduces ``wet``.  Only what the kinds present need is read from ``fx_params``."""
+        from the label reproduces ``wet``.  Only what the kinds present need is read from ``fx_params``.  ``latent`` (B, in_ch,
+        W): what a step with ``fx_head`` predicts from."""
         from . import fx
-        if self.learned_fx is not None:
-            return self._learned_constants(fx_params, bs, device)
+        if self._fxp is not None:
+            return self._learned_constants(fx_params, bs, device, latent)
         missing = self.missing_fx_params(fx_params, bs)
         if missing:
             raise ValueError(f"fx_params lacks {missing}: the re-render needs them from the batch, or learned / fixed through "
@@ -504,28 +561,35 @@ class LFOExtractionThroughEffect(BaseLightingModule):
 
     def missing_fx_params(self, fx_params, bs: int) -> List[str]:
         """The "<kind>.<name>" a batch of ``bs`` rows needs for its re-render and has from nowhere: not in ``fx_params`` (which
-        may be None: a dry / wet pair of a recording) and neither learned nor fixed by ``learned_fx``."""
+        may be None: a dry / wet pair of a recording) and neither learned nor fixed by ``learned_fx`` / ``fx_head``."""
         from . import fx
         out = []
         for kind in dict.fromkeys(self._kinds[i % len(self._kinds)] for i in range(bs)):
             for name in fx.FX_PARAM_NAMES.get(kind, ()):
-                if (fx_params is None or name not in fx_params) and not (self.learned_fx is not None
-                                                                         and self.learned_fx.covers(kind, name)):
+                if (fx_params is None or name not in fx_params) and not (self._fxp is not None
+                                                                         and self._fxp.covers(kind, name)):
                     out.append(f"{kind}.{name}")
         return out
 
-    def _learned_constants(self, fx_params, bs: int, device) -> Dict[str, T]:
-        """``clip_constants`` of a step with ``learned_fx``.  Precedence per (kind, name): learned or fixed by ``learned_fx``
-        on the rows of that kind, else the batch's ``fx_params`` as in ``clip_constants`` (a ValueError names what neither has).
+    def _learned_constants(self, fx_params, bs: int, device, latent: Optional[T] = None) -> Dict[str, T]:
+        """``clip_constants`` of a step with ``learned_fx`` (or ``fx_head``: the same plan, but the one launch is
+        ``mx_fx_head_fwd`` on ``latent``, which is required then; it keeps the (B, P) values and ``_head_rows``).  Precedence
+        per (kind, name): learned or fixed by ``learned_fx`` on the rows of that kind, else the batch's ``fx_params`` as in
+        ``clip_constants`` (a ValueError names what neither has).
         The fixed numbers meet their row's sample count in double and are rounded once (the rule of a python float), per
         (B, device) once; the learned values are written over their rows by ``mx_fx_params_expand`` (fp64 map, rounded once,
         then the rule of a tensor parameter).  Without ``fx_params`` the vectors are the cached ones, rewritten in place on
         every step: no launch but the one.  Keeps the (P,) fp32 values for ``common_step`` to log."""
         from . import fx
-        lf = self.learned_fx
+        lf = self._fxp
         missing = self.missing_fx_params(fx_params, bs)
         if missing:
-            raise ValueError(f"the re-render needs {missing}: neither in the batch's fx_params nor learned / fixed by learned_fx")
+            raise ValueError(f"the re-render needs {missing}: neither in the batch's fx_params nor learned / fixed by "
+                             f"{self._fxp_name}")
+        if self.fx_head is not None:
+            if latent is None:
+                raise ValueError("a step with fx_head predicts the effect parameters from the model's latent: pass latent=")
+            latent = self._head_latent(latent, bs)
         m = self._mixed_rows(bs, device)
         lists, kinds = m["lists"], m["kinds"]
         if self.check_fx_params:                                    # what is still read from the batch, on the rows that read it
@@ -586,8 +650,22 @@ class LFOExtractionThroughEffect(BaseLightingModule):
             elif key in learned_slots and isinstance(p, T) and v.data_ptr() == p.data_ptr():
                 v = v.clone()                                       # the launch below writes: not into the batch's own tensor
             consts[key] = v.contiguous()
+        if self.fx_head is not None:
+            pooled, raw_rows, self._fx_values = lf.forward_rows(latent, consts, m["row_kind"], m["max_lfo_delay"],
+                                                                m["max_min_delay"])
+            self._head_rows = (pooled, raw_rows)
+            return consts
         self._fx_values = lf.expand(consts, m["row_kind"], m["max_lfo_delay"], m["max_min_delay"])
         return consts
+
+    def _head_latent(self, latent, bs: int) -> T:
+        """The latent as ``mx_fx_head_fwd`` reads it, or the ValueError that says what is wrong with it."""
+        if not (isinstance(latent, T) and latent.ndim == 3 and latent.size(0) == bs and latent.dtype == torch.float32):
+            raise ValueError(f"fx_head needs the model's latent as a ({bs}, in_ch, n_frames) fp32 tensor")
+        if latent.size(1) != self.fx_head.in_ch:
+            raise ValueError(f"the model's latent has {latent.size(1)} channels, fx_head was built for in_ch = "
+                             f"{self.fx_head.in_ch}")
+        return latent.detach().contiguous()
 
     def _render_rows(self, dry: T, mod: T, consts: Dict[str, T], stash: bool):
         """wet_hat (B, N), every family through its row list (``_launch_rows``) into the one buffer: flanger + chorus rows
@@ -632,7 +710,7 @@ class LFOExtractionThroughEffect(BaseLightingModule):
         def wanted(*kinds: str) -> Dict[str, T]:                    # slot name -> its row of gbuf, for the kinds' learned names
             if gbuf is None:
                 return {}
-            slots = {fx.FX_NAME_SLOT[n] for k in kinds for n in self.learned_fx.learned(k)}
+            slots = {fx.FX_NAME_SLOT[n] for k in kinds for n in self._fxp.learned(k)}
             return {s: gbuf[i] for i, s in enumerate(fx.FX_SLOTS) if s in slots}
 
         if m["delay"].numel():
@@ -656,17 +734,19 @@ class LFOExtractionThroughEffect(BaseLightingModule):
         assert audio.ndim == 3 and audio.size(1) == 1, "mono clips (B, 1, N)"
         return audio[:, 0, :]
 
-    def render(self, dry: T, mod_sig: T, fx_params) -> T:
+    def render(self, dry: T, mod_sig: T, fx_params, latent: Optional[T] = None) -> T:
         """wet_hat (B, 1, N) = the effect on ``dry`` (B, 1, N) driven by ``mod_sig`` (B, n_mod) at its own rate, with the
         per-clip constants of ``fx_params``; no graph and no stash kept (``_render_rows``: the data path's launches; the
-        phaser with lead 0, see the class docstring)."""
+        phaser with lead 0, see the class docstring).  ``latent``: required by a step with ``fx_head`` (a ValueError without
+        it), whose forward kernel alone runs then."""
         rows = self._rows(dry)
         with torch.no_grad():
-            consts = self.clip_constants(fx_params, rows.size(0), rows.device)
+            consts = self.clip_constants(fx_params, rows.size(0), rows.device, latent)
             y = self._render_rows(rows, mod_sig.detach().float().contiguous(), consts, stash=False)[0]
         return y.unsqueeze(1)
 
-    def audio_loss(self, mod_sig_hat: T, dry: T, wet: T, fx_params, prefix: Optional[str] = None):
+    def audio_loss(self, mod_sig_hat: T, dry: T, wet: T, fx_params, prefix: Optional[str] = None,
+                   latent: Optional[T] = None):
         """(loss, wet_hat (B, 1, N)) for an LFO (B, n_frames); with grad mode on and an LFO that requires grad the loss
         carries the graph of ``_EffectAudioLossFn``, otherwise nothing is stashed and no backward kernel runs.  ``prefix``:
         log every audio term under it."""
@@ -674,13 +754,24 @@ class LFOExtractionThroughEffect(BaseLightingModule):
         dry_r, wet_r = self._rows(dry), self._rows(wet)
         terms: Dict[str, T] = {}
         raw = None if self.learned_fx is None else self.learned_fx.raw
-        if torch.is_grad_enabled() and (mod_sig_hat.requires_grad or (raw is not None and raw.requires_grad)):
+        head = self.fx_head
+        if head is not None and latent is None:
+            raise ValueError("a step with fx_head predicts the effect parameters from the model's latent: pass latent=")
+        if head is not None and torch.is_grad_enabled() and (mod_sig_hat.requires_grad or latent.requires_grad or
+                                                             head.weight.requires_grad or head.bias.requires_grad):
+            with torch.no_grad():
+                consts = self.clip_constants(fx_params, dry_r.size(0), dry_r.device, latent)
+            loss, wet_hat = _EffectAudioLossFn.apply(mod_sig_hat, None, self, dry_r, wet_r, consts, terms, latent, head.weight,
+                                                     head.bias)
+            wet_hat = wet_hat.unsqueeze(1)
+        elif head is None and torch.is_grad_enabled() and (mod_sig_hat.requires_grad or
+                                                           (raw is not None and raw.requires_grad)):
             with torch.no_grad():
                 consts = self.clip_constants(fx_params, dry_r.size(0), dry_r.device)
             loss, wet_hat = _EffectAudioLossFn.apply(mod_sig_hat, raw, self, dry_r, wet_r, consts, terms)
             wet_hat = wet_hat.unsqueeze(1)
         else:
-            wet_hat, loss = self.render(dry, mod_sig_hat, fx_params), None
+            wet_hat, loss = self.render(dry, mod_sig_hat, fx_params, latent), None
         if prefix is not None or loss is None:
             with torch.no_grad():
                 missing = [k for k in self.audio_loss_dict if k not in terms]
@@ -702,8 +793,18 @@ class LFOExtractionThroughEffect(BaseLightingModule):
         assert dry is not None, "the re-render needs the dry clip"
         missing = self.missing_fx_params(fx_params, dry.size(0))
         if missing:
-            raise ValueError(f"the re-render needs {missing}: neither in the batch's fx_params nor learned / fixed by learned_fx")
-        mod_sig_hat, _ = self.model(stack_dry_wet(dry, wet) if self.use_dry else wet)
+            raise ValueError(f"the re-render needs {missing}: neither in the batch's fx_params nor learned / fixed by "
+                             f"{self._fxp_name}")
+        latent = None
+        if self.fx_head is None:
+            mod_sig_hat, _ = self.model(stack_dry_wet(dry, wet) if self.use_dry else wet)
+        else:
+            out = self.model(stack_dry_wet(dry, wet) if self.use_dry else wet)
+            if not (isinstance(out, (tuple, list)) and len(out) == 2 and isinstance(out[0], T) and isinstance(out[1], T)):
+                raise ValueError("fx_head needs a model whose forward returns the pair (lfo, latent), as "
+                                 "models.Spectral2DCNN does; this model returns no latent")
+            mod_sig_hat, latent = out
+            self._head_latent(latent, dry.size(0))                  # its ValueErrors, before any launch
         mod_sig_hat = mod_sig_hat.squeeze(1)
         if mod_sig is not None:
             mod_sig = linear_interpolate_last_dim(mod_sig, mod_sig_hat.size(-1), align_corners=True)
@@ -719,7 +820,7 @@ class LFOExtractionThroughEffect(BaseLightingModule):
             n_samples = int((n_frames / n_frames_in) * dry.size(-1))            # TBPTTLFOEffectModeling._prepare_all_rows
             dry = self.center_crop_mod_sig(dry, n_samples).contiguous()
             wet = self.center_crop_mod_sig(wet, n_samples).contiguous()
-        loss, wet_hat = self.audio_loss(mod_sig_hat, dry, wet, fx_params, prefix)
+        loss, wet_hat = self.audio_loss(mod_sig_hat, dry, wet, fx_params, prefix, latent)
         if self.lfo_loss_dict and mod_sig is not None:
             lfo_term = self.calc_and_log_losses(mod_sig_hat, mod_sig.contiguous(), self.lfo_loss_dict, f"{prefix}/lfo_",
                                                 log_total=False)
@@ -729,8 +830,17 @@ class LFOExtractionThroughEffect(BaseLightingModule):
         if is_training and self.learned_fx is not None:             # views of the launch's values vector: no host sync
             for i, name in enumerate(self.step_metric_names):
                 self.log(name, self._fx_values[i])
+        if is_training and self.fx_head is not None:                # a handful of (B, P) device operations: no host sync
+            m = self._mixed_rows(dry.size(0), dry.device)
+            mean = (self._fx_values * m["head_mask"]).sum(0) / m["head_count"]
+            std = ((((self._fx_values - mean) ** 2) * m["head_mask"]).sum(0) / m["head_count"]).sqrt()
+            for i, name in enumerate(self.fx_head.names):
+                self.log(f"fx/{name}", mean[i])
+                self.log(f"fx_std/{name}", std[i])
         data_dict = {"dry": dry.detach(), "wet": wet.detach(), "wet_hat": wet_hat.detach(),
                      "mod_sig_hat": mod_sig_hat.detach()}
+        if self.fx_head is not None:
+            data_dict["fx_values"] = self._fx_values
         if mod_sig is not None:
             data_dict["mod_sig"] = mod_sig.detach()
         return loss, data_dict, fx_params
