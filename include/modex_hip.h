@@ -818,4 +818,6 @@ int mx_fx_params_grad(const double *grads, const float *raw, const double *tab_f
 #endif
 /* K17, the per-clip effect-parameter head (csrc/fx_head.hip): two more entry points, declared in a file of their own */
 #include "modex_fx_head.h"
+/* K18, the LFO fit (csrc/lfo_fit.hip): one more entry point, declared in a file of its own for the same reason */
+#include "modex_lfo_fit.h"
 #endif /* MODEX_HIP_H */

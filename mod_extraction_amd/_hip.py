@@ -142,6 +142,11 @@ HEAD_SIGNATURES = {
     "mx_fx_head_bwd": [_P, _P, _P, _P, _P, _P, _I64, _F64, _P, _P, _P, _I64, _I64, _I64, _F64, _P, _P, _P, _P, _P],
 }
 
+# name -> argtypes of what include/modex_lfo_fit.h declares (K18, the LFO fit): again a table of its own beside its header
+FIT_SIGNATURES = {
+    "mx_lfo_fit": [_P, _I64, _I64, _I64, _F32, _F32, _F32, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P],
+}
+
 # measurement twins (same signatures): the dependent chain of the sample-recurrent kernels without global traffic
 PROBE_TWINS = ("mx_flanger_fwd", "mx_phaser_fwd", "mx_lstm_fwd", "mx_lstm_bwd_l1")
 for _name in PROBE_TWINS:
@@ -162,7 +167,7 @@ def load() -> ctypes.CDLL:
                 f"{SO_PATH} not found: build it with `python -m mod_extraction_amd.build` "
                 "(there is no CPU fallback)")
         lib = ctypes.CDLL(SO_PATH)
-        for name, argtypes in list(SIGNATURES.items()) + list(HEAD_SIGNATURES.items()):
+        for name, argtypes in list(SIGNATURES.items()) + list(HEAD_SIGNATURES.items()) + list(FIT_SIGNATURES.items()):
             fn = getattr(lib, name)          # AttributeError if the .so lacks a declared symbol
             fn.argtypes = argtypes
             fn.restype = ctypes.c_int

@@ -17,8 +17,8 @@ from torch import Tensor as T, nn
 
 from . import losses as L
 from .models import HiddenStateModel, RandomLFO
-from .modulations import (find_valid_mod_sig_indices, smoothen, smoothen_bwd, smoothen_with_grad, stretch_corners, stretch_corners_bwd,
-                          valid_mod_sig_mask)
+from .modulations import (LFO_SHAPES, LFOFit, find_valid_mod_sig_indices, fit_lfo, fit_rate_window, fit_shape_mask, smoothen, smoothen_bwd,
+                          smoothen_with_grad, stretch_corners, stretch_corners_bwd, valid_mod_sig_mask)
 from .util import linear_interpolate_last_dim, linear_interpolate_last_dim_bwd
 
 log = logging.getLogger(__name__)
@@ -129,7 +129,15 @@ class LFOExtraction(BaseLightingModule):
                  max_n_corners: int = 16,
                  stretch_smooth_n_frames: int = 0,
                  sub_batch_size: Optional[int] = None,
-                 loss_dict: Optional[Dict[str, float]] = None) -> None:
+                 loss_dict: Optional[Dict[str, float]] = None,
+                 fit_metrics: Optional[Dict[str, object]] = None) -> None:
+        """``fit_metrics`` (e.g. ``{rate_hz: [0.25, 8.0]}``, optionally ``shapes``, ``rate_div``, ``n_phases``, ``n_rounds``):
+        validation steps also fit rate, phase and shape (``modulations.fit_lfo``) to the prediction and to the label, in one
+        launch on the stacked 2 B rows, log ``val/fit_*`` (``FIT_METRIC_NAMES``) as device scalars and put the prediction's
+        ``LFOFit`` into ``data_dict["lfo_fit"]``.  The prediction is compared with the FIT OF THE LABEL, not with
+        ``fx_params``: phaser rows, quasi-periodic / combined labels and the crop under ``model_smooth_n_frames`` need no special
+        case, and ``val/fit_label_resid`` shows when the label itself is no plain periodic LFO.  Training steps never fit;
+        without the argument nothing changes."""
         super().__init__(loss_dict)
         self.model = model
         self.sr = sr
@@ -139,6 +147,45 @@ class LFOExtraction(BaseLightingModule):
         self.max_n_corners = max_n_corners
         self.stretch_smooth_n_frames = stretch_smooth_n_frames
         self.sub_batch_size = sub_batch_size
+        self.fit_metrics = self._check_fit_metrics(fit_metrics)
+        self.val_metric_names = [f"val/{k}" for k in self.FIT_METRIC_NAMES] if self.fit_metrics is not None else []
+
+    FIT_METRIC_NAMES = ("fit_rate_err_hz", "fit_rate_err_rel", "fit_shape_acc", "fit_resid", "fit_label_resid")
+
+    @staticmethod
+    def _check_fit_metrics(spec) -> Optional[Dict[str, object]]:
+        """The keyword arguments of ``fit_lfo`` a ``fit_metrics`` dict stands for, checked at construction (ValueError)."""
+        if spec is None:
+            return None
+        if not isinstance(spec, dict) or "rate_hz" not in spec:
+            raise ValueError(f"fit_metrics must be a dict with the key rate_hz: [min, max], got {spec!r}")
+        unknown = sorted(set(spec) - {"rate_hz", "shapes", "rate_div", "n_phases", "n_rounds"})
+        if unknown:
+            raise ValueError(f"fit_metrics: unknown keys {unknown} (known: rate_hz, shapes, rate_div, n_phases, n_rounds)")
+        kw: Dict[str, object] = {"rate_hz": fit_rate_window(spec["rate_hz"], float("inf")),
+                                 "shapes": list(spec.get("shapes", LFO_SHAPES))}
+        fit_shape_mask(kw["shapes"])
+        for key, lo, hi in (("rate_div", 1, 16), ("n_phases", 4, 128), ("n_rounds", 0, 8)):
+            if key in spec:
+                v = spec[key]
+                if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:
+                    raise ValueError(f"fit_metrics: {key} must be an integer in [{lo}, {hi}], got {v!r}")
+                kw[key] = v
+        return kw
+
+    def _fit_and_log(self, mod_sig_hat: T, mod_sig: T, lfo_sr: float):
+        """One ``mx_lfo_fit`` launch on [prediction; label]; logs the five ``val/fit_*`` scalars (no host sync) and returns the
+        prediction's ``LFOFit``."""
+        bs = mod_sig_hat.size(0)
+        both = fit_lfo(torch.cat([mod_sig_hat.detach().float(), mod_sig.detach().float()], dim=0), lfo_sr, **self.fit_metrics)
+        hat, lab = LFOFit(*[v[:bs] for v in both[:6]]), LFOFit(*[v[bs:] for v in both[:6]])
+        err = (hat.rate_hz - lab.rate_hz).abs()
+        self.log("val/fit_rate_err_hz", err.mean())
+        self.log("val/fit_rate_err_rel", (err / lab.rate_hz).mean())
+        self.log("val/fit_shape_acc", (hat.shape == lab.shape).float().mean())
+        self.log("val/fit_resid", hat.resid.mean())
+        self.log("val/fit_label_resid", lab.resid.mean())
+        return hat
 
     def common_step(self, batch, is_training: bool):
         """lightning.py:96-158."""
@@ -152,6 +199,7 @@ class LFOExtraction(BaseLightingModule):
         else:
             mod_sig_hat, _ = self.model(wet)
         mod_sig_hat = mod_sig_hat.squeeze(1)
+        lfo_sr = mod_sig_hat.size(-1) * float(self.sr) / wet.size(-1)       # the rate of the LFO's points (before any crop)
         if mod_sig is None:
             mod_sig = torch.zeros_like(mod_sig_hat)
         else:
@@ -173,6 +221,8 @@ class LFOExtraction(BaseLightingModule):
         data_dict = {"wet": wet.detach(), "mod_sig": mod_sig.detach(), "mod_sig_hat": mod_sig_hat.detach()}
         if dry is not None:
             data_dict["dry"] = dry.detach()
+        if self.fit_metrics is not None and not is_training:
+            data_dict["lfo_fit"] = self._fit_and_log(mod_sig_hat, mod_sig, lfo_sr)
         return loss, data_dict, fx_params
 
     def sub_batch_size_common_step(self, batch, is_training: bool):

@@ -5,7 +5,7 @@ kernel; ``make_mod_signals`` is the batched form the training loop uses (one lau
 batch, optional crop offset and on-the-fly resampling).
 """
 import math
-from typing import List, Optional, Sequence, Union
+from typing import List, NamedTuple, Optional, Sequence, Tuple, Union
 
 import torch
 from torch import Tensor as T
@@ -350,3 +350,89 @@ def make_combined_mod_sigs(n_samples: int, sr: float, freq: T, phase: T, shape_t
     _hip.call("mx_lfo_combined", _hip.ptr(freq), _hip.ptr(phase), _hip.ptr(tab), B, n_samples, tab.size(1) - 1, float(sr),
               _hip.ptr(out), _hip.ptr(n_corners), _hip.stream())
     return out, n_corners
+
+
+# ---- K18: the inverse of ``make_mod_signals`` (csrc/lfo_fit.hip) ---------------------------------
+LFO_SHAPES = ("cos", "rect_cos", "inv_rect_cos", "tri", "saw", "rsaw")       # the default set of the fit: all but "sqr"
+SHAPE_NAMES = tuple(sorted(SHAPE_IDS, key=SHAPE_IDS.get))
+
+
+class LFOFit(NamedTuple):
+    """What ``fit_lfo`` returns: (B,) device tensors, ``shape`` int32 (ids of ``SHAPE_IDS``), the rest fp32;
+    ``per_shape_resid`` (B, 7) fp32 (+inf where a shape was not allowed) or None.  ``offset + amp * make_mod_signals(n, sr,
+    rate_hz, phase, shape)`` is the fitted template (``synth_from_fit``); ``resid`` is its squared error over the row's
+    centred energy."""
+    shape: T
+    rate_hz: T
+    phase: T
+    amp: T
+    offset: T
+    resid: T
+    per_shape_resid: Optional[T] = None
+
+    def shape_names(self) -> List[str]:
+        """The fitted shapes by name (copies ``shape`` to the host: a sync)."""
+        return [SHAPE_NAMES[i] for i in self.shape.tolist()]
+
+
+def fit_shape_mask(shapes: Sequence[str]) -> int:
+    """Bit mask over ``SHAPE_IDS`` of a non-empty list of shape names (ValueError otherwise)."""
+    if isinstance(shapes, str) or len(shapes) == 0:
+        raise ValueError(f"fit_lfo: shapes must be a non-empty list of names from {list(SHAPE_IDS)}, got {shapes!r}")
+    mask = 0
+    for s in shapes:
+        if s not in SHAPE_IDS:
+            raise ValueError(f"fit_lfo: unknown LFO shape {s!r} (known: {list(SHAPE_IDS)})")
+        mask |= 1 << SHAPE_IDS[s]
+    return mask
+
+
+def fit_rate_window(rate_hz, sr: float) -> Tuple[float, float]:
+    """(f_min, f_max) of a two-element rate window with 0 < f_min <= f_max < sr / 2 (ValueError otherwise)."""
+    try:
+        f_min, f_max = (float(v) for v in rate_hz)
+    except (TypeError, ValueError):
+        raise ValueError(f"fit_lfo: rate_hz must be a (min, max) pair in Hz, got {rate_hz!r}") from None
+    if not (sr > 0.0 and 0.0 < f_min <= f_max < sr / 2.0):
+        raise ValueError(f"fit_lfo: need 0 < rate_hz[0] <= rate_hz[1] < sr / 2, got {rate_hz!r} at sr = {sr}")
+    return f_min, f_max
+
+
+def fit_lfo(mod_sig: T, sr: float, rate_hz=(0.25, 8.0), shapes: Sequence[str] = LFO_SHAPES, rate_div: int = 4,
+            n_phases: int = 32, n_rounds: int = 4, per_shape: bool = False) -> LFOFit:
+    """Rate, phase and shape of every row of ``mod_sig`` ((B, n) or (n,), fp32, on the device; ``sr`` the rate of its
+    points, 172.5 for 345 points of a 2 s clip) in one ``mx_lfo_fit`` launch: a grid search over the rate window ``rate_hz``
+    (spacing ``sr / (rate_div n)``) and ``n_phases`` centre phases, ``n_rounds`` rounds of 5 x 5 refinement, per allowed shape,
+    with a non-negative amplitude and a free offset (include/modex_lfo_fit.h has the definition).  Rows a row stride apart
+    (inner stride 1) are read in place."""
+    mask = fit_shape_mask(shapes)
+    f_min, f_max = fit_rate_window(rate_hz, float(sr))
+    if not isinstance(mod_sig, torch.Tensor) or mod_sig.ndim not in (1, 2) or mod_sig.dtype != torch.float32:
+        raise ValueError("fit_lfo: mod_sig must be an fp32 tensor of shape (B, n) or (n,)")
+    if not mod_sig.is_cuda:
+        raise ValueError("fit_lfo: mod_sig must be on a HIP device (there is no CPU fallback)")
+    m = mod_sig.detach()
+    m = m.unsqueeze(0) if m.ndim == 1 else m
+    B, n = m.shape
+    if B == 0:
+        raise ValueError("fit_lfo: mod_sig has no rows")
+    if m.stride(1) != 1 or (B > 1 and m.stride(0) < n):
+        m = m.contiguous()
+    stride = max(m.stride(0), n) if B > 1 else n
+    dev = m.device
+    out = [torch.empty(B, device=dev, dtype=torch.int32)] + [torch.empty(B, device=dev, dtype=torch.float32) for _ in range(5)]
+    table = torch.empty((B, 7), device=dev, dtype=torch.float32) if per_shape else None
+    _hip.call("mx_lfo_fit", m.data_ptr(), stride, B, n, float(sr), f_min, f_max, mask, int(rate_div), int(n_phases),
+              int(n_rounds), *[_hip.ptr(o) for o in out], _hip.ptr(table), _hip.stream())
+    return LFOFit(*out, table)
+
+
+def synth_from_fit(fit: LFOFit, n_samples: int, sr: float, start: Union[None, int, T] = None,
+                   n_out: Optional[int] = None) -> T:
+    """``offset + amp * make_mod_signals(n_samples, sr, rate_hz, phase, shape, start=start, n_out=n_out)``: (B, n_out or
+    n_samples).  With the ``n_samples`` and ``sr`` of the fitted rows this is the fitted template; ``start`` (an int, or a
+    (B,) int32 tensor) continues it beyond the clip: ``start = n`` gives the next ``n_samples`` points."""
+    if isinstance(start, int):
+        start = torch.full_like(fit.shape, start)
+    sig = make_mod_signals(n_samples, sr, fit.rate_hz, fit.phase, fit.shape, start=start, n_out=n_out)
+    return fit.offset.unsqueeze(1) + fit.amp.unsqueeze(1) * sig

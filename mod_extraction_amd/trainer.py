@@ -118,8 +118,9 @@ def reduce_metrics(logged: Dict[str, List[torch.Tensor]], world_size: int,
 
 def metric_names(module, prefix: str) -> List[str]:
     """The scalars a BaseLightingModule logs per step under ``prefix`` (lightning.py:33-62); a training step may log more
-    under names of its own (``step_metric_names``: the learned effect parameters, ``fx/<kind>.<name>``)."""
-    extra = list(getattr(module, "step_metric_names", ())) if prefix == "train" else []
+    under names of its own (``step_metric_names``: the learned effect parameters, ``fx/<kind>.<name>``), a validation step
+    under ``val_metric_names`` (the LFO fit metrics, ``val/fit_*``)."""
+    extra = list(getattr(module, "step_metric_names" if prefix == "train" else "val_metric_names", ()))
     return [f"{prefix}/{k}" for k in getattr(module, "loss_dict", {})] + [f"{prefix}/loss"] + extra
 
 
