@@ -251,47 +251,40 @@ class LFOExtraction(BaseLightingModule):
 
 class _EffectAudioLossFn(torch.autograd.Function):
     """loss = sum_k w_k loss_k(effect(dry, mod_sig_hat), wet) as ONE autograd node for every ``effect``: ``forward(ctx,
-    mod_sig_hat, raw, step, dry, wet, consts, terms)`` returns (loss, wet_hat (B, N)) and fills ``terms`` with the unweighted
-    value of every weighted loss.  Every family renders its rows into one wet_hat (``step._render_rows``), the
+    mod_sig_hat, step, dry, wet, consts, terms, *params)`` returns (loss, wet_hat (B, N)) and fills ``terms`` with the
+    unweighted value of every weighted loss.  Every family renders its rows into one wet_hat (``step._render_rows``), the
     value-and-gradient kernels of the weighted losses run once (``effect_loss_grad``), and every family's adjoint writes its
-    rows of one (B, n_frames) gradient at once (``step._adjoint_rows``).  Only that gradient is kept for the backward, which
-    scales it; d loss / d wet_hat, the stashes (allocated for all B rows) and the adjoints' workspaces do not outlive the
-    call."""
+    rows of one (B, n_frames) gradient at once (``step._adjoint_rows``).  Only that gradient (and those of ``params``) is
+    kept for the backward, which scales it; d loss / d wet_hat, the stashes (allocated for all B rows) and the adjoints'
+    workspaces do not outlive the call."""
 
     @staticmethod
-    def forward(ctx, mod_sig_hat, raw, step, dry, wet, consts, terms, latent=None, weight=None, bias=None):
-        """``raw``: ``step.learned_fx.raw`` (the second differentiable input; ``consts`` already hold its mapped values) or
-        None.  With it every family's adjoint is also asked for the per-clip fp64 gradients of its learned slots, rows of one
-        (6, B) buffer, which ``mx_fx_params_grad`` reduces to d loss / d raw; without it the launches are those of the step
-        without learned parameters.  ``latent``, ``weight``, ``bias`` (a step with ``fx_head``; ``consts`` already hold the
-        predicted values, ``step._head_rows`` what the forward launch kept): three more differentiable inputs, whose gradients
-        ``mx_fx_head_bwd`` forms from the same (6, B) buffer."""
+    def forward(ctx, mod_sig_hat, step, dry, wet, consts, terms, *params):
+        """``params``: the differentiable inputs beside the LFO, whose values ``consts`` already hold -- ``()``; ``(raw,)`` of
+        ``step.learned_fx``; ``(latent, weight, bias)`` of ``step.fx_head`` (``step._head_rows``: what its forward launch kept).
+        With them every family's adjoint is also asked for the per-clip fp64 gradients of its learned slots, rows of one
+        (6, B) buffer, which ``mx_fx_params_grad`` reduces to d loss / d raw or ``mx_fx_head_bwd`` to the gradients of the
+        three; without them the launches are those of the step without learned parameters."""
         from .effect_losses import effect_loss_grad, effect_loss_terms
         mod = mod_sig_hat.detach().float().contiguous()
         wet_hat, stashes = step._render_rows(dry, mod, consts, stash=True)
         a, t = wet_hat.unsqueeze(1), wet.unsqueeze(1)
         weighted: Dict[str, T] = {}
         dy = effect_loss_grad(a, t, step.audio_loss_dict, values=weighted, **step._grad_modules())
-        ctx.head = latent is not None
-        if ctx.head:
+        # the adjoints write (they do not add) the rows of their family, and the reduction reads only those: no zeros
+        gbuf = torch.empty((6, dry.size(0)), device=dry.device, dtype=torch.float64) if params else None
+        dmod = step._adjoint_rows(dy, dry, mod, consts, stashes, gbuf=gbuf)
+        param_grads: Tuple[Optional[T], ...] = ()
+        if params:
             m = step._mixed_rows(dry.size(0), dry.device)
-            gbuf = torch.empty((6, dry.size(0)), device=dry.device, dtype=torch.float64)
-            dmod = step._adjoint_rows(dy, dry, mod, consts, stashes, gbuf=gbuf)
-            pooled, raw_rows = step._head_rows
-            d_bias, d_weight, d_latent = step.fx_head.backward_rows(
-                gbuf, raw_rows, pooled, m["row_kind"], m["max_lfo_delay"], m["max_min_delay"], latent.size(-1),
-                need_d_latent=latent.requires_grad)
-            ctx.save_for_backward(dmod, d_latent, d_weight, d_bias)
-        elif raw is None:
-            dmod = step._adjoint_rows(dy, dry, mod, consts, stashes)
-            ctx.save_for_backward(dmod)
-        else:
-            m = step._mixed_rows(dry.size(0), dry.device)
-            # the adjoints write (they do not add) the rows of their family, and the reduction reads only those: no zeros
-            gbuf = torch.empty((6, dry.size(0)), device=dry.device, dtype=torch.float64)
-            dmod = step._adjoint_rows(dy, dry, mod, consts, stashes, gbuf=gbuf)
-            d_raw = step.learned_fx.grad(gbuf, m["row_kind"], m["max_lfo_delay"], m["max_min_delay"])
-            ctx.save_for_backward(dmod, d_raw)
+            geometry = (m["row_kind"], m["max_lfo_delay"], m["max_min_delay"])
+            if step.fx_head is None:
+                param_grads = (step.learned_fx.grad(gbuf, *geometry),)
+            else:                               # (d_bias, d_weight, d_latent), reversed into the order of ``params``
+                latent, (pooled, raw_rows) = params[0], step._head_rows
+                param_grads = step.fx_head.backward_rows(gbuf, raw_rows, pooled, *geometry, latent.size(-1),
+                                                         need_d_latent=latent.requires_grad)[::-1]
+        ctx.save_for_backward(dmod, *param_grads)
         w = {k: v for k, v in step.audio_loss_dict.items() if v > 0}
         terms.update({k: v / w[k] for k, v in weighted.items()})
         if any(k in w for k in ("l1", "mse", "esr", "dc")):
@@ -301,13 +294,10 @@ class _EffectAudioLossFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g, _g_wet_hat):
-        dmod = ctx.saved_tensors[0]
-        if ctx.head:
-            need = ctx.needs_input_grad
-            head = tuple(t * g if t is not None and n else None for t, n in zip(ctx.saved_tensors[1:], need[7:10]))
-            return (dmod * g if need[0] else None, None, None, None, None, None, None) + head
-        d_raw = ctx.saved_tensors[1] * g if len(ctx.saved_tensors) > 1 and ctx.needs_input_grad[1] else None
-        return (dmod * g if ctx.needs_input_grad[0] else None), d_raw, None, None, None, None, None
+        need = ctx.needs_input_grad               # of (mod_sig_hat, step, dry, wet, consts, terms, *params)
+        dmod, *param_grads = ctx.saved_tensors
+        d_params = tuple(t * g if t is not None and n else None for t, n in zip(param_grads, need[6:]))
+        return (dmod * g if need[0] else None, None, None, None, None, None) + d_params
 
 
 EFFECTS = ("flanger", "tremolo", "phaser")              # what a string ``effect`` may name
@@ -323,6 +313,19 @@ def mixed_row_lists(kinds: Sequence[str], bs: int) -> Dict[str, List[int]]:
     for i in range(bs):
         out[family[kinds[i % len(kinds)]]].append(i)
     return out
+
+
+# The per-row constants of the effect launches (the keys of fx.FX_CONSTS), in the order of the dict ``clip_constants`` returns:
+# (key, the ``fx_params`` name it comes from, the launch families whose rows read it, its transform).  A key is present iff
+# one of its families has a row.  Transform: None = the value itself, "1-" = 1 - v, else the per-row sample count of
+# ``_mixed_rows`` the value is multiplied by.
+CLIP_CONSTS = (("mix", "mix", ("delay", "tremolo", "phaser"), None),
+               ("one_minus_mix", "mix", ("delay", "tremolo"), "1-"),
+               ("feedback", "feedback", ("delay", "phaser"), None),
+               ("depth", "depth", ("delay", "phaser"), None),
+               ("lfo_scale", "width", ("delay",), "max_lfo_delay"),
+               ("min_delay", "min_delay_width", ("delay",), "max_min_delay"),
+               ("centre_frequency_hz", "centre_frequency_hz", ("phaser",), None))
 
 
 class LFOExtractionThroughEffect(BaseLightingModule):
@@ -439,18 +442,10 @@ class LFOExtractionThroughEffect(BaseLightingModule):
                 raise NotImplementedError(f"audio loss '{name}' has no gradient kernel (supported: {GRAD_NAMES})")
         if not any(w > 0 for w in audio_loss_dict.values()):
             raise ValueError("audio_loss_dict needs at least one loss with a weight above 0")
-        has_flanger = "flanger" in self._kinds
-        if has_flanger:
-            if max_min_delay_ms < 0 or max_lfo_delay_ms < 0:
-                raise ValueError("max_min_delay_ms and max_lfo_delay_ms must not be negative")
-            self.max_min_delay_samples = fx.delay_samples(max_min_delay_ms, sr)
-            self.max_lfo_delay_samples = fx.delay_samples(max_lfo_delay_ms, sr)
-        else:                                                       # no delay line: the arguments are ignored
-            self.max_min_delay_samples = self.max_lfo_delay_samples = 0
+        self.max_min_delay_samples = self.max_lfo_delay_samples = 0   # no delay line: the arguments are ignored
+        if "flanger" in self._kinds:
+            self.max_min_delay_samples, self.max_lfo_delay_samples = self._delay_line(max_min_delay_ms, max_lfo_delay_ms, sr, "")
         self.max_delay_samples = self.max_min_delay_samples + self.max_lfo_delay_samples
-        if has_flanger and not 2 <= self.max_delay_samples <= fx.FLANGER_MAX_DELAY_SAMPLES:
-            raise ValueError(f"delay line of {self.max_delay_samples} samples: the flanger kernels keep it in LDS and support "
-                             f"2 .. {fx.FLANGER_MAX_DELAY_SAMPLES} samples (LFO row included)")
         if self.kinds is not None:
             from .data_modules import CHORUS_FX
             if chorus_max_min_delay_ms is None:
@@ -460,14 +455,8 @@ class LFOExtractionThroughEffect(BaseLightingModule):
             self.chorus_max_min_delay_ms, self.chorus_max_lfo_delay_ms = chorus_max_min_delay_ms, chorus_max_lfo_delay_ms
             self.chorus_max_min_delay_samples = self.chorus_max_lfo_delay_samples = 0
             if "chorus" in self.kinds:
-                if chorus_max_min_delay_ms < 0 or chorus_max_lfo_delay_ms < 0:
-                    raise ValueError("chorus_max_min_delay_ms and chorus_max_lfo_delay_ms must not be negative")
-                self.chorus_max_min_delay_samples = fx.delay_samples(chorus_max_min_delay_ms, sr)
-                self.chorus_max_lfo_delay_samples = fx.delay_samples(chorus_max_lfo_delay_ms, sr)
-                m = self.chorus_max_min_delay_samples + self.chorus_max_lfo_delay_samples
-                if not 2 <= m <= fx.FLANGER_MAX_DELAY_SAMPLES:
-                    raise ValueError(f"chorus delay line of {m} samples: the flanger kernels keep it in LDS and support "
-                                     f"2 .. {fx.FLANGER_MAX_DELAY_SAMPLES} samples (LFO row included)")
+                self.chorus_max_min_delay_samples, self.chorus_max_lfo_delay_samples = self._delay_line(
+                    chorus_max_min_delay_ms, chorus_max_lfo_delay_ms, sr, "chorus_")
         self.model = model
         self.sr, self.use_dry = sr, use_dry
         self.model_smooth_n_frames = model_smooth_n_frames
@@ -478,28 +467,11 @@ class LFOExtractionThroughEffect(BaseLightingModule):
         self.lfo_loss_dict = self.loss_dict
         self.loss_dict = dict(audio_loss_dict, **{f"lfo_{k}": w for k, w in self.lfo_loss_dict.items()})
         self._mixed = None
-        if isinstance(learned_fx, dict):
-            learned_fx = fx.LearnedFxParams(learned_fx)
-        if learned_fx is not None:
-            if not isinstance(learned_fx, fx.LearnedFxParams):
-                raise ValueError("learned_fx: a spec dict or an fx.LearnedFxParams")
-            for k in learned_fx.kinds:
-                if k not in self._kinds:
-                    raise ValueError(f"learned_fx names the kind '{k}', which is not among this step's kinds {self._kinds}")
+        learned_fx = self._param_source(learned_fx, "learned_fx", fx.LearnedFxParams)
         self.learned_fx = learned_fx                                # None registers nothing: the parameters are the model's
         if fx_head is not None and learned_fx is not None:
             raise ValueError("learned_fx and fx_head are mutually exclusive: shared and per-clip entries do not mix")
-        if isinstance(fx_head, dict):
-            spec = dict(fx_head)
-            extra = {k: spec.pop(k) for k in ("in_ch", "raw_gain") if k in spec}
-            fx_head = fx.FxParamHead(spec, **extra)
-        if fx_head is not None:
-            if not isinstance(fx_head, fx.FxParamHead):
-                raise ValueError("fx_head: a spec dict or an fx.FxParamHead")
-            for k in fx_head.kinds:
-                if k not in self._kinds:
-                    raise ValueError(f"fx_head names the kind '{k}', which is not among this step's kinds {self._kinds}")
-        self.fx_head = fx_head                                      # likewise
+        self.fx_head = fx_head = self._param_source(fx_head, "fx_head", fx.FxParamHead, ("in_ch", "raw_gain"))     # likewise
         self._fixed_plan = None
         self._fx_values: Optional[T] = None
         self._head_rows: Optional[Tuple[T, T]] = None               # (pooled, raw_rows) of the last mx_fx_head_fwd
@@ -513,9 +485,33 @@ class LFOExtractionThroughEffect(BaseLightingModule):
         """Who supplies learned / fixed effect parameters: ``learned_fx``, ``fx_head`` or None."""
         return self.learned_fx if self.learned_fx is not None else self.fx_head
 
-    @property
-    def _fxp_name(self) -> str:
-        return "fx_head" if self.fx_head is not None else "learned_fx"
+    @staticmethod
+    def _delay_line(max_min_delay_ms: float, max_lfo_delay_ms: float, sr: float, prefix: str) -> Tuple[int, int]:
+        """The two sample counts of the delay-line geometry ``{prefix}max_min_delay_ms`` / ``{prefix}max_lfo_delay_ms``
+        (``prefix``: "" for the flanger rows, "chorus_" for the chorus rows), or the ValueError that says what is wrong."""
+        from . import fx
+        if max_min_delay_ms < 0 or max_lfo_delay_ms < 0:
+            raise ValueError(f"{prefix}max_min_delay_ms and {prefix}max_lfo_delay_ms must not be negative")
+        n_min, n_lfo = fx.delay_samples(max_min_delay_ms, sr), fx.delay_samples(max_lfo_delay_ms, sr)
+        if not 2 <= n_min + n_lfo <= fx.FLANGER_MAX_DELAY_SAMPLES:
+            raise ValueError(f"{prefix.replace('_', ' ')}delay line of {n_min + n_lfo} samples: the flanger kernels keep it in LDS "
+                             f"and support 2 .. {fx.FLANGER_MAX_DELAY_SAMPLES} samples (LFO row included)")
+        return n_min, n_lfo
+
+    def _param_source(self, arg, what: str, cls, own_keys: Sequence[str] = ()):
+        """The ``learned_fx`` / ``fx_head`` argument (``what``) as its ``cls`` object: built from a spec dict (``own_keys``: the
+        constructor's keywords that sit beside the kinds), type-checked, and naming none but this step's kinds.  None stays."""
+        if isinstance(arg, dict):
+            spec = dict(arg)
+            own = {k: spec.pop(k) for k in own_keys if k in spec}
+            arg = cls(spec, **own)
+        if arg is not None:
+            if not isinstance(arg, cls):
+                raise ValueError(f"{what}: a spec dict or an fx.{cls.__name__}")
+            for k in arg.kinds:
+                if k not in self._kinds:
+                    raise ValueError(f"{what} names the kind '{k}', which is not among this step's kinds {self._kinds}")
+        return arg
 
     def _mixed_rows(self, bs: int, device) -> Dict[str, object]:
         """The row plan of a batch of ``bs`` rows on ``device`` (cached): the int32 row list of every launch family, the
@@ -558,56 +554,93 @@ class LFOExtractionThroughEffect(BaseLightingModule):
         return None if m["all_rows"] == family else m[family]
 
     def clip_constants(self, fx_params, bs: int, device, latent: Optional[T] = None) -> Dict[str, T]:
-        """ONE dict of (B,) fp32 constants for all families of the batch, each formed as the data path forms it
-        (``SyntheticFxBatcher.render``, ``fx.derive_clip_constants``): a tensor parameter meets the per-row sample count in
-        fp32 and one_minus_mix is 1 - mix in fp32; a python float meets them in double and is rounded once.  So a re-render
-        from the label reproduces ``wet``.  Only what the kinds present need is read from ``fx_params``.  ``latent`` (B, in_ch,
-        W): what a step with ``fx_head`` predicts from."""
+        """ONE dict of (B,) fp32 constants for all families of the batch: the keys of ``CLIP_CONSTS`` whose families have a
+        row, in its order, read from ``fx_params`` or supplied by ``learned_fx`` / ``fx_head`` (precedence: the class docstring).
+        The rounding rule is the data path's (``SyntheticFxBatcher.render``, ``fx.derive_clip_constants``), so a re-render from
+        the label reproduces ``wet``: a tensor parameter meets the per-row sample count in fp32 and one_minus_mix is 1 - mix in
+        fp32; a python float, and a number fixed by ``learned_fx`` / ``fx_head``, meets them in double and is rounded once; a
+        learned or predicted value is mapped in fp64, rounded once and then follows the rule of a tensor parameter
+        (``mx_fx_params_expand`` / ``mx_fx_head_fwd``, the one launch).  Only what the kinds present need is read from
+        ``fx_params``; a ValueError names what nobody supplies.
+        With ``learned_fx`` / ``fx_head`` the fixed numbers (``_fixed_vectors``) lie over the batch's vectors on the rows of their
+        kind, the launch writes the learned values over the rows of theirs, and its (P,) / (B, P) fp32 values are kept for
+        ``common_step`` to log (``fx_head``: also ``_head_rows``).  Without ``fx_params`` the vectors are the cached ones,
+        rewritten in place on every step: no launch but the one.  ``latent`` (B, in_ch, W): what a step with ``fx_head``
+        predicts from, required then."""
         from . import fx
-        if self._fxp is not None:
-            return self._learned_constants(fx_params, bs, device, latent)
-        missing = self.missing_fx_params(fx_params, bs)
-        if missing:
-            raise ValueError(f"fx_params lacks {missing}: the re-render needs them from the batch, or learned / fixed through "
-                             f"learned_fx")
+        src = self._fxp
+        self._require_fx_params(fx_params, bs)
+        if self.fx_head is not None:
+            if latent is None:
+                raise ValueError("a step with fx_head predicts the effect parameters from the model's latent: pass latent=")
+            latent = self._head_latent(latent, bs)
         m = self._mixed_rows(bs, device)
-        lists = m["lists"]
+        if self.check_fx_params:                                    # what is read from the batch, each kind's ranges on its own rows
+            kinds = [self._kinds[i % len(self._kinds)] for i in range(bs)]
+            for kind in dict.fromkeys(kinds):
+                rows = [i for i in range(bs) if kinds[i] == kind]
+                for name in fx.FX_PARAM_NAMES.get(kind, ()):
+                    if src is None or not src.covers(kind, name):
+                        p = fx_params[name]
+                        fx._check_range(p[rows] if isinstance(p, T) and len(rows) < bs else p, len(rows),
+                                        *fx._fx_param_range(kind, name))
+        plan = None if src is None else self._fixed_vectors(m)
 
-        def vec(name: str, f=lambda v: v) -> T:
-            p = fx_params[name]
+        def transformed(v: T, how: Optional[str]) -> T:
+            return v if how is None else 1.0 - v if how == "1-" else v * m[how]
+
+        consts = {}
+        for key, name, families, how in CLIP_CONSTS:
+            if not any(m["lists"][f] for f in families):
+                continue
+            p = None if fx_params is None else fx_params.get(name)
+            if p is None:                                           # learned / fixed on every row that reads it
+                consts[key] = plan["vals"][key]
+                continue
             if isinstance(p, T):
                 assert p.shape == (bs,), f"fx_params['{name}']: a ({bs},) tensor or a python float"
-                return f(p.to(device=device, dtype=torch.float32)).contiguous()
-            return f(torch.full((bs,), float(p), device=device, dtype=torch.float64)).float()
-
-        def on(name: str, fam: str) -> fx.Param:                    # a family's rows of a parameter (all rows, a float: as is)
-            p = fx_params[name]
-            return vec(name)[m[fam].long()] if isinstance(p, T) and m["all_rows"] != fam else p
-
-        if self.check_fx_params:                                    # each family's ranges on its own rows
-            n = {f: len(lists[f]) for f in lists}
-            if n["delay"]:
-                fx._check_param(on("feedback", "delay"), n["delay"], can_be_one=False)
-                for name in ("min_delay_width", "width", "depth", "mix"):
-                    fx._check_param(on(name, "delay"), n["delay"])
-            if n["tremolo"]:
-                fx._check_param(on("mix", "tremolo"), n["tremolo"])
-            if n["phaser"]:
-                fx.derive_phaser_params(n["phaser"], device, on("depth", "phaser"), on("centre_frequency_hz", "phaser"),
-                                        on("feedback", "phaser"), on("mix", "phaser"), check=True)
-        consts = {}
-        if lists["delay"] or lists["tremolo"] or lists["phaser"]:
-            consts["mix"] = vec("mix")
-        if lists["delay"] or lists["tremolo"]:
-            consts["one_minus_mix"] = vec("mix", lambda v: 1.0 - v)
-        if lists["delay"] or lists["phaser"]:
-            consts["feedback"], consts["depth"] = vec("feedback"), vec("depth")
-        if lists["delay"]:
-            consts["lfo_scale"] = vec("width", lambda v: v * m["max_lfo_delay"])
-            consts["min_delay"] = vec("min_delay_width", lambda v: v * m["max_min_delay"])
-        if lists["phaser"]:
-            consts["centre_frequency_hz"] = vec("centre_frequency_hz")
+                v = transformed(p.to(device=device, dtype=torch.float32), how)
+            else:
+                v = transformed(torch.full((bs,), float(p), device=device, dtype=torch.float64), how).float()
+            if plan is not None:
+                if plan["mask"][key] is not None:
+                    v = torch.where(plan["mask"][key], plan["vals"][key], v)
+                elif key in plan["learned"] and isinstance(p, T) and v.data_ptr() == p.data_ptr():
+                    v = v.clone()                                   # the launch below writes: not into the batch's own tensor
+            consts[key] = v.contiguous()
+        if src is None:
+            return consts
+        geometry = (m["row_kind"], m["max_lfo_delay"], m["max_min_delay"])
+        if self.fx_head is None:
+            self._fx_values = src.expand(consts, *geometry)
+        else:
+            pooled, raw_rows, self._fx_values = src.forward_rows(latent, consts, *geometry)
+            self._head_rows = (pooled, raw_rows)
         return consts
+
+    def _fixed_vectors(self, m: Dict[str, object]) -> Dict[str, object]:
+        """What ``learned_fx`` / ``fx_head`` fix or learn, laid out on the rows of the plan ``m``, per (B, device) once: "vals"
+        the (B,) fp32 vector of every key of ``fx.FX_CONSTS`` (a fixed number on the rows of its kind, 0 elsewhere), "mask" its
+        (B,) bool rows (None for a key without one), "learned" the keys the launch writes."""
+        from . import fx
+        src, bs, device, kinds = self._fxp, m["bs"], m["device"], m["kinds"]
+        plan = self._fixed_plan
+        if plan is None or plan["bs"] != bs or plan["device"] != device:
+            counts = {k: m[k].double().cpu() for k in ("max_lfo_delay", "max_min_delay")}
+            vals = {k: torch.zeros(bs, dtype=torch.float64) for k in fx.FX_CONSTS}
+            mask = {k: torch.zeros(bs, dtype=torch.bool) for k in fx.FX_CONSTS}
+            for (kind, name), v in src.fixed.items():
+                for i in (i for i in range(bs) if kinds[i] == kind):
+                    for key, from_name, _, how in CLIP_CONSTS:
+                        if from_name == name:
+                            vals[key][i] = v if how is None else 1.0 - v if how == "1-" else v * float(counts[how][i])
+                            mask[key][i] = True
+            learned = {n.split(".", 1)[1] for n in src.names}
+            plan = {"bs": bs, "device": device, "vals": {k: v.float().to(device) for k, v in vals.items()},
+                    "mask": {k: (v.to(device) if bool(v.any()) else None) for k, v in mask.items()},
+                    "learned": {key for key, from_name, _, _ in CLIP_CONSTS if from_name in learned}}
+            self._fixed_plan = plan
+        return plan
 
     def missing_fx_params(self, fx_params, bs: int) -> List[str]:
         """The "<kind>.<name>" a batch of ``bs`` rows needs for its re-render and has from nowhere: not in ``fx_params`` (which
@@ -621,92 +654,12 @@ class LFOExtractionThroughEffect(BaseLightingModule):
                     out.append(f"{kind}.{name}")
         return out
 
-    def _learned_constants(self, fx_params, bs: int, device, latent: Optional[T] = None) -> Dict[str, T]:
-        """``clip_constants`` of a step with ``learned_fx`` (or ``fx_head``: the same plan, but the one launch is
-        ``mx_fx_head_fwd`` on ``latent``, which is required then; it keeps the (B, P) values and ``_head_rows``).  Precedence
-        per (kind, name): learned or fixed by ``learned_fx`` on the rows of that kind, else the batch's ``fx_params`` as in
-        ``clip_constants`` (a ValueError names what neither has).
-        The fixed numbers meet their row's sample count in double and are rounded once (the rule of a python float), per
-        (B, device) once; the learned values are written over their rows by ``mx_fx_params_expand`` (fp64 map, rounded once,
-        then the rule of a tensor parameter).  Without ``fx_params`` the vectors are the cached ones, rewritten in place on
-        every step: no launch but the one.  Keeps the (P,) fp32 values for ``common_step`` to log."""
-        from . import fx
-        lf = self._fxp
+    def _require_fx_params(self, fx_params, bs: int) -> None:
+        """The ValueError that lists ``missing_fx_params``, if any."""
         missing = self.missing_fx_params(fx_params, bs)
         if missing:
-            raise ValueError(f"the re-render needs {missing}: neither in the batch's fx_params nor learned / fixed by "
-                             f"{self._fxp_name}")
-        if self.fx_head is not None:
-            if latent is None:
-                raise ValueError("a step with fx_head predicts the effect parameters from the model's latent: pass latent=")
-            latent = self._head_latent(latent, bs)
-        m = self._mixed_rows(bs, device)
-        lists, kinds = m["lists"], m["kinds"]
-        if self.check_fx_params:                                    # what is still read from the batch, on the rows that read it
-            for kind in dict.fromkeys(kinds):
-                rows = [i for i in range(bs) if kinds[i] == kind]
-                for name in fx.FX_PARAM_NAMES.get(kind, ()):
-                    if not lf.covers(kind, name):
-                        p = fx_params[name]
-                        fx._check_range(p[rows] if isinstance(p, T) else p, len(rows), *fx._fx_param_range(kind, name))
-        plan = self._fixed_plan
-        if plan is None or plan["bs"] != bs or plan["device"] != device:
-            mm, ml = m["max_min_delay"].double().cpu(), m["max_lfo_delay"].double().cpu()
-            vals = {k: torch.zeros(bs, dtype=torch.float64) for k in fx.FX_CONSTS}
-            mask = {k: torch.zeros(bs, dtype=torch.bool) for k in fx.FX_CONSTS}
-            for (kind, name), v in lf.fixed.items():
-                slot = fx.FX_NAME_SLOT[name]
-                for i in (i for i in range(bs) if kinds[i] == kind):
-                    vals[slot][i] = v * float(ml[i]) if name == "width" else v * float(mm[i]) if name == "min_delay_width" else v
-                    mask[slot][i] = True
-                    if name == "mix":
-                        vals["one_minus_mix"][i], mask["one_minus_mix"][i] = 1.0 - v, True
-            plan = {"bs": bs, "device": device, "vals": {k: v.float().to(device) for k, v in vals.items()},
-                    "mask": {k: (v.to(device) if bool(v.any()) else None) for k, v in mask.items()}}
-            self._fixed_plan = plan
-        learned_slots = {fx.FX_NAME_SLOT[n.split(".", 1)[1]] for n in lf.names}
-        if "mix" in learned_slots:
-            learned_slots.add("one_minus_mix")
-        source = {"lfo_scale": ("width", lambda v: v * m["max_lfo_delay"]), "min_delay": ("min_delay_width", lambda v: v * m["max_min_delay"]),
-                  "feedback": ("feedback", None), "depth": ("depth", None), "mix": ("mix", None),
-                  "one_minus_mix": ("mix", lambda v: 1.0 - v), "centre_frequency_hz": ("centre_frequency_hz", None)}
-        wanted = []
-        if lists["delay"] or lists["tremolo"] or lists["phaser"]:
-            wanted.append("mix")
-        if lists["delay"] or lists["tremolo"]:
-            wanted.append("one_minus_mix")
-        if lists["delay"] or lists["phaser"]:
-            wanted += ["feedback", "depth"]
-        if lists["delay"]:
-            wanted += ["lfo_scale", "min_delay"]
-        if lists["phaser"]:
-            wanted.append("centre_frequency_hz")
-        consts = {}
-        for key in wanted:
-            name, f = source[key]
-            p = None if fx_params is None else fx_params.get(name)
-            if p is None:                                           # learned / fixed on every row that reads it
-                consts[key] = plan["vals"][key]
-                continue
-            if isinstance(p, T):
-                assert p.shape == (bs,), f"fx_params['{name}']: a ({bs},) tensor or a python float"
-                v = p.to(device=device, dtype=torch.float32)
-                v = f(v) if f is not None else v
-            else:
-                v = torch.full((bs,), float(p), device=device, dtype=torch.float64)
-                v = (f(v) if f is not None else v).float()
-            if plan["mask"][key] is not None:
-                v = torch.where(plan["mask"][key], plan["vals"][key], v)
-            elif key in learned_slots and isinstance(p, T) and v.data_ptr() == p.data_ptr():
-                v = v.clone()                                       # the launch below writes: not into the batch's own tensor
-            consts[key] = v.contiguous()
-        if self.fx_head is not None:
-            pooled, raw_rows, self._fx_values = lf.forward_rows(latent, consts, m["row_kind"], m["max_lfo_delay"],
-                                                                m["max_min_delay"])
-            self._head_rows = (pooled, raw_rows)
-            return consts
-        self._fx_values = lf.expand(consts, m["row_kind"], m["max_lfo_delay"], m["max_min_delay"])
-        return consts
+            raise ValueError(f"the re-render needs {missing}: neither in the batch's fx_params nor learned / fixed through "
+                             f"learned_fx or fx_head")
 
     def _head_latent(self, latent, bs: int) -> T:
         """The latent as ``mx_fx_head_fwd`` reads it, or the ValueError that says what is wrong with it."""
@@ -797,28 +750,21 @@ class LFOExtractionThroughEffect(BaseLightingModule):
 
     def audio_loss(self, mod_sig_hat: T, dry: T, wet: T, fx_params, prefix: Optional[str] = None,
                    latent: Optional[T] = None):
-        """(loss, wet_hat (B, 1, N)) for an LFO (B, n_frames); with grad mode on and an LFO that requires grad the loss
-        carries the graph of ``_EffectAudioLossFn``, otherwise nothing is stashed and no backward kernel runs.  ``prefix``:
-        log every audio term under it."""
+        """(loss, wet_hat (B, 1, N)) for an LFO (B, n_frames); with grad mode on and an LFO, ``learned_fx.raw`` or an input of
+        ``fx_head`` (``latent``, its weight, its bias) that requires grad the loss carries the graph of ``_EffectAudioLossFn``,
+        otherwise nothing is stashed and no backward kernel runs.  ``prefix``: log every audio term under it."""
         from .effect_losses import effect_loss_terms
         dry_r, wet_r = self._rows(dry), self._rows(wet)
         terms: Dict[str, T] = {}
-        raw = None if self.learned_fx is None else self.learned_fx.raw
         head = self.fx_head
         if head is not None and latent is None:
             raise ValueError("a step with fx_head predicts the effect parameters from the model's latent: pass latent=")
-        if head is not None and torch.is_grad_enabled() and (mod_sig_hat.requires_grad or latent.requires_grad or
-                                                             head.weight.requires_grad or head.bias.requires_grad):
+        # the node's differentiable inputs beside the LFO
+        params = (latent, head.weight, head.bias) if head is not None else () if self.learned_fx is None else (self.learned_fx.raw,)
+        if torch.is_grad_enabled() and any(t.requires_grad for t in (mod_sig_hat, *params)):
             with torch.no_grad():
                 consts = self.clip_constants(fx_params, dry_r.size(0), dry_r.device, latent)
-            loss, wet_hat = _EffectAudioLossFn.apply(mod_sig_hat, None, self, dry_r, wet_r, consts, terms, latent, head.weight,
-                                                     head.bias)
-            wet_hat = wet_hat.unsqueeze(1)
-        elif head is None and torch.is_grad_enabled() and (mod_sig_hat.requires_grad or
-                                                           (raw is not None and raw.requires_grad)):
-            with torch.no_grad():
-                consts = self.clip_constants(fx_params, dry_r.size(0), dry_r.device)
-            loss, wet_hat = _EffectAudioLossFn.apply(mod_sig_hat, raw, self, dry_r, wet_r, consts, terms)
+            loss, wet_hat = _EffectAudioLossFn.apply(mod_sig_hat, self, dry_r, wet_r, consts, terms, *params)
             wet_hat = wet_hat.unsqueeze(1)
         else:
             wet_hat, loss = self.render(dry, mod_sig_hat, fx_params, latent), None
@@ -841,10 +787,7 @@ class LFOExtractionThroughEffect(BaseLightingModule):
         prefix = "train" if is_training else "val"
         dry, wet, mod_sig, fx_params = batch
         assert dry is not None, "the re-render needs the dry clip"
-        missing = self.missing_fx_params(fx_params, dry.size(0))
-        if missing:
-            raise ValueError(f"the re-render needs {missing}: neither in the batch's fx_params nor learned / fixed by "
-                             f"{self._fxp_name}")
+        self._require_fx_params(fx_params, dry.size(0))             # before any launch
         latent = None
         if self.fx_head is None:
             mod_sig_hat, _ = self.model(stack_dry_wet(dry, wet) if self.use_dry else wet)
@@ -1093,9 +1036,7 @@ class TBPTTLFOEffectModeling(BaseLightingModule):
         n_chunks_max = (batch[0].size(-1) - self.warmup_n_samples) // self.step_n_samples
         if prep is None:
             if is_training and world_size > 1:          # stay in lock-step with the other ranks
-                for _ in range(n_chunks_max):
-                    optimizer.zero_grad()
-                    optimizer.step(grad_scale=allreduce_flat_grad(optimizer.flat_grad, world_size))
+                self._idle_steps(optimizer, world_size, n_chunks_max)
             return None
         dry, wet, mod_sig_hat, mod_sig, lfo_sr = prep
         em, W, S = self.effect_model, self.warmup_n_samples, self.step_n_samples
@@ -1149,13 +1090,7 @@ class TBPTTLFOEffectModeling(BaseLightingModule):
                     # lightning.py:344-384 with the extractor in the graph: CNN -> moving average -> resampling -> this chunk
                     # of the LFO -> LSTM -> loss; backward in the opposite order, every stage on its own kernel
                     optimizer.zero_grad()
-                    with torch.enable_grad():
-                        hat, _ = self.lfo_model(lfo_in)
-                    hs = smoothen(hat.detach().squeeze(1), self.model_smooth_n_frames)
-                    hst = stretch_corners(hs, max_n_corners=self.max_n_corners, smooth_n_frames=self.stretch_smooth_n_frames) \
-                        if self.should_stretch else hs
-                    n_f = hst.size(-1)
-                    lfo_sr = linear_interpolate_last_dim(hst, n, align_corners=True).unsqueeze(1)
+                    hat, hs, hst, lfo_sr = self._extract_in_graph(lfo_in, n)
                     lat = lfo_sr[:, :, start:end]
                     y, h0, c0 = em.run_chunk(x, lat, stash)
                     if self._fused_l1:
@@ -1163,11 +1098,7 @@ class TBPTTLFOEffectModeling(BaseLightingModule):
                     else:
                         dy = effect_loss_grad(y, tgt, self.loss_dict, **self._grad_modules())
                         dlat = em.bptt_chunk_dlfo(x, lat, y, stash, h0, c0, lstm_grad, dy=dy)
-                    d_hs = linear_interpolate_last_dim_bwd(dlat[:, 0, :], n_f, n, start)
-                    if self.should_stretch:
-                        d_hs = stretch_corners_bwd(hs, d_hs, max_n_corners=self.max_n_corners, smooth_n_frames=self.stretch_smooth_n_frames)
-                    d_hs = smoothen_bwd(d_hs, self.model_smooth_n_frames)     # transpose of the moving average
-                    hat.backward(d_hs.view_as(hat))
+                    self._extract_backward(hat, hs, hst, dlat[:, 0, :], n, start)
                     optimizer.step(grad_scale=allreduce_flat_grad(optimizer.flat_grad, world_size))
                     em.detach_hidden()
                     mod_sig_hat = hst
@@ -1194,9 +1125,7 @@ class TBPTTLFOEffectModeling(BaseLightingModule):
                     y = em.run_chunk(x, lat)[0]
                 chunks.append(y)
             if is_training and world_size > 1:          # ranks may have cropped differently: pad the step count
-                for _ in range(n_chunks_max - done):
-                    optimizer.zero_grad()
-                    optimizer.step(grad_scale=allreduce_flat_grad(optimizer.flat_grad, world_size))
+                self._idle_steps(optimizer, world_size, n_chunks_max - done)
             wet_hat = torch.cat(chunks, dim=-1)
             m = wet_hat.size(-1)
             dry_c, wet_c, wet_hat = dry[:, :, W:m], wet[:, :, W:m].contiguous(), wet_hat[:, :, W:m].contiguous()
@@ -1221,6 +1150,34 @@ class TBPTTLFOEffectModeling(BaseLightingModule):
             return lfo
         return torch.cat([lfo, param_latent.repeat(1, 1, lfo.size(-1))], dim=1)
 
+    @staticmethod
+    def _idle_steps(optimizer, world_size: int, count: int) -> None:
+        """``count`` optimizer steps on an all-reduced zero gradient: a rank with fewer chunks than the others (or none) stays
+        in lock-step with them."""
+        from .trainer import allreduce_flat_grad
+        for _ in range(count):
+            optimizer.zero_grad()
+            optimizer.step(grad_scale=allreduce_flat_grad(optimizer.flat_grad, world_size))
+
+    def _extract_in_graph(self, lfo_in: T, n: int):
+        """The UNFROZEN extractor's forward chain (lightning.py:344-366): CNN (the only stage that records a graph) -> moving
+        average -> stretch_corners -> resampling to ``n`` samples.  Returns (hat, hs, hst, the audio-rate LFO (B, 1, n))."""
+        with torch.enable_grad():
+            hat, _ = self.lfo_model(lfo_in)
+        hs = smoothen(hat.detach().squeeze(1), self.model_smooth_n_frames)
+        hst = stretch_corners(hs, max_n_corners=self.max_n_corners, smooth_n_frames=self.stretch_smooth_n_frames) \
+            if self.should_stretch else hs
+        return hat, hs, hst, linear_interpolate_last_dim(hst, n, align_corners=True).unsqueeze(1)
+
+    def _extract_backward(self, hat: T, hs: T, hst: T, d_lfo: T, n: int, start: int) -> None:
+        """The backward of ``_extract_in_graph`` from d loss / d LFO (B, chunk) of the chunk at ``start``, every stage on its own
+        kernel: resampling window -> stretch_corners -> moving average -> ``hat.backward``."""
+        d_hs = linear_interpolate_last_dim_bwd(d_lfo, hst.size(-1), n, start)
+        if self.should_stretch:
+            d_hs = stretch_corners_bwd(hs, d_hs, max_n_corners=self.max_n_corners, smooth_n_frames=self.stretch_smooth_n_frames)
+        d_hs = smoothen_bwd(d_hs, self.model_smooth_n_frames)       # transpose of the moving average
+        hat.backward(d_hs.view_as(hat))
+
     def _general_train_chunk(self, x, tgt, wet, lfo_sr, mod_sig_hat, start, end, lfo_in, optimizer, world_size):
         """One TBPTT training step (lightning.py:358-384) with the effect model as an autograd node: any LSTM size, a
         param_model in the graph (re-evaluated on every step like the reference does), and -- ``lfo_in`` given -- the unfrozen
@@ -1233,11 +1190,7 @@ class TBPTTLFOEffectModeling(BaseLightingModule):
         with torch.enable_grad():
             hat = None
             if lfo_in is not None:
-                hat, _ = self.lfo_model(lfo_in)
-                hs = smoothen(hat.detach().squeeze(1), self.model_smooth_n_frames)
-                hst = stretch_corners(hs, max_n_corners=self.max_n_corners, smooth_n_frames=self.stretch_smooth_n_frames) \
-                    if self.should_stretch else hs
-                lfo_sr = linear_interpolate_last_dim(hst, n, align_corners=True).unsqueeze(1)
+                hat, hs, hst, lfo_sr = self._extract_in_graph(lfo_in, n)
                 mod_sig_hat = hst
             lat_lfo = lfo_sr[:, :, start:end]
             if hat is not None:
@@ -1248,11 +1201,7 @@ class TBPTTLFOEffectModeling(BaseLightingModule):
         dy = effect_loss_grad(_channel_rows(y.detach()), _channel_rows(tgt), self.loss_dict, **self._grad_modules())
         y.backward(dy.view_as(y))
         if hat is not None:
-            d_hs = linear_interpolate_last_dim_bwd(lat_lfo.grad[:, 0, :].contiguous(), hst.size(-1), n, start)
-            if self.should_stretch:
-                d_hs = stretch_corners_bwd(hs, d_hs, max_n_corners=self.max_n_corners, smooth_n_frames=self.stretch_smooth_n_frames)
-            d_hs = smoothen_bwd(d_hs, self.model_smooth_n_frames)
-            hat.backward(d_hs.view_as(hat))
+            self._extract_backward(hat, hs, hst, lat_lfo.grad[:, 0, :].contiguous(), n, start)
         optimizer.step(grad_scale=allreduce_flat_grad(optimizer.flat_grad, world_size))
         em.detach_hidden()
         return y.detach(), lfo_sr, mod_sig_hat

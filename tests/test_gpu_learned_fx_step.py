@@ -16,7 +16,12 @@ audio-loss step (fx.LearnedFxParams, csrc/fx_params.hip).
    tremolo (mix).
 6. real-pair shape: (dry, wet, None, None) batches, the flanger with all five names learned or fixed, Spectral2DCNN, three
    trainer.Trainer steps through a stub data module: finite losses, raw and the extractor's first weight both moved,
-   fx/flanger.feedback among the logged metrics; with one needed name missing the step raises a ValueError that names it."""
+   fx/flanger.feedback among the logged metrics; with one needed name missing the step raises a ValueError that names it.
+7. every source in one batch: ``clip_constants`` alone (no audio), with ``learned_fx`` and with a zero-weight ``fx_head``, on
+   B = 6 rows of (flanger, chorus, phaser, tremolo, dry, flanger) whose constants come from fixed numbers, learned values,
+   (B,) batch tensors and python floats at once.  Every vector, on the rows of the families that read it, is torch.equal to
+   the value formed in numpy from the rounding rule; the batch's tensors are not written; with every name covered and no
+   ``fx_params`` the cached vectors are rewritten in place."""
 import math
 
 import numpy as np
@@ -279,3 +284,87 @@ def test_real_pair_shape(dev):
     bad = lightning.LFOExtractionThroughEffect(cnn(N), sr=SR, effect="flanger", learned_fx=short).to(dev).train()
     with pytest.raises(ValueError, match="flanger.width"):
         bad.training_step((dry, wet, None, None))
+
+
+# ---- 7. every source of a constant in one batch ------------------------------------------------------------------------
+SIX = FIVE + ("flanger",)
+READERS = {"mix": ("delay", "tremolo", "phaser"), "one_minus_mix": ("delay", "tremolo"), "feedback": ("delay", "phaser"),
+           "depth": ("delay", "phaser"), "lfo_scale": ("delay",), "min_delay": ("delay",), "centre_frequency_hz": ("phaser",)}
+NAME_OF = {"mix": "mix", "one_minus_mix": "mix", "feedback": "feedback", "depth": "depth", "lfo_scale": "width",
+           "min_delay": "min_delay_width", "centre_frequency_hz": "centre_frequency_hz"}
+FAMILY = {"flanger": "delay", "chorus": "delay", "phaser": "phaser", "tremolo": "tremolo", "dry": "dry"}
+
+
+def hand_constant(key, row, kind, table, values, fxp, counts):
+    """One constant of one row by the stated rule.  A learned value (``values``: the launch's own fp32) and a batch tensor are
+    fp32 and meet the row's fp32 sample count, or 1 - mix, in fp32; a fixed number and a python float are doubles, meet them in
+    double and are rounded once.  Precedence: learned or fixed by ``table`` on the rows of its kind, else the batch."""
+    name = NAME_OF[key]
+    full = f"{kind}.{name}"
+    if full in table.names:
+        e = table.names.index(full)
+        v = np.float32(values[e] if values.ndim == 1 else values[row, e])
+    elif (kind, name) in table.fixed:
+        v = float(table.fixed[(kind, name)])
+    else:
+        p = fxp[name]
+        v = np.float32(p[row].item()) if isinstance(p, torch.Tensor) else float(p)
+    count = {"lfo_scale": counts[0][row], "min_delay": counts[1][row]}.get(key)
+    assert count is None or count.dtype == np.float32
+    if isinstance(v, np.float32):
+        out = v * count if count is not None else np.float32(1.0) - v if key == "one_minus_mix" else v
+        assert out.dtype == np.float32
+        return out
+    return np.float32(v * float(count) if count is not None else 1.0 - v if key == "one_minus_mix" else v)
+
+
+def check_constants(step, consts, values, fxp, B, dev):
+    table = step.learned_fx if step.learned_fx is not None else step.fx_head
+    m = step._mixed_rows(B, dev)
+    counts = (m["max_lfo_delay"].cpu().numpy(), m["max_min_delay"].cpu().numpy())
+    assert list(consts) == ["mix", "one_minus_mix", "feedback", "depth", "lfo_scale", "min_delay", "centre_frequency_hz"]
+    values = values.cpu().numpy()
+    for key, vec in consts.items():
+        assert vec.shape == (B,) and vec.dtype == torch.float32 and vec.is_contiguous() and vec.device == dev
+        rows = [i for i in range(B) if FAMILY[SIX[i]] in READERS[key]]
+        want = torch.tensor(np.asarray([hand_constant(key, i, SIX[i], table, values, fxp, counts) for i in rows], dtype=np.float32))
+        assert torch.equal(vec.cpu()[rows], want), (key, vec.cpu()[rows].tolist(), want.tolist())
+
+
+def step_with(source, spec, dev):
+    from mod_extraction_amd import lightning
+    kw = {"learned_fx": spec} if source == "learned_fx" else {"fx_head": dict(spec, in_ch=8)}
+    return lightning.LFOExtractionThroughEffect(torch.nn.Identity(), sr=SR, effect=SIX, **kw).to(dev)
+
+
+@pytest.mark.parametrize("source", ["learned_fx", "fx_head"])
+def test_every_source_in_one_batch(dev, source):
+    B = 6
+    g = torch.Generator().manual_seed(77)
+    latent = torch.randn(B, 8, 4, generator=g).to(dev) if source == "fx_head" else None
+    # flanger: width fixed, feedback and mix learned, the rest from the batch; chorus: the batch alone; phaser: the centre
+    # fixed; tremolo: mix fixed
+    spec = {"flanger": {"width": 0.8, "feedback": {"min": 0.0, "max": 0.7, "init": 0.3}, "mix": {"min": 0.0, "max": 1.0, "init": 0.4}},
+            "phaser": {"centre_frequency_hz": 1300.1}, "tremolo": {"mix": 0.65}}
+    step = step_with(source, spec, dev)
+    fxp = {"feedback": (0.05 + 0.6 * torch.rand(B, generator=g)).to(dev), "min_delay_width": 0.37,
+           "width": torch.rand(B, generator=g).to(dev), "depth": 0.9, "mix": torch.rand(B, generator=g).to(dev)}
+    keep = {k: v.clone() for k, v in fxp.items() if isinstance(v, torch.Tensor)}
+    consts = step.clip_constants(fxp, B, dev, latent)
+    assert step._fx_values.shape == ((2,) if source == "learned_fx" else (B, 2))
+    check_constants(step, consts, step._fx_values, fxp, B, dev)
+    assert all(torch.equal(fxp[k], v) for k, v in keep.items())                         # the batch's tensors are not written
+    # every name covered and no fx_params: the cached vectors, rewritten in place by the one launch
+    full = {"flanger": dict(DELAY, width=0.8), "chorus": dict(DELAY, min_delay_width=0.25), "phaser": dict(ALL["phaser"], mix=0.9),
+            "tremolo": {"mix": 0.65}}
+    step = step_with(source, full, dev)
+    first = step.clip_constants(None, B, dev, latent)
+    check_constants(step, first, step._fx_values, None, B, dev)
+    ptrs = {k: v.data_ptr() for k, v in first.items()}
+    before = {k: v.clone() for k, v in first.items()}
+    with torch.no_grad():
+        (step.learned_fx.raw if source == "learned_fx" else step.fx_head.bias).add_(0.3)
+    second = step.clip_constants(None, B, dev, latent)
+    assert {k: v.data_ptr() for k, v in second.items()} == ptrs
+    check_constants(step, second, step._fx_values, None, B, dev)
+    assert not torch.equal(second["feedback"], before["feedback"]) and torch.equal(first["feedback"], second["feedback"])

@@ -127,6 +127,37 @@ def test_constants_are_the_batchers():
         checked.clip_constants(dict(fxp, feedback=fb), B, CPU)
 
 
+def test_constants_table_against_the_kernel_side_tables():
+    """``lightning.CLIP_CONSTS`` (key, fx_params name, reading families, transform) against fx.FX_CONSTS / FX_PARAM_NAMES /
+    FX_NAME_SLOT, and the keys of ``clip_constants`` against it for every combination of families present."""
+    import itertools
+    from mod_extraction_amd import fx, lightning
+    table = lightning.CLIP_CONSTS
+    keys = [row[0] for row in table]
+    assert len(keys) == len(set(keys)) == len(fx.FX_CONSTS) and set(keys) == set(fx.FX_CONSTS)
+    assert keys == ["mix", "one_minus_mix", "feedback", "depth", "lfo_scale", "min_delay", "centre_frequency_hz"]
+    name_of = {row[0]: row[1] for row in table}
+    readers = {row[0]: tuple(row[2]) for row in table}
+    family = {"flanger": "delay", "chorus": "delay", "tremolo": "tremolo", "phaser": "phaser"}
+    for kind, names in fx.FX_PARAM_NAMES.items():
+        for name in names:
+            assert name_of[fx.FX_NAME_SLOT[name]] == name and family[kind] in readers[fx.FX_NAME_SLOT[name]], (kind, name)
+    assert name_of["one_minus_mix"] == "mix" and set(readers["one_minus_mix"]) == {"delay", "tremolo"} <= set(readers["mix"])
+    assert all(set(r) <= {"delay", "tremolo", "phaser"} for r in readers.values())
+    B = 5
+    fxp = {"feedback": 0.3, "min_delay_width": 0.7, "width": 0.1, "depth": 0.9, "mix": 0.6, "centre_frequency_hz": 1300.1}
+    five = ("flanger", "chorus", "phaser", "tremolo", "dry")
+    effects = [c for n in range(1, 6) for c in itertools.combinations(five, n)] + ["flanger", "tremolo", "phaser"]
+    seen = set()
+    for effect in effects:
+        step = step_of(effect)
+        lists = step._mixed_rows(B, CPU)["lists"]
+        want = [k for k in keys if any(lists[f] for f in readers[k])]
+        assert list(step.clip_constants(fxp, B, CPU)) == want, effect
+        seen.add(tuple(f for f in ("delay", "tremolo", "phaser") if lists[f]))
+    assert len(seen) == 8                                                           # every combination of families, none included
+
+
 def test_shipped_config_builds_its_object_graph():
     from mod_extraction_amd import cli, data_modules, lightning, models, optim
     old = os.getcwd()
