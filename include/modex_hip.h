@@ -820,4 +820,5 @@ int mx_fx_params_grad(const double *grads, const float *raw, const double *tab_f
 #include "modex_fx_head.h"
 /* K18, the LFO fit (csrc/lfo_fit.hip): one more entry point, declared in a file of its own for the same reason */
 #include "modex_lfo_fit.h"
+#include "modex_pair_align.h"
 #endif /* MODEX_HIP_H */

@@ -147,6 +147,13 @@ FIT_SIGNATURES = {
     "mx_lfo_fit": [_P, _I64, _I64, _I64, _F32, _F32, _F32, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P],
 }
 
+# name -> argtypes of what include/modex_pair_align.h declares (K19, lag and polarity of dry / wet pairs): likewise
+ALIGN_SIGNATURES = {
+    "mx_pair_xcorr": [_P, _I64, _P, _I64, _I64, _I64, _I64, _P, _P],
+    "mx_pair_peak": [_P, _I64, _P, _I64, _P, _I64, _I64, _I64, _P, _P, _P, _P],
+    "mx_pair_shift": [_P, _I64, _I64, _I64, _P, _P, _P, _I64, _P],
+}
+
 # measurement twins (same signatures): the dependent chain of the sample-recurrent kernels without global traffic
 PROBE_TWINS = ("mx_flanger_fwd", "mx_phaser_fwd", "mx_lstm_fwd", "mx_lstm_bwd_l1")
 for _name in PROBE_TWINS:
@@ -167,7 +174,8 @@ def load() -> ctypes.CDLL:
                 f"{SO_PATH} not found: build it with `python -m mod_extraction_amd.build` "
                 "(there is no CPU fallback)")
         lib = ctypes.CDLL(SO_PATH)
-        for name, argtypes in list(SIGNATURES.items()) + list(HEAD_SIGNATURES.items()) + list(FIT_SIGNATURES.items()):
+        for name, argtypes in (list(SIGNATURES.items()) + list(HEAD_SIGNATURES.items()) + list(FIT_SIGNATURES.items())
+                               + list(ALIGN_SIGNATURES.items())):
             fn = getattr(lib, name)          # AttributeError if the .so lacks a declared symbol
             fn.argtypes = argtypes
             fn.restype = ctypes.c_int

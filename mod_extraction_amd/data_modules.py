@@ -17,6 +17,7 @@ rank -- the IDMT / EGFx datasets are not part of this repository, and the benchm
 Data-module classes keep the reference names and accept the reference ``init_args`` so the shipped
 YAML configs instantiate.
 """
+import logging
 import math
 import os
 from typing import Any, Dict, List, Optional, Sequence, Tuple
@@ -28,6 +29,8 @@ from torch import Tensor as T
 from . import _hip, fx, util
 from .modulations import (SHAPE_IDS, draw_combined_table, draw_quasi_tables, make_combined_mod_sigs, make_mod_signals,
                           make_quasi_periodic_batch)
+
+log = logging.getLogger(__name__)
 
 LFO_SHAPES = ["cos", "rect_cos", "inv_rect_cos", "tri", "saw", "rsaw"]
 
@@ -564,19 +567,40 @@ class RandomAudioChunkDryWetDataModule(_SyntheticDataModule):
     ``dry_train_dir`` / ``wet_train_dir`` (and the ``_val_`` pair) present on disk the batches are recorded pairs
     (``datasets.RandomAudioChunkDryWetDataset``); otherwise synthetic dry clips and this package's phaser render."""
     kinds = ("phaser",)
+    # lag / polarity alignment of the recorded pairs (datasets.RandomAudioChunkDryWetDataset): these keys go to the pair
+    # datasets only; without align_max_lag_ms nothing is estimated and the pairs are read as they lie on disk
+    _ALIGN_KEYS = ("align_max_lag_ms", "align_n_probes", "align_min_corr")
 
     def _pair_dataset(self, which: str):
         dry_d, wet_d = self.ignored_args.get(f"dry_{which}_dir"), self.ignored_args.get(f"wet_{which}_dir")
         if not dry_d or not wet_d or not os.path.isdir(dry_d) or not os.path.isdir(wet_d):
             return None
         from . import datasets
-        kw = {k: self.ignored_args[k] for k in self._DS_KEYS if k in self.ignored_args}
+        kw = {k: self.ignored_args[k] for k in self._DS_KEYS + self._ALIGN_KEYS if k in self.ignored_args}
         n_ex = self.train_num_examples_per_epoch if which == "train" else self.val_num_examples_per_epoch
         return datasets.RandomAudioChunkDryWetDataset(dry_d, wet_d, self.n_samples, self.sr, num_examples_per_epoch=n_ex, **kw)
+
+    @property
+    def pair_alignment(self) -> Dict[str, Any]:
+        """``{"train": table, "val": table}``: each pair set's ``{file name: datasets.PairAlignment}``, None where there
+        is no such set or nothing was estimated."""
+        pairs = getattr(self, "_pairs", {})
+        return {w: (pairs[w].pair_alignment if pairs.get(w) is not None else None) for w in ("train", "val")}
+
+    def _align(self, which: str, ds, device: torch.device) -> None:
+        """Every rank computes the same deterministic table: no collective."""
+        table = ds.estimate_alignment(device)
+        good = [al for al in table.values() if al.ok]
+        lags = [al.lag for al in good] or [0]
+        log.info("%s pairs: %d files, %d aligned, lag %d .. %d samples, %d inverted", which, len(table), len(good), min(lags),
+                 max(lags), sum(al.polarity < 0 for al in good))
 
     def setup(self, device: torch.device, rank: int = 0, seed: int = 43) -> None:
         self._pairs = {w: self._pair_dataset(w) for w in ("train", "val")}
         self._device = device
+        for which, ds in self._pairs.items():
+            if ds is not None and ds.align_max_lag is not None:
+                self._align(which, ds, device)
         if self._pairs["train"] is None:
             super().setup(device, rank, seed)
 

@@ -18,7 +18,7 @@ Audio I/O is scipy's RIFF reader (memory mapped; PCM 16/24/32 and float32), scal
 """
 import logging
 import os
-from typing import Any, Dict, List, Optional, Tuple, Type
+from typing import Any, Dict, List, NamedTuple, Optional, Sequence, Tuple, Type
 
 import numpy as np
 import torch
@@ -192,14 +192,79 @@ class RandomAudioChunkDataset:
         return self.peak_normalize(chunk) if self.should_peak_norm else chunk
 
 
+class PairAlignment(NamedTuple):
+    """One file pair's constant alignment: the wet file is read ``lag`` samples later than the dry one and multiplied by
+    ``polarity`` (+1 / -1); ``corr`` is the median |normalised correlation| of the probes that found it, and ``ok`` is False
+    where the estimate was not trusted (then lag 0, polarity +1: the pair is read as it lies on disk)."""
+    lag: int
+    polarity: int
+    corr: float
+    ok: bool
+
+
+def reduce_probe_lags(lags: Sequence[int], corrs: Sequence[float], min_corr: float) -> PairAlignment:
+    """The per-file reduction of ``estimate_alignment``, on the probes' (lag, signed corr) pairs: the lower median of the
+    lags (periodic material has periodic correlation peaks, so single probes can sit a period off: the median outvotes
+    them), the polarity from the sign of the summed corr, the median |corr|.  No probe, or a median |corr| below
+    ``min_corr``: lag 0, polarity +1, ok False."""
+    if len(lags) != len(corrs):
+        raise ValueError("reduce_probe_lags: one corr per lag")
+    if len(lags) == 0:
+        return PairAlignment(0, 1, 0.0, False)
+    med = float(np.median(np.abs(np.asarray(corrs, dtype=np.float64))))
+    if not med >= min_corr:
+        return PairAlignment(0, 1, med, False)
+    lag = sorted(int(v) for v in lags)[(len(lags) - 1) // 2]
+    return PairAlignment(lag, -1 if float(np.sum(np.asarray(corrs, dtype=np.float64))) < 0.0 else 1, med, True)
+
+
+def wav_window(path: str, start: int, n: int) -> T:
+    """(channels, n) float32: the file's samples start .. start + n, zeros where the index leaves the file."""
+    frames = wav_info(path)[0]
+    lo, hi = max(0, start), min(frames, start + n)
+    if lo == start and hi == start + n:
+        return wav_load(path, frame_offset=start, num_frames=n)[0]
+    ch = wav_info(path)[2]
+    out = torch.zeros((ch, n), dtype=torch.float32)
+    if lo < hi:
+        out[:, lo - start:hi - start] = wav_load(path, frame_offset=lo, num_frames=hi - lo)[0]
+    return out
+
+
 class RandomAudioChunkDryWetDataset(RandomAudioChunkDataset):
-    """datasets.py:236-329: chunks of recorded dry / wet pairs (same file name in two directories)."""
+    """datasets.py:236-329: chunks of recorded dry / wet pairs (same file name in two directories).
+
+    Alignment (no counterpart in the reference).  A recorded wet went through a re-amping chain or an interface round trip:
+    it is late by a constant bulk latency and sometimes inverted, which a sample-by-sample re-render of the dry chunk
+    cannot absorb.  With ``align_max_lag_ms`` set, ``estimate_alignment(device)`` measures one integer lag and one polarity
+    a file pair by cross-correlation on the device (``alignment.estimate_pair_lag`` on ``align_n_probes`` chunks a file,
+    reduced by ``reduce_probe_lags`` with ``align_min_corr``) into ``pair_alignment``; ``set_alignment`` installs such a table
+    without a device.  With a table, an item's wet chunk is the wet file at ``start + lag`` times the polarity: an exact shift
+    (no interpolation), zeros only where the index leaves the file, which is at most |lag| samples at a file's two ends --
+    ``end_buffer_n_samples >= the largest lag`` keeps the random starts clear of the end that positive lags reach.
+    ``should_peak_norm`` still normalises dry and wet independently, as the reference does: a step that compares a
+    re-render of dry with wet sample by sample wants it off.  With ``align_max_lag_ms=None`` and no ``set_alignment`` nothing
+    differs from the reference's reads."""
+
+    ALIGN_ROW_BUDGET = 64                               # probe rows of one estimate_pair_lag call
 
     def __init__(self, dry_dir: str, wet_dir: str, n_samples: int, sr: float, ext: str = "wav",
                  num_examples_per_epoch: int = 10000, silence_fraction_allowed: float = 0.1,
                  silence_threshold_energy: float = 1e-6, n_retries: int = 10, check_dataset: bool = True,
                  min_suitable_files_fraction: float = 0.5, end_buffer_n_samples: int = 0, should_peak_norm: bool = False,
-                 peak_norm_db: float = -1.0) -> None:
+                 peak_norm_db: float = -1.0, align_max_lag_ms: Optional[float] = None, align_n_probes: int = 8,
+                 align_min_corr: float = 0.5) -> None:
+        self.align_max_lag: Optional[int] = None
+        if align_max_lag_ms is not None:
+            lag = int(round(float(align_max_lag_ms) * 1e-3 * sr))
+            if not (align_max_lag_ms > 0 and 1 <= lag <= min(8192, n_samples - 1)):
+                raise ValueError(f"align_max_lag_ms = {align_max_lag_ms!r} is {lag} samples at sr = {sr}: need 1 .. "
+                                 f"min(8192, n_samples - 1) = {min(8192, n_samples - 1)}")
+            if int(align_n_probes) < 1 or not 0.0 <= align_min_corr <= 1.0:
+                raise ValueError("align_n_probes must be >= 1 and align_min_corr in 0 .. 1")
+            self.align_max_lag = lag
+        self.align_max_lag_ms, self.align_n_probes, self.align_min_corr = align_max_lag_ms, int(align_n_probes), align_min_corr
+        self.pair_alignment: Optional[Dict[str, PairAlignment]] = None
         super().__init__(dry_dir, n_samples, sr, ext, num_examples_per_epoch, silence_fraction_allowed,
                          silence_threshold_energy, n_retries, check_dataset, min_suitable_files_fraction,
                          end_buffer_n_samples, should_peak_norm, peak_norm_db)
@@ -222,9 +287,91 @@ class RandomAudioChunkDryWetDataset(RandomAudioChunkDataset):
         self.input_paths = self.dry_paths
         self.name_to_wet_path = {os.path.basename(d): w for d, w in pairs}
 
+    def set_alignment(self, mapping: Optional[Dict[str, Any]]) -> None:
+        """Install ``{file name: PairAlignment or (lag, polarity[, corr, ok])}`` (None removes it): for users who know their
+        latency, and for tests.  Files the table does not name are read unshifted."""
+        if mapping is None:
+            self.pair_alignment = None
+            return
+        table = {}
+        for name, v in mapping.items():
+            v = tuple(v)
+            al = PairAlignment(int(v[0]), int(v[1]), float(v[2]) if len(v) > 2 else 1.0, bool(v[3]) if len(v) > 3 else True)
+            if name not in self.name_to_wet_path:
+                raise ValueError(f"set_alignment: no pair named {name!r}")
+            if al.polarity not in (1, -1):
+                raise ValueError(f"set_alignment: polarity of {name!r} must be +1 or -1, got {al.polarity}")
+            table[name] = al
+        self.pair_alignment = table
+
+    def probe_starts(self, dry_path: str) -> List[int]:
+        """The ``align_n_probes`` evenly spaced chunk starts of a file (fewer where they coincide): no RNG draw."""
+        wet_frames = wav_info(self.name_to_wet_path[os.path.basename(dry_path)])[0]
+        span = min(self.num_frames(dry_path), wet_frames) - self.n_samples
+        if span <= 0:
+            return [0]
+        p = self.align_n_probes
+        return sorted({(span * k) // max(1, p - 1) for k in range(p)}) if p > 1 else [span // 2]
+
+    def estimate_alignment(self, device: torch.device) -> Dict[str, PairAlignment]:
+        """Measure ``pair_alignment``: per pair ``align_n_probes`` chunks of ``n_samples`` (channel 0) at evenly spaced
+        offsets, those with a dry mean energy below ``silence_threshold_energy`` left out; the probes of as many files as
+        fit ``ALIGN_ROW_BUDGET`` rows go through one ``alignment.estimate_pair_lag`` call, and ``reduce_probe_lags`` reduces
+        each file's.  Deterministic and without a draw from the RNG helpers: every rank computes the same table and the
+        item stream of a seeded run does not move.  Untrusted pairs keep lag 0 / polarity +1 and are named in a warning."""
+        if self.align_max_lag is None:
+            raise ValueError("estimate_alignment needs align_max_lag_ms")
+        from . import alignment
+        n = self.n_samples
+        table: Dict[str, PairAlignment] = {}
+        batch: List[Tuple[str, T, T]] = []                      # (file name, dry probe (n,), wet probe (n,))
+
+        def flush() -> None:
+            if not batch:
+                return
+            dry = torch.stack([d for _, d, _ in batch]).to(device)
+            wet = torch.stack([w for _, _, w in batch]).to(device)
+            est = alignment.estimate_pair_lag(dry, wet, self.align_max_lag)
+            lags, corrs = est.lag.cpu().tolist(), est.corr.cpu().tolist()
+            for name in dict.fromkeys(nm for nm, _, _ in batch):
+                rows = [i for i, (nm, _, _) in enumerate(batch) if nm == name]
+                table[name] = reduce_probe_lags([lags[i] for i in rows], [corrs[i] for i in rows], self.align_min_corr)
+            batch.clear()
+
+        for dry_path in self.dry_paths:
+            name = os.path.basename(dry_path)
+            wet_path = self.name_to_wet_path[name]
+            probes = []
+            for start in self.probe_starts(dry_path):
+                d = wav_window(dry_path, start, n)[0]
+                if float((d ** 2).mean()) < self.silence_threshold_energy:
+                    continue
+                probes.append((name, d, wav_window(wet_path, start, n)[0]))
+            if not probes:
+                table[name] = reduce_probe_lags([], [], self.align_min_corr)
+                continue
+            if len(batch) + len(probes) > self.ALIGN_ROW_BUDGET:
+                flush()
+            batch.extend(probes)
+        flush()
+        table = {os.path.basename(p): table[os.path.basename(p)] for p in self.dry_paths}
+        bad = [name for name, al in table.items() if not al.ok]
+        if bad:
+            log.warning("alignment not trusted (no usable probe, or median |corr| < %.2f), read unshifted: %s",
+                        self.align_min_corr, ", ".join(bad))
+        self.pair_alignment = table
+        return table
+
     def __getitem__(self, _: int) -> Tuple[T, T]:
         dry, dry_path, ch, start = self.search_dataset_for_audio_chunk(self.n_samples, self.end_buffer_n_samples)
-        wet, _ = wav_load(self.name_to_wet_path[os.path.basename(dry_path)], frame_offset=start, num_frames=self.n_samples)
+        name = os.path.basename(dry_path)
+        al = self.pair_alignment.get(name) if self.pair_alignment is not None else None
+        if al is None:
+            wet, _ = wav_load(self.name_to_wet_path[name], frame_offset=start, num_frames=self.n_samples)
+        else:
+            wet = wav_window(self.name_to_wet_path[name], start + al.lag, self.n_samples)
+            if al.polarity < 0:
+                wet = -wet
         if wet.size(0) > 1:
             wet = wet[ch, :].view(1, -1)
         assert dry.shape == wet.shape
