@@ -288,13 +288,16 @@ int mx_plane_stats_finish(const float *part, const float *bias, const float *slo
 /* LayerNorm -> Conv2d(5x13, dilation (1,dilation), same) -> +bias -> MaxPool(2,1), fused.
  * in (B,Cin,H,352): log-mel (first_layer=1) or the previous block's pooled pre-activations (their
  * PReLU, slope (Cin,), is applied on the fly).  out (B,64,H/2,352) pooled PRE-activations,
- * out_amax (B,64,H/2,352) uint8 = which of the two pooled rows won (first max on ties). */
+ * out_amax (B,64,H/2,352) uint8 = which of the two pooled rows won (first max on ties).
+ * Cin: any even number >= 2.  All 352 columns of out and out_amax are written: columns >= Wv of out are zeros, those of
+ * out_amax are unspecified (0 or 1).  Columns >= Wv of in are read but never reach a result. */
 int mx_conv_block_fwd(const float *in, const float *stats, const float *slope, const float *wt,
                       const float *bias, int64_t B, int64_t Cin, int64_t H, int64_t Wv, int32_t dilation,
                       int32_t first_layer, float *out, uint8_t *out_amax, void *stream);
 
 /* data gradient of the block's convolution: G (B,64,H/2,352) = dL/d(pooled pre-activation),
- * routed through amax; wt_flipped = weights packed with flip=1; dxhat (B,64,H,352). */
+ * routed through amax; wt_flipped = weights packed with flip=1; dxhat (B,64,H,352).
+ * All 352 columns of dxhat are written: columns >= Wv are zeros.  Columns >= Wv of G and amax never reach a result. */
 int mx_conv_block_dgrad(const float *G, const uint8_t *amax, const float *wt_flipped, int64_t B, int64_t H,
                         int64_t Wv, int32_t dilation, float *dxhat, void *stream);
 

@@ -1,6 +1,8 @@
 """GPU parity, kernel by kernel: the fused conv block forward, its data gradient and its weight
 gradient against torch's CPU Conv2d / LayerNorm / MaxPool2d / PReLU autograd (fp32), for every
-temporal dilation the model family uses and for full (345) and short (88) frame counts."""
+temporal dilation the model family uses and for full (345) and short (88) frame counts.  This is the
+chain test of the exact-fp32 family; tests/test_gpu_f32block_units.py holds each of its entry points to
+an fp64 reference (guard bands, poisoned pad columns, exact-on-integers cases, derived bounds)."""
 import numpy as np
 import pytest
 import torch
