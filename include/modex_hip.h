@@ -824,4 +824,5 @@ int mx_fx_params_grad(const double *grads, const float *raw, const double *tab_f
 /* K18, the LFO fit (csrc/lfo_fit.hip): one more entry point, declared in a file of its own for the same reason */
 #include "modex_lfo_fit.h"
 #include "modex_pair_align.h"
+#include "modex_gain_match.h"
 #endif /* MODEX_HIP_H */

@@ -154,6 +154,14 @@ ALIGN_SIGNATURES = {
     "mx_pair_shift": [_P, _I64, _I64, _I64, _P, _P, _P, _I64, _P],
 }
 
+# name -> argtypes of what include/modex_gain_match.h declares (K20, the per-clip gain match, forward and backward): likewise
+GAIN_SIGNATURES = {
+    "mx_gain_match_partials": [_P, _I64, _P, _I64, _I64, _I64, _P, _P],
+    "mx_gain_match_apply": [_P, _I64, _P, _I64, _I64, _I32, _F64, _I32, _F64, _F64, _P, _I64, _P, _P, _P, _P],
+    "mx_gain_match_bwd_partials": [_P, _I64, _P, _I64, _I64, _I64, _P, _P],
+    "mx_gain_match_bwd_apply": [_P, _I64, _P, _I64, _P, _I64, _P, _P, _P, _P, _I64, _I64, _I32, _F64, _P, _I64, _P],
+}
+
 # measurement twins (same signatures): the dependent chain of the sample-recurrent kernels without global traffic
 PROBE_TWINS = ("mx_flanger_fwd", "mx_phaser_fwd", "mx_lstm_fwd", "mx_lstm_bwd_l1")
 for _name in PROBE_TWINS:
@@ -175,7 +183,7 @@ def load() -> ctypes.CDLL:
                 "(there is no CPU fallback)")
         lib = ctypes.CDLL(SO_PATH)
         for name, argtypes in (list(SIGNATURES.items()) + list(HEAD_SIGNATURES.items()) + list(FIT_SIGNATURES.items())
-                               + list(ALIGN_SIGNATURES.items())):
+                               + list(ALIGN_SIGNATURES.items()) + list(GAIN_SIGNATURES.items())):
             fn = getattr(lib, name)          # AttributeError if the .so lacks a declared symbol
             fn.argtypes = argtypes
             fn.restype = ctypes.c_int

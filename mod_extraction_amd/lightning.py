@@ -268,9 +268,15 @@ class _EffectAudioLossFn(torch.autograd.Function):
         from .effect_losses import effect_loss_grad, effect_loss_terms
         mod = mod_sig_hat.detach().float().contiguous()
         wet_hat, stashes = step._render_rows(dry, mod, consts, stash=True)
+        rendered = wet_hat                        # what the adjoints (and the gain match's backward) read
+        if step.match_gain is not None:           # every row in one launch pair, dry rows included: the losses see the match
+            wet_hat = step._match_rows(rendered, wet)
         a, t = wet_hat.unsqueeze(1), wet.unsqueeze(1)
         weighted: Dict[str, T] = {}
         dy = effect_loss_grad(a, t, step.audio_loss_dict, values=weighted, **step._grad_modules())
+        if step.match_gain is not None:           # d loss / d z -> d loss / d (the un-matched render), in place
+            from .gain import match_gain_backward
+            match_gain_backward(dy, rendered, wet, step._gain, step.match_gain, step.match_gain_eps, out=dy)
         # the adjoints write (they do not add) the rows of their family, and the reduction reads only those: no zeros
         gbuf = torch.empty((6, dry.size(0)), device=dry.device, dtype=torch.float64) if params else None
         dmod = step._adjoint_rows(dy, dry, mod, consts, stashes, gbuf=gbuf)
@@ -376,6 +382,15 @@ class LFOExtractionThroughEffect(BaseLightingModule):
       is ``learned_fx`` at its ``init``.  Every training step logs ``fx/<kind>.<name>`` = the mean of the predicted values
       over the rows of that kind and ``fx_std/<kind>.<name>`` = their standard deviation; ``data_dict["fx_values"]`` holds
       them all, (B, P).  ``render(..., latent=)`` needs the latent.
+    * ``match_gain`` (optional): "ls" or "rms" -- one gain per clip that carries the re-render onto ``wet`` before any loss
+      sees it (``gain.match_gain``, K20: "ls" the least-squares gain <wet_hat, wet> / (<wet_hat, wet_hat> + eps), "rms" the
+      energy match), with ``match_gain_eps`` and the clamp ``match_gain_range`` = (lo, hi), 0 < lo <= 1 <= hi, or None.
+      A recorded wet is never at the dry's level and every effect here passes the dry at unit gain.  All rows of the batch
+      are matched in one launch pair, the losses, the returned ``wet_hat`` and the logged terms are those of the matched
+      rows, and d loss / d wet_hat passes through ``gain.match_gain_backward`` (in place) before the adjoints, which read the
+      un-matched render.  A training step logs ``gain/mean``, ``gain/std`` and ``gain/clamped`` (the share of clamped rows),
+      ``data_dict["gain"]`` is the (B,) vector; ``render`` has no ``wet`` and stays un-matched.  Without it the step's
+      launches are unchanged.  What a free gain trades off against: DESIGN section 7.
     * ``loss_dict`` (optional, default none): an LFO-domain term (lightning.py:33-62) added to the loss when the batch carries
       ``mod_sig``; it is logged as ``{prefix}/lfo_{name}``.
     The LFO enters the effect at the extractor's own rate (n_frames points, resampled in-kernel exactly as the data path
@@ -417,10 +432,20 @@ class LFOExtractionThroughEffect(BaseLightingModule):
                  pre_emph_filter_cfs: Sequence[float] = (-0.95, 1.0),
                  pre_emph_low_pass: bool = False,
                  learned_fx=None,
-                 fx_head=None) -> None:
+                 fx_head=None,
+                 match_gain: Optional[str] = None,
+                 match_gain_eps: float = 1e-8,
+                 match_gain_range: Optional[Sequence[float]] = (0.05, 20.0)) -> None:
         super().__init__({} if loss_dict is None else loss_dict)
         self._set_pre_emph(pre_emph_filter_cfs, pre_emph_low_pass)
         from . import fx
+        from .gain import check_mode
+        if isinstance(match_gain_range, list):  # a config file's spelling of the pair
+            match_gain_range = tuple(match_gain_range)
+        # eps and the range are validated without match_gain too: a typo does not wait for the day it is switched on
+        check_mode("ls" if match_gain is None else match_gain, match_gain_eps, match_gain_range, "match_gain")
+        self.match_gain, self.match_gain_eps, self.match_gain_range = match_gain, match_gain_eps, match_gain_range
+        self._gain = None                       # the gain.GainMatch of the last matched batch
         from .effect_losses import GRAD_NAMES
         if should_stretch:
             raise NotImplementedError("should_stretch is not supported when training through the rendered effect")
@@ -479,6 +504,15 @@ class LFOExtractionThroughEffect(BaseLightingModule):
         self.step_metric_names = [] if learned_fx is None else [f"fx/{n}" for n in learned_fx.names]
         if fx_head is not None:
             self.step_metric_names = [f"fx/{n}" for n in fx_head.names] + [f"fx_std/{n}" for n in fx_head.names]
+        if match_gain is not None:
+            self.step_metric_names = self.step_metric_names + ["gain/mean", "gain/std", "gain/clamped"]
+
+    def _match_rows(self, rendered: T, wet: T) -> T:
+        """The rows of ``rendered`` brought to the level of ``wet`` (``gain.match_gain``: two launches for all rows); the
+        ``GainMatch`` is kept in ``_gain`` for the backward, the log and ``data_dict``."""
+        from .gain import match_gain
+        self._gain = match_gain(rendered, wet, self.match_gain, self.match_gain_eps, self.match_gain_range)
+        return self._gain.z
 
     @property
     def _fxp(self):
@@ -741,7 +775,8 @@ class LFOExtractionThroughEffect(BaseLightingModule):
         """wet_hat (B, 1, N) = the effect on ``dry`` (B, 1, N) driven by ``mod_sig`` (B, n_mod) at its own rate, with the
         per-clip constants of ``fx_params``; no graph and no stash kept (``_render_rows``: the data path's launches; the
         phaser with lead 0, see the class docstring).  ``latent``: required by a step with ``fx_head`` (a ValueError without
-        it), whose forward kernel alone runs then."""
+        it), whose forward kernel alone runs then.  There is no ``wet`` here, so the result is NOT gain-matched whatever
+        ``match_gain`` says: it is the effect at unit dry gain."""
         rows = self._rows(dry)
         with torch.no_grad():
             consts = self.clip_constants(fx_params, rows.size(0), rows.device, latent)
@@ -768,6 +803,8 @@ class LFOExtractionThroughEffect(BaseLightingModule):
             wet_hat = wet_hat.unsqueeze(1)
         else:
             wet_hat, loss = self.render(dry, mod_sig_hat, fx_params, latent), None
+            if self.match_gain is not None:                         # validation: the terms below are taken on the matched rows
+                wet_hat = self._match_rows(wet_hat, wet)
         if prefix is not None or loss is None:
             with torch.no_grad():
                 missing = [k for k in self.audio_loss_dict if k not in terms]
@@ -821,8 +858,8 @@ class LFOExtractionThroughEffect(BaseLightingModule):
                 loss = loss + lfo_term
         self.log(f"{prefix}/loss", loss)
         if is_training and self.learned_fx is not None:             # views of the launch's values vector: no host sync
-            for i, name in enumerate(self.step_metric_names):
-                self.log(name, self._fx_values[i])
+            for i, name in enumerate(self.learned_fx.names):
+                self.log(f"fx/{name}", self._fx_values[i])
         if is_training and self.fx_head is not None:                # a handful of (B, P) device operations: no host sync
             m = self._mixed_rows(dry.size(0), dry.device)
             mean = (self._fx_values * m["head_mask"]).sum(0) / m["head_count"]
@@ -830,10 +867,17 @@ class LFOExtractionThroughEffect(BaseLightingModule):
             for i, name in enumerate(self.fx_head.names):
                 self.log(f"fx/{name}", mean[i])
                 self.log(f"fx_std/{name}", std[i])
+        if is_training and self.match_gain is not None:             # three (B,) device reductions: no host sync
+            g = self._gain.gain
+            self.log("gain/mean", g.mean())
+            self.log("gain/std", g.std(unbiased=False))
+            self.log("gain/clamped", self._gain.flags.float().mean())
         data_dict = {"dry": dry.detach(), "wet": wet.detach(), "wet_hat": wet_hat.detach(),
                      "mod_sig_hat": mod_sig_hat.detach()}
         if self.fx_head is not None:
             data_dict["fx_values"] = self._fx_values
+        if self.match_gain is not None:
+            data_dict["gain"] = self._gain.gain
         if mod_sig is not None:
             data_dict["mod_sig"] = mod_sig.detach()
         return loss, data_dict, fx_params
