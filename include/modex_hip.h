@@ -13,6 +13,10 @@
  *     re-entrant per stream; the library never synchronises
  *   - return value: 0 = launched, MX_ERR_ARG (-1) bad argument, MX_ERR_UNSUPPORTED (-2) size not
  *     supported (e.g. delay line > LDS), MX_ERR_LAUNCH (-3) HIP launch error.  Never throws.
+ *   - every entry point is `int mx_name(...)`; a parameter is a pointer or one of int64_t, int32_t, uint64_t,
+ *     uint32_t, float, double.  This file is the one statement of the signatures: csrc/common.h includes it, so
+ *     the compiler holds every definition to its declaration, and mod_extraction_amd/_hip.py derives its ctypes
+ *     table from this text (and refuses any other parameter type).
  *
  * Each entry point cites the reference code it replaces (file:line in /root/reference).
  */
@@ -768,7 +772,7 @@ int mx_reduce_rows_adamw_step(const float *part, int64_t R, float *param, float 
                               float grad_scale, void *stream);
 
 /* ---- K12 with gradient clipping (csrc/optim_clip.hip) -- the trainer keys gradient_clip_val / gradient_clip_algorithm of
- * the reference's configs/trained/*.yml, i.e. torch.nn.utils.clip_grad_norm_ (2-norm) and clip_grad_value_ on the one flat
+ * the reference's configs/trained/ files, i.e. torch.nn.utils.clip_grad_norm_ (2-norm) and clip_grad_value_ on the one flat
  * gradient; the clip coefficient is formed and consumed on the device.
  *
  * mx_grad_sumsq: stat[0] = sum of grad[i]^2, i in [0, n), in fp64 (squares exact).  Two launches: workgroup w of G sums the
@@ -816,13 +820,145 @@ int mx_fx_params_grad(const double *grads, const float *raw, const double *tab_f
                       double raw_gain, const int32_t *row_kind, const float *max_lfo_delay, const float *max_min_delay,
                       int64_t B, double scale, float *d_raw, void *stream);
 
+/* ---- K17: effect parameters per clip, from a linear head on the extractor's latent (csrc/fx_head.hip) -- no counterpart in
+ * the reference.  The table, the slots, the kinds, raw_gain, row_kind and the sample counts are those of K16 (above);
+ * raw is no longer shared but one row per clip:
+ *   pooled[b, c] = mean_w latent[b, c, w];  raw[b, e] = bias[e] + sum_c weight[e, c] pooled[b, c];  value[b, e] = map(raw[b, e]),
+ * each an fp64 evaluation in a fixed order of the fp32 result before it, rounded to fp32 once.  So weight == 0 writes the
+ * bits mx_fx_params_expand writes for raw = bias.  latent (B, C, W) fp32 dense, weight (P, C), bias (P,) fp32.  NULL required
+ * pointer, P, B, C or W <= 0: MX_ERR_ARG; P > 16, C > 1024 or C W >= 2^31: MX_ERR_UNSUPPORTED; all before any launch.
+ *
+ * mx_fx_head_fwd (one workgroup per clip): writes pooled (B, C), raw_rows (B, P) (both required: the backward reads them) and
+ * values (B, P) (optional), and on the rows of an entry's kind the value into the row of its slot's (B,) vector by the rule
+ * of mx_fx_params_expand (lfo_scale / min_delay times the row's sample count in fp32, one_minus_mix = 1 - mix in fp32).  Rows
+ * and slots without an entry are not written; a NULL vector skips its slot. */
+int mx_fx_head_fwd(const float *latent, int64_t B, int64_t C, int64_t W, const float *weight, const float *bias,
+                   const double *tab_f, const int32_t *tab_i, int64_t P, double raw_gain, const int32_t *row_kind,
+                   const float *max_lfo_delay, const float *max_min_delay, float *lfo_scale, float *min_delay, float *feedback,
+                   float *depth, float *mix, float *one_minus_mix, float *centre_frequency_hz, float *pooled, float *raw_rows,
+                   float *values, void *stream);
+/* With d_raw[b, e] = scale * grads[slot_e, b] * (the row's sample count where the slot has one) * d value / d raw at
+ * raw_rows[b, e] on the rows of the entry's kind, 0 elsewhere (grads (6, B) fp64 as in mx_fx_params_grad; other rows are not
+ * read and may hold anything): d_raw_rows (B, P), d_bias (P,) = sum_b d_raw, d_weight (P, C) = sum_b d_raw[b, e] pooled[b, c],
+ * d_latent (B, C, W) = (1 / W) sum_e d_raw[b, e] weight[e, c] for every w (every element is written; rows without an entry
+ * get exact zeros).  Each output is fp32, optional, and one rounding of an fp64 sum in a fixed order.  At most two launches,
+ * no atomics, no workspace: deterministic.  Both count vectors are required. */
+int mx_fx_head_bwd(const double *grads, const float *raw_rows, const float *pooled, const float *weight, const double *tab_f,
+                   const int32_t *tab_i, int64_t P, double raw_gain, const int32_t *row_kind, const float *max_lfo_delay,
+                   const float *max_min_delay, int64_t B, int64_t C, int64_t W, double scale, float *d_raw_rows, float *d_bias,
+                   float *d_weight, float *d_latent, void *stream);
+
+/* ---- K18: rate, phase and shape of LFO rows (csrc/lfo_fit.hip) -- no counterpart in the reference.
+ * y: B rows of n fp32 points, y_stride floats apart; sr: the rate of the points in Hz; [f_min, f_max]: the rate window in Hz;
+ * shape_mask: bit s allows shape id s (0 cos, 1 rect_cos, 2 inv_rect_cos, 3 tri, 4 saw, 5 rsaw, 6 sqr).
+ *
+ * A candidate (shape s, rate f, centre phase phic) has the template t_i = the value mx_lfo_synth writes at point i for
+ * (fl32(f), ph, s, exp = 1, start = 0), where ph makes the template's own argument at position (n + 1) / 2 equal phic:
+ *   ph_eff = (phic - step_eff (n + 1) / 2) mod 2 pi (step_eff: the fp32 phase step of the shape, the halved one for the
+ *   rectified cosines);  ph = ph_eff, or 2 (ph_eff mod pi) for the rectified cosines;  fp64, rounded to fp32 once; a value
+ *   that rounds to fl32(2 pi) becomes 0, so 0 <= ph < 2 pi.
+ * Objective, fp64 in a fixed order, yc = y - mean(y), tc = t - mean(t):  Syy = sum yc^2, Stt = sum tc^2, Sty = sum tc yc,
+ *   a = Sty / Stt if Stt > 0 and Sty > 0, else 0 (a >= 0: with a free sign saw / rsaw and rect_cos / inv_rect_cos are one
+ *   family);  R = Syy - a Sty;  b = mean(y) - a mean(t).
+ * Search per allowed shape: the grid f_k = f_min + k df, df = sr / (rate_div n), k < K = floor((f_max - f_min) / df) + 1,
+ * phi_j = j (2 pi / J), j < J: argmin R, ties to the lowest (k, j); then rounds l = 1..L over the 5 x 5 points
+ * f0 + i df / 2^l (clamped into the window), (phi0 + j (2 pi / J) / 2^l) mod 2 pi, i, j = -2..2, visited in (i, j) order, a
+ * point replacing the best only where R is strictly smaller.  Then the argmin over the shapes, ties to the lowest id.
+ *
+ * Outputs (B,), each one fp32 rounding of the fp64 quantity: shape (int32), rate_hz = fl32(f), phase = ph, amp = a,
+ * offset = b, resid = R / Syy; per_shape_resid (B, 7) is optional and holds each shape's R / Syy, +inf where not allowed.
+ * offset + amp * mx_lfo_synth(rate_hz, phase, shape) is the best template bit for bit.  A constant row (Syy == 0) returns the
+ * lowest allowed shape, rate f_min, phase 0, amp 0, offset its mean, resid 0; a row no candidate correlates positively with
+ * returns amp 0, resid 1.  One launch, one workgroup per row, no atomics, no workspace: deterministic.
+ * NULL required pointer, B <= 0, f_min <= 0, f_max < f_min, f_max >= sr / 2, an empty mask or bits above 6, L < 0,
+ * y_stride < n: MX_ERR_ARG; n outside [16, 4096], K > 512, J outside [4, 128], L > 8, rate_div outside [1, 16]:
+ * MX_ERR_UNSUPPORTED; all before any launch.  K == 1 (f_min == f_max) fits phase and shape at a known rate. */
+int mx_lfo_fit(const float *y, int64_t y_stride, int64_t B, int64_t n, float sr, float f_min, float f_max, int32_t shape_mask,
+               int32_t rate_div, int32_t J, int32_t L, int32_t *shape, float *rate_hz, float *phase, float *amp, float *offset,
+               float *resid, float *per_shape_resid, void *stream);
+
+/* ---- K19: constant lag and polarity of dry / wet rows (csrc/pair_align.hip) -- no counterpart in the reference.
+ * dry, wet: B rows of N fp32 samples, dry_stride / wet_stride floats apart; l runs over -L..L, 0 <= L < N.
+ *
+ *   r[b, l + L] = sum_n dry[b, n] wet[b, n + l]   over the n with both indices in [0, N)
+ *   c           = r / sqrt(sum dry^2 sum wet^2)   (the energies of the whole rows)
+ *   lag         = the l of the largest |c|; ties go to the smallest |l|, then to the non-negative one
+ *   corr        = the signed c at lag; the polarity is its sign
+ *   frac        = 0.5 (a - c+) / (a - 2 b0 + c+) with a, b0, c+ = |c| at lag - 1, lag, lag + 1: the vertex of the parabola
+ *                 through the three; 0 at the window's two edges (lag = -L or L) or where the denominator is 0
+ *   a row whose dry or wet energy is 0: lag 0, corr 0, frac 0
+ * Convention: wet[n + lag] ~ sign(corr) dry[n]; a wet that is late by d samples has lag = +d.
+ *
+ * Every sum is fp64 in a fixed order (the product of two fp32 values is exact in fp64), no atomics, no workspace: the same
+ * arguments give the same bits.  |r - exact| <= N 2^-53 sum |dry wet|.
+ * All three: a NULL required pointer, B <= 0, N <= 0, a stride < N: MX_ERR_ARG; N > 2^24, B > 65535: MX_ERR_UNSUPPORTED;
+ * xcorr and peak also L < 0 or L >= N: MX_ERR_ARG, L > 8192: MX_ERR_UNSUPPORTED; all before any launch. */
+
+/* r_out: (B, 2 L + 1) fp64, contiguous.  Grid (tile of 64 lags, row); one lag a lane. */
+int mx_pair_xcorr(const float *dry, int64_t dry_stride, const float *wet, int64_t wet_stride, int64_t B, int64_t N, int64_t L,
+                  double *r_out, void *stream);
+
+/* r: what mx_pair_xcorr wrote for the same rows.  Outputs (B,): lag_out int32, corr_out and frac_out fp32, each one rounding
+ * of the fp64 quantity.  One workgroup a row. */
+int mx_pair_peak(const float *dry, int64_t dry_stride, const float *wet, int64_t wet_stride, const double *r, int64_t B,
+                 int64_t N, int64_t L, int32_t *lag_out, float *corr_out, float *frac_out, void *stream);
+
+/* out[b, n] = s_b wet[b, n + lag[b]], 0 where n + lag[b] leaves [0, N); s_b = -1 where corr[b] < 0, else +1 (corr may be
+ * NULL: s_b = +1).  lag: (B,) int32, any value; out rows out_stride floats apart.  With mx_pair_peak's lag and corr,
+ * out ~ dry.  out may not overlap wet: MX_ERR_ARG. */
+int mx_pair_shift(const float *wet, int64_t wet_stride, int64_t B, int64_t N, const int32_t *lag, const float *corr,
+                  float *out, int64_t out_stride, void *stream);
+
+/* ---- K20: one gain per clip (csrc/gain_match.hip) -- no counterpart in the reference.
+ * y_hat (the rendered wet), y (the recorded wet): B rows of N fp32 samples, a row stride (in floats, >= N) apart.
+ *
+ *   a = <y_hat, y_hat>,  c = <y_hat, y>,  e = <y, y>                      (fp64 sums of exact products, fixed order)
+ *   mode MX_GAIN_LS:   g = c / (a + eps)                                   (least squares)
+ *   mode MX_GAIN_RMS:  g = sqrt((e + eps) / (a + eps))                     (energy match)
+ *   clamp != 0: g < lo -> lo, g > hi -> hi, and the row is flagged; 0 < lo <= 1 <= hi.  clamp == 0: lo and hi are not read.
+ *   g is rounded once to fp32;  z = fl32(g * y_hat)                        (one fp32 multiplication)
+ * There is no branch for a silent row: eps > 0 keeps every quotient finite (a silent y_hat: "ls" g = 0, then the clamp).
+ *
+ * Backward, with dz = d loss / d z, s = <dz, y_hat> and the fp32 g the forward applied:
+ *   MX_GAIN_LS,  row not flagged:  dy_hat = g dz + s (y - 2 g y_hat) / (a + eps)
+ *   MX_GAIN_RMS, row not flagged:  dy_hat = g dz - s g y_hat / (a + eps)
+ *   a flagged row, either mode:    dy_hat = g dz
+ * each element formed in fp64 and rounded once.  y gets no gradient.
+ *
+ * A workgroup owns MX_GAIN_CHUNK samples of one row: n_chunks = ceil(N / MX_GAIN_CHUNK), grid (n_chunks, B).  The two
+ * `partials` launches write one fp64 partial sum per workgroup into a caller-supplied workspace; the two `apply` launches
+ * re-reduce the n_chunks partials of their row in one fixed order in every workgroup.  No atomics: the same arguments give
+ * the same bits.  |sum - exact| <= N 2^-53 sum |terms|.
+ * All four, before any launch: a NULL pointer, B < 1, N < 1, a stride < N, a mode other than the two, eps that is not a
+ * finite number above 0, clamp != 0 with a range outside 0 < lo <= 1 <= hi, an output that overlaps an input (but
+ * dy_hat == dz with the same stride): MX_ERR_ARG.  N > 2^24, B > 65535: MX_ERR_UNSUPPORTED. */
+#define MX_GAIN_CHUNK 2048
+#define MX_GAIN_LS 0
+#define MX_GAIN_RMS 1
+
+/* partials: (B, n_chunks, 3) fp64 = the partial a, c, e of every chunk. */
+int mx_gain_match_partials(const float *y_hat, int64_t y_hat_stride, const float *y, int64_t y_stride, int64_t B, int64_t N,
+                           double *partials, void *stream);
+
+/* partials: what mx_gain_match_partials wrote for the same rows.  z: B rows z_stride apart; it may not overlap y_hat
+ * (the backward reads the un-matched rows).  gain (B,) fp32, sums (B, 3) fp64 = a, c, e, flags (B,) int32 (1 = clamped):
+ * written by the workgroup of chunk 0. */
+int mx_gain_match_apply(const float *y_hat, int64_t y_hat_stride, const double *partials, int64_t B, int64_t N, int32_t mode,
+                        double eps, int32_t clamp, double lo, double hi, float *z, int64_t z_stride, float *gain,
+                        double *sums, int32_t *flags, void *stream);
+
+/* partials: (B, n_chunks) fp64 = the partial s of every chunk. */
+int mx_gain_match_bwd_partials(const float *dz, int64_t dz_stride, const float *y_hat, int64_t y_hat_stride, int64_t B,
+                               int64_t N, double *partials, void *stream);
+
+/* gain, sums, flags: what mx_gain_match_apply wrote; partials: what mx_gain_match_bwd_partials wrote.  dy_hat may be dz
+ * itself (same pointer, same stride: the in-place update); it may overlap nothing else that is read. */
+int mx_gain_match_bwd_apply(const float *dz, int64_t dz_stride, const float *y_hat, int64_t y_hat_stride, const float *y,
+                            int64_t y_stride, const float *gain, const double *sums, const int32_t *flags,
+                            const double *partials, int64_t B, int64_t N, int32_t mode, double eps, float *dy_hat,
+                            int64_t dy_hat_stride, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
-/* K17, the per-clip effect-parameter head (csrc/fx_head.hip): two more entry points, declared in a file of their own */
-#include "modex_fx_head.h"
-/* K18, the LFO fit (csrc/lfo_fit.hip): one more entry point, declared in a file of its own for the same reason */
-#include "modex_lfo_fit.h"
-#include "modex_pair_align.h"
-#include "modex_gain_match.h"
 #endif /* MODEX_HIP_H */

@@ -1,5 +1,5 @@
 """K19: the constant lag and the polarity of recorded dry / wet pairs, by cross-correlation on the device
-(csrc/pair_align.hip; include/modex_pair_align.h has the definition) -- no counterpart in the reference.
+(csrc/pair_align.hip; include/modex_hip.h, K19, has the definition) -- no counterpart in the reference.
 
     r[b, l + L] = sum_n dry[b, n] wet[b, n + l],  l = -L..L;   c = r / sqrt(sum dry^2 sum wet^2)
     lag = argmax |c| (ties: smallest |l|, then l >= 0);  corr = c[lag];  frac = the parabolic sub-sample offset

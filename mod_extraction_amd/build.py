@@ -18,9 +18,10 @@ SRC = os.path.join(HERE, "csrc")
 OUT_DIR = os.path.join(HERE, "_lib")
 OBJ_DIR = os.path.join(OUT_DIR, "obj")
 SO = os.path.join(OUT_DIR, "libmodex_hip.so")
+INCLUDE = os.path.join(HERE, "..", "include")       # the public header; csrc/common.h includes it
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
-         "-fvisibility=hidden", "-Wall", "-Wno-unused-function", "-I", os.path.join(HERE, "..", "include")]
+         "-fvisibility=hidden", "-Wall", "-Wno-unused-function", "-I", INCLUDE]
 
 
 # Per-file overrides.  The FFT kernels (MR-STFT loss, log-mel front end) are VALU-issue bound and only tolerance-tested
@@ -41,7 +42,7 @@ def sources():
 
 def build(force: bool = False, verbose: bool = True) -> str:
     os.makedirs(OBJ_DIR, exist_ok=True)
-    headers = [os.path.join(SRC, f) for f in os.listdir(SRC) if f.endswith(".h")]
+    headers = [os.path.join(d, f) for d in (SRC, INCLUDE) for f in os.listdir(d) if f.endswith(".h")]
     hdr_time = max([os.path.getmtime(h) for h in headers] + [0.0])
     jobs = []
     for f in sources():

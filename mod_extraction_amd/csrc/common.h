@@ -4,10 +4,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#define MX_OK 0
-#define MX_ERR_ARG (-1)       // bad shape / null pointer / out-of-range parameter
-#define MX_ERR_UNSUPPORTED (-2)  // e.g. delay line larger than the LDS budget
-#define MX_ERR_LAUNCH (-3)    // hipGetLastError() after launch
+// The public header: MX_OK / MX_ERR_*, and the declaration of every entry point, so that an MX_EXPORT definition which
+// differs from its declaration is a compile error ("conflicting types") in whichever translation unit defines it.
+#include "modex_hip.h"
 
 #define MX_EXPORT extern "C" __attribute__((visibility("default")))
 

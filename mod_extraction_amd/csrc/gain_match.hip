@@ -1,5 +1,5 @@
 // gain_match.hip -- K20: one gain per clip that carries a rendered wet (y_hat) onto a recorded one (y), forward and
-// backward -- no counterpart in the reference (include/modex_gain_match.h has the definition).
+// backward -- no counterpart in the reference (include/modex_hip.h, K20, has the definition).
 //
 //     a = <y_hat, y_hat>, c = <y_hat, y>, e = <y, y>;   "ls": g = c / (a + eps);   "rms": g = sqrt((e + eps) / (a + eps))
 //     z = fl32(fl32(g) * y_hat);   s = <dz, y_hat>;   dy_hat = g dz + s dg/dy_hat  (a clamped row: g dz)
@@ -23,7 +23,7 @@
 //     dz[i] before it writes dy_hat[i] and nobody else touches i, so dy_hat may be dz.
 // Memory bound: forward 2 reads + (1 read, 1 write) of B N floats, backward 2 + (3, 1).
 #include "common.h"
-#include "modex_gain_match.h"
+#include "modex_hip.h"
 
 #define GM_THREADS 256
 #define GM_CHUNK MX_GAIN_CHUNK

@@ -1,5 +1,5 @@
 // pair_align.hip -- K19: the constant lag and the polarity of a recorded dry / wet pair by cross-correlation, and the integer
-// shift that undoes them -- no counterpart in the reference (include/modex_pair_align.h has the definition).
+// shift that undoes them -- no counterpart in the reference (include/modex_hip.h, K19, has the definition).
 //
 //     r[b, l + L] = sum_n dry[b, n] wet[b, n + l]   (both indices in [0, N)),   l = -L..L
 //     c = r / sqrt(sum dry^2 sum wet^2);  lag = argmax |c| (ties: smallest |l|, then l >= 0);  corr = c[lag];
@@ -21,7 +21,7 @@
 //     alignment, so it is read through a 4-byte-aligned vector type.  Chunks at the row's tail or across the source's ends
 //     go element by element with the bounds check.
 #include "common.h"
-#include "modex_pair_align.h"
+#include "modex_hip.h"
 
 #define XC_THREADS 256
 #define XC_WAVES (XC_THREADS / MX_WAVE)

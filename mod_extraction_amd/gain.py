@@ -1,5 +1,5 @@
 """K20: one gain per clip that carries a rendered wet onto a recorded one, forward and backward on the device
-(csrc/gain_match.hip; include/modex_gain_match.h has the definition) -- no counterpart in the reference.
+(csrc/gain_match.hip; include/modex_hip.h, K20, has the definition) -- no counterpart in the reference.
 
     a = <y_hat, y_hat>,  c = <y_hat, y>,  e = <y, y>          (fp64 sums of exact products, a fixed order)
     "ls":  g = c / (a + eps)             "rms":  g = sqrt((e + eps) / (a + eps))

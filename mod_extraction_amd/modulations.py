@@ -403,7 +403,7 @@ def fit_lfo(mod_sig: T, sr: float, rate_hz=(0.25, 8.0), shapes: Sequence[str] = 
     """Rate, phase and shape of every row of ``mod_sig`` ((B, n) or (n,), fp32, on the device; ``sr`` the rate of its
     points, 172.5 for 345 points of a 2 s clip) in one ``mx_lfo_fit`` launch: a grid search over the rate window ``rate_hz``
     (spacing ``sr / (rate_div n)``) and ``n_phases`` centre phases, ``n_rounds`` rounds of 5 x 5 refinement, per allowed shape,
-    with a non-negative amplitude and a free offset (include/modex_lfo_fit.h has the definition).  Rows a row stride apart
+    with a non-negative amplitude and a free offset (include/modex_hip.h, K18, has the definition).  Rows a row stride apart
     (inner stride 1) are read in place."""
     mask = fit_shape_mask(shapes)
     f_min, f_max = fit_rate_window(rate_hz, float(sr))

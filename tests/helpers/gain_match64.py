@@ -1,4 +1,4 @@
-"""The per-clip gain match (K20, include/modex_gain_match.h) restated in numpy fp64, one row at a time.
+"""The per-clip gain match (K20, include/modex_hip.h) restated in numpy fp64, one row at a time.
 
     a = <y_hat, y_hat>, c = <y_hat, y>, e = <y, y>;   "ls": g = c / (a + eps);   "rms": g = sqrt((e + eps) / (a + eps))
     gain_range (lo, hi): g < lo -> lo, g > hi -> hi, flagged;   g32 = fl32(g);   z = g32 * y_hat

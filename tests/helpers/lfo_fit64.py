@@ -1,4 +1,4 @@
-"""The LFO fit (K18, include/modex_lfo_fit.h) restated in numpy: the definition the kernel implements, vectorised over candidates.
+"""The LFO fit (K18, include/modex_hip.h) restated in numpy: the definition the kernel implements, vectorised over candidates.
 
 Templates are the fp32 values of ``lfo_value`` (csrc/lfo_common.h): rate, phase and phase step are rounded to fp32 as the
 kernel rounds them and every fp32 operation of ``lfo_value`` is an fp32 numpy operation; only the cosine is taken in fp64 of

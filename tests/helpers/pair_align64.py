@@ -1,4 +1,4 @@
-"""The lag and polarity estimate (K19, include/modex_pair_align.h) restated in numpy fp64: r, c, the tie rule, frac, the
+"""The lag and polarity estimate (K19, include/modex_hip.h) restated in numpy fp64: r, c, the tie rule, frac, the
 zero-energy rule, the shift -- and the seeded table of dry / wet rows the CPU and GPU tests share.
 
     r[l + L] = sum_n dry[n] wet[n + l]  (both indices in [0, N));   c = r / sqrt(sum dry^2 sum wet^2)

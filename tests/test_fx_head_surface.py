@@ -136,26 +136,21 @@ def test_model_without_a_latent_or_with_other_channels():
 
 
 def test_abi_has_the_two_entry_points():
-    """The two entries are declared in include/modex_fx_head.h, which include/modex_hip.h includes, and bound through
-    ``_hip.HEAD_SIGNATURES``, which ``_hip.load`` binds beside ``_hip.SIGNATURES``: the text of modex_hip.h and
-    ``_hip.SIGNATURES`` are held equal to each other (tests/test_abi.py) and to 107 entry points
-    (tests/test_learned_fx_surface.py), so entry points that are added have a header and a table of their own."""
-    import re
+    """The two entries are declared in include/modex_hip.h (section K17) like every other, and ``_hip.SIGNATURES``, the one
+    binding table, is derived from that text (tests/test_abi.py holds the two to each other over all entry points)."""
     from mod_extraction_amd import _hip, build
     from tests.test_abi import header_arg_counts
     lib = ctypes.CDLL(build.build(verbose=False))
-    main = open(os.path.join(ROOT, "include", "modex_hip.h")).read()
-    assert re.search(r'^#include "modex_fx_head\.h"$', main, flags=re.M)
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "modex_fx_head.h")).read(), flags=re.S)
-    counts = {name: len(args.split(",")) for name, args in re.findall(r"\bint\s+(mx_\w+)\s*\(([^;]*?)\)\s*;", text, flags=re.S)}
-    assert set(counts) == set(_hip.HEAD_SIGNATURES) == {"mx_fx_head_fwd", "mx_fx_head_bwd"}
+    counts = header_arg_counts()
+    assert {n for n in counts if n.startswith("mx_fx_head_")} == {"mx_fx_head_fwd", "mx_fx_head_bwd"}
     for name, n in (("mx_fx_head_fwd", 24), ("mx_fx_head_bwd", 20)):
-        assert hasattr(lib, name) and counts[name] == n == len(_hip.HEAD_SIGNATURES[name]), name
+        assert hasattr(lib, name) and counts[name] == n == len(_hip.SIGNATURES[name]), name
     assert _hip.ABI_VERSION == 21 == lib.mx_abi_version()
-    assert len(header_arg_counts()) == 107 and not set(_hip.HEAD_SIGNATURES) & set(_hip.SIGNATURES)
     zeros = {ctypes.c_void_p: None, ctypes.c_int64: 0, ctypes.c_float: 0.0, ctypes.c_double: 0.0}
-    for name, argtypes in _hip.HEAD_SIGNATURES.items():                      # as tests/test_abi.py does for the main table
-        assert getattr(_hip.load(), name)(*[zeros[t] for t in argtypes]) == -1, name
+    for name in ("mx_fx_head_fwd", "mx_fx_head_bwd"):
+        fn = getattr(_hip.load(), name)
+        assert fn.argtypes == _hip.SIGNATURES[name]                          # load() binds the table
+        assert fn(*[zeros[t] for t in fn.argtypes]) == -1, name
     # arguments are checked before any launch: P = 17, C = 1025 are refused without a device
     lib2 = _hip.load()
     one = ctypes.c_void_p(8)

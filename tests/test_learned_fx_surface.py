@@ -87,8 +87,7 @@ def test_abi_has_the_two_entry_points():
     counts = header_arg_counts()
     for name, n in (("mx_fx_params_expand", 18), ("mx_fx_params_grad", 13)):
         assert hasattr(lib, name) and counts[name] == n == len(_hip.SIGNATURES[name]), name
-    assert _hip.ABI_VERSION == 21 == lib.mx_abi_version()
-    assert len(counts) == 107
+    assert _hip.ABI_VERSION == 21 == lib.mx_abi_version()                    # (tests/test_abi.py pins the number of entry points)
     # arguments are checked before any launch: P = 17 is refused without a device
     lib2 = _hip.load()
     one = ctypes.c_void_p(8)

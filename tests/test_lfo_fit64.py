@@ -1,4 +1,4 @@
-"""CPU: the LFO fit as a definition (include/modex_lfo_fit.h), on its numpy restatement tests/helpers/lfo_fit64.py -- what
+"""CPU: the LFO fit as a definition (include/modex_hip.h, K18), on its numpy restatement tests/helpers/lfo_fit64.py -- what
 the fit finds on clean LFOs, and its special cases.  The kernel is held to the same helper in tests/test_gpu_lfo_fit.py.
 
 Rows: ``0.1 + 0.7 t`` for the six default shapes, one rate from each of the bands 1.5-3, 3-6 and 6-12 cycles in the row (kept

@@ -1,9 +1,8 @@
-"""CPU: the surface of the pair alignment (K19) -- the header include/modex_pair_align.h against ``_hip.ALIGN_SIGNATURES``,
+"""CPU: the surface of the pair alignment (K19) -- its declarations in include/modex_hip.h against ``_hip.SIGNATURES``,
 the limits of the three entry points (checked before any launch, so without a device), the ``ValueError``s of the wrappers
 in ``mod_extraction_amd.alignment``, ``PairLag``, and the shipped config.  No device work."""
 import ctypes
 import os
-import re
 
 import pytest
 import torch
@@ -14,29 +13,20 @@ ARG, UNSUPPORTED = -1, -2
 
 
 def test_header_table_and_symbols():
-    """Three entry points, declared in a header of their own that modex_hip.h includes, bound through a table of their own:
-    modex_hip.h's own declarations and ``_hip.SIGNATURES`` stay at 107 entries, the other two tables at their names."""
+    """Three entry points, declared in include/modex_hip.h (section K19) and bound from ``_hip.SIGNATURES``, which is derived
+    from that text."""
     from mod_extraction_amd import _hip, build
     from tests.test_abi import header_arg_counts
     lib = ctypes.CDLL(build.build(verbose=False))
-    main = open(os.path.join(ROOT, "include", "modex_hip.h")).read()
-    for inc in ("modex_fx_head", "modex_lfo_fit", "modex_pair_align"):
-        assert re.search(rf'^#include "{inc}\.h"$', main, flags=re.M), inc
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "modex_pair_align.h")).read(), flags=re.S)
-    counts = {name: len(args.split(",")) for name, args in re.findall(r"\bint\s+(mx_\w+)\s*\(([^;]*?)\)\s*;", text, flags=re.S)}
-    assert counts == NAMES
-    assert {k: len(v) for k, v in _hip.ALIGN_SIGNATURES.items()} == NAMES
-    others = set(_hip.SIGNATURES) | set(_hip.HEAD_SIGNATURES) | set(_hip.FIT_SIGNATURES)
-    assert not set(_hip.ALIGN_SIGNATURES) & others
-    assert set(_hip.HEAD_SIGNATURES) == {"mx_fx_head_fwd", "mx_fx_head_bwd"} and set(_hip.FIT_SIGNATURES) == {"mx_lfo_fit"}
-    assert _hip.ABI_VERSION == 21 == lib.mx_abi_version() and len(header_arg_counts()) == 107
-    assert len(header_arg_counts()) + len(_hip.HEAD_SIGNATURES) + len(_hip.FIT_SIGNATURES) + len(_hip.ALIGN_SIGNATURES) == 113
+    assert {k: v for k, v in header_arg_counts().items() if k.startswith("mx_pair_")} == NAMES
+    assert {k: len(v) for k, v in _hip.SIGNATURES.items() if k.startswith("mx_pair_")} == NAMES
+    assert _hip.ABI_VERSION == 21 == lib.mx_abi_version()
     zeros = {ctypes.c_void_p: None, ctypes.c_int64: 0, ctypes.c_int32: 0, ctypes.c_float: 0.0}
-    for name, argtypes in _hip.ALIGN_SIGNATURES.items():
+    for name in NAMES:
         assert hasattr(lib, name)
         fn = getattr(_hip.load(), name)
-        assert fn.argtypes == argtypes                                        # load() binds the table
-        assert fn(*[zeros[t] for t in argtypes]) == ARG
+        assert fn.argtypes == _hip.SIGNATURES[name]                           # load() binds the table
+        assert fn(*[zeros[t] for t in fn.argtypes]) == ARG
 
 
 def p(v):
