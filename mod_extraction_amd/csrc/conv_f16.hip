@@ -28,10 +28,13 @@
 // The next stage's global loads are issued into registers before the current stage's MFMAs (26 vectors per
 // thread), fragments are software pipelined in two half-tap sets.  4 waves = (co tile) x (output row),
 // 11 accumulators of 32x32 each; epilogue identical to the fp32 kernel (bias + max-pool + argmax, or plain).
-// Used for the five 64->64 blocks (all dilations; LDS 100-123 KB); the 2-channel first block and the weight
-// gradients stay on the exact-fp32 kernels (conv2d.hip, wgrad.hip).
+// That kernel (conv_f16x3_kernel, operands staged through registers) still runs the DENSE data gradient at dilation 8 and
+// 16.  The forward runs on its LDS-DMA descendants below: conv_f16x3_dma16_kernel (dilation <= 4, four-row patch ring),
+// conv_f16x3_dma3_kernel (dilation 8 and 16, three-row patch ring, halo tiles left out), conv1_f16x3_tile_kernel (first
+// block); the dense data gradient at dilation <= 4 on conv_f16x3_dma_kernel.
 #include "conv_common.h"
 #include <hip/hip_fp16.h>
+#include <type_traits>
 
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 #define F16_WSCALE 256.0f
@@ -442,6 +445,8 @@ __device__ __forceinline__ void conv_f16_epilogue(ACC &acc, const ConvF16Args &a
     }
 }
 
+// Launched with OUTMODE 1 at T = 8 and 16 only (the dense data gradient); OUTMODE 0 is the forward it once ran, kept
+// compilable: conv_f16x3_dma3_kernel below took it over and computes the same bits.
 template <int T, int OUTMODE>      // OUTMODE 0: bias + maxpool + argmax, 1: plain rows
 __global__ __launch_bounds__(256, 1) void conv_f16x3_kernel(ConvF16Args a)
 {
@@ -1428,6 +1433,266 @@ __global__ __launch_bounds__(256, 1) void conv_f16x3_dma16_kernel(ConvF16Args a)
     conv_f16_epilogue<0>(acc, a, smem, b, h0, row, c, lane);
 }
 
+// ---- LDS-DMA version on a ring of THREE row slots (forward, T = 8 and 16) --------------------------------------------
+// conv_f16x3_dma_kernel's tap body (v_mfma_f32_32x32x16_f16: K = one tap x 16 channels, so no tap pair straddles two
+// stages and no more than two patch rows are ever read at once), weights in the same two half-stage buffers, the patch in
+// a ring of three ROW slots of 4 planes [split][khalf] x (352 + 12 T) positions:
+//   T = 8 : 2 x 28 KB + 3 x 28 672 B = 143 360 B;      T = 16 : 2 x 28 KB + 3 x 34 816 B = 161 792 B (budget 163 840).
+// The plane pitches (448 / 544 positions) are multiples of 16 positions: every plane starts on bank 0.
+// Stage (cb, kh) reads input rows j = kh (output row 0) and kh + 1 (output row 1) of the six rows j = 0..5 = h0 - 2 ..
+// h0 + 3 of channel block cb; row j lives in slot j % 3 (6 cb + j = j mod 3).  The stage fetches row kh + 2 for its
+// successor into the slot that row kh - 1 left; stage (cb, 4) fetches row 0 of block cb + 1 into the free slot 0, and
+// row 1 of that block -- slot 1 holds row 4 until the stage ends -- follows the end-of-stage barrier in one burst: one
+// exposed row fetch per channel-block opening, three per workgroup.  (A stage order that avoids it would have to change
+// the order in which an accumulator meets its stages, and with it the rounding: results stay bit-identical instead.)
+// DMA pieces per wave and stage: 6 + 7 of weights, 7 (T = 8) / 9 (T = 16) of the new row, in the 26 slots of a stage:
+//   phase A (14 slots): W1 <- this stage's taps 7..12 in slots 0..5, row pieces 0..7 behind them; ends on vmcnt(row pieces)
+//   phase B (12 slots): W0 <- the next stage's taps 0..6 in slots 0..6, row piece 8 riding along in slot 0; ends on vmcnt(0)
+//
+// Halo tiles.  The B fragment of (tap kw, column tile nt) holds patch positions 32 nt + l + kw T, l < 32, that is image
+// columns w = 32 nt + l + (kw - 6) T.  Positions with w < 0 or w >= 352 are never fetched from the operand: their DMA
+// descriptor names the zero slot (make of desc[] below), whatever Wv is and whatever the operand's pad columns hold.  So
+// the fragment is all zeros, for EVERY frame count, exactly when 32 nt + 31 + (kw - 6) T < 0 or 32 nt + (kw - 6) T >= 352
+// (conv_halo_tile): its three matrix instructions per channel half add products with an exact zero operand, and they and the
+// fragment's two LDS reads are left out.  T = 16: left nt = 0 for kw <= 4, nt = 1 for kw <= 2, nt = 2 for kw = 0, and
+// mirrored on the right (nt = 10, 9, 8 for kw >= 8, 10, 12): 18 of the 143 (tap, tile) pairs; T = 8: nt = 0 for kw <= 2
+// and nt = 10 for kw >= 10: 6 of 143.  (With the shipped 345 frames the set is the same: the next candidate, nt = 10 at
+// shift 16, still reaches column 336 < 345.)  One instantiation therefore serves every Wv.  The taps are unrolled, so
+// the set is a compile-time property of (tap, tile, column half); the K loop is instantiated once per column half and the
+// wave-uniform c selects the instance once (k_loop below), so every tap is straight-line code; tile 5 (both halves) is
+// never in the set.  (Choosing between two bodies per TAP spilled 385 / 950 registers: every tap then ends in a join of
+// fragment sets of which only one side wrote the halo tiles'.)  Measured: profiles/r22/README.md.
+__host__ __device__ constexpr bool conv_halo_tile(int T, int kw, int nt)
+{
+    return 32 * nt + 31 + (kw - 6) * T < 0 || 32 * nt + (kw - 6) * T >= CV_PITCH;
+}
+
+#ifndef DMA3_SKIP
+#define DMA3_SKIP 1     // 0: every halo tile computed (for A/B timing; same results)
+#endif
+template <int T>
+__global__ __launch_bounds__(256, 1) void conv_f16x3_dma3_kernel(ConvF16Args a)
+{
+    constexpr int NCB = 4, NKH = CV_KH;
+    constexpr int PWP = CV_PITCH + 12 * T;            // patch positions per row (w = q - 6T)
+    static_assert(PWP % 16 == 0, "plane pitch: a multiple of 16 positions, so that every row is whole DMA pieces on bank 0");
+    constexpr int WSL = CV_KW * 64 * 16;
+    constexpr int PLANE = PWP * 16;                   // bytes of one (split, khalf) plane of a row
+    constexpr int W_SPLIT = 7 * 2048, W_BYTES = 2 * W_SPLIT;
+    constexpr int R_PIECES = 4 * PWP / 64;            // pieces of one patch row = 4 planes [split][khalf]: 28 / 34
+    constexpr int SLOT_BYTES = R_PIECES * 1024;
+    constexpr int RPW = (R_PIECES + 3) / 4;           //        per wave: 7 / 9
+    constexpr int RPA = RPW < 8 ? RPW : 8;            //        of them in phase A
+    static_assert(RPW >= 7 && RPW <= 9, "DMA schedule");
+    constexpr int SP_STRIDE = 2 * PLANE;              // bytes between the hi and lo images of a patch row
+    constexpr int W0_OFF = 0, W1_OFF = W_BYTES, P0_OFF = 2 * W_BYTES;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char *)smem;
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int row = wave >> 1, c = wave & 1, half = lane >> 5, l32 = lane & 31;
+    // XCD-contiguous (clip, row pair) tiles: see conv_f16x3_kernel
+    int tile_id = blockIdx.y * gridDim.x + blockIdx.x;
+    {
+        const int n_tiles = gridDim.x * gridDim.y;
+        if ((n_tiles & 7) == 0) tile_id = (tile_id & 7) * (n_tiles >> 3) + (tile_id >> 3);
+    }
+    const int b = tile_id / gridDim.x, h0 = (tile_id - b * gridDim.x) * 2;
+
+    floatx16 acc[CV_WT];
+#pragma unroll
+    for (int i = 0; i < CV_WT; ++i)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[i][r] = 0.0f;
+
+    // patch piece descriptors of one row: bit 31 = no source (halo column), bit 30 = split, low bits = byte offset of the
+    // slot's 16 bytes inside the operand row
+    int desc[RPW];
+#pragma unroll
+    for (int k = 0; k < RPW; ++k) {
+        const int i = (wave + 4 * k) * 64 + lane;
+        const int plane = i / PWP, pos = i - plane * PWP, w = pos - 6 * T;
+        const int split = plane >> 1, part = plane & 1;
+        desc[k] = (i < 4 * PWP && w >= 0 && w < CV_PITCH) ? ((split << 30) | (w * 32 + part * 16)) : -1;
+    }
+    const unsigned long long zero_src = (unsigned long long)k_zero_slot, xh = (unsigned long long)a.x_hi,
+                             xl = (unsigned long long)a.x_lo, wh = (unsigned long long)a.w_hi, wlo = (unsigned long long)a.w_lo;
+    const int H = a.H;
+
+    // DMA slots: issued unconditionally, address arithmetic apart from the issue (see conv_f16x3_dma_kernel)
+    struct DmaSlot { unsigned long long src; unsigned lds; };
+    auto slot_w = [&](int st, int t0, int nt, int woff, int j) {
+        const int pw = wave + 4 * j, per = 2 * nt;
+        const int split = pw / per, rem = pw - split * per;
+        DmaSlot d;
+        d.src = (split ? wlo : wh) + ((unsigned long long)st * WSL + (t0 * 2 + rem) * 512 + lane * 8) * 2;
+        d.lds = lds0 + woff + split * W_SPLIT + rem * 1024;
+        return d;
+    };
+    // piece k of input row j (= h0 - 2 + j) of channel block cb -> row slot j % 3; cb == NCB: zeros (no next stage);
+    // a wave without a piece k repeats its piece k - 1 (the same bytes to the same place)
+    auto slot_row = [&](int cb, int j, int k) {
+        const bool in_range = wave + 4 * k < R_PIECES;
+        const int pp = in_range ? wave + 4 * k : wave + 4 * (k - 1);
+        const int d = in_range ? desc[k] : desc[k > 0 ? k - 1 : 0];
+        const int hx = h0 + j - NKH / 2;
+        const bool v = hx >= 0 && hx < H && cb < NCB;
+        const long long st_off = (((long long)b * H + hx) * NCB + cb) * (CV_PITCH * 32);
+        const unsigned long long src = ((d & (1 << 30)) ? xl : xh) + st_off + (unsigned)(d & 0xFFFFF);
+        DmaSlot r;
+        r.src = (d >= 0 && v) ? src : zero_src;
+        r.lds = lds0 + P0_OFF + (j % 3) * SLOT_BYTES + pp * 1024;
+        return r;
+    };
+    auto slot_issue = [&](const DmaSlot &d) { glds16(d.src, d.lds); };
+    auto row_burst = [&](int cb, int j) {                    // a whole row at once
+#pragma unroll
+        for (int k = 0; k < RPW; ++k)
+            if (wave + 4 * k < R_PIECES) slot_issue(slot_row(cb, j, k));
+    };
+
+    // prologue: taps 0..6 of stage 0 and its two rows
+#pragma unroll
+    for (int j = 0; j < 7; ++j) slot_issue(slot_w(0, 0, 7, W0_OFF, j));
+    row_burst(0, 0);
+    row_burst(0, 1);
+    DMA_WAIT();
+    __syncthreads();
+
+    // The K loop for column half C (C < 0: no tile counts as halo), instantiated once per column half: the halo set is
+    // then a compile-time property of every tap's straight-line body, and the wave-uniform c selects the instance ONCE.
+    // Both instances execute the same sequence of workgroup barriers.
+    auto k_loop = [&](auto c_tag) __attribute__((always_inline)) {
+    constexpr int C = decltype(c_tag)::value;
+#pragma unroll 1
+    for (int cb = 0; cb < NCB; ++cb) {
+#pragma unroll 1
+        for (int kh = 0; kh < NKH; ++kh) {
+            const int s = cb * NKH + kh;
+            const bool more = s + 1 < NCB * NKH;
+            const int sn = more ? s + 1 : s;             // the stage whose weights the phase-B slots fetch (last stage: its own again, into the buffer nobody reads any more)
+            // the row fetched for the successor: its kernel row + 1, or row 0 when it opens a channel block (cbn == NCB: zeros)
+            const int cbn = kh + 1 < NKH ? cb : cb + 1, jn = kh + 1 < NKH ? kh + 2 : 0;
+            const unsigned char *const Pr = smem + P0_OFF + ((kh + row) % 3) * SLOT_BYTES;       // this wave's input row
+            const unsigned char *b_p = Pr + half * PLANE + (c * 6 * 32 + l32) * 16;              // + split*SP_STRIDE + (t*32 + kw*T)*16
+            const unsigned char *bm_p = Pr + half * PLANE + (5 * 32 + l32) * 16;                 // middle tile
+            // fragments of one tap, double buffered (FA: a0h a0l a1h a1l; FBH/FBL: tiles 0..4 + the middle tile)
+            half8 FA[2][4], FBH[2][6], FBL[2][6];
+            // column tile of the wave's patch fragment `tile` for column half C; C < 0: no tile counts as halo
+            auto halo = [&](int C, int kw, int tile) { return C >= 0 && conv_halo_tile(T, kw, tile < 5 ? C * 6 + tile : 5); };
+            // read r (0..15) of the tap (weights buffer at woff, local tap tl, kernel column kw) into fragment set f
+            auto rd = [&](int C, int f, int woff, int tl, int kw, int r) {
+                if (r < 4) {
+                    const int ch = (r >> 1) ? (c ^ 1) : c;
+                    FA[f][r] = *reinterpret_cast<const half8 *>(smem + woff + (r & 1) * W_SPLIT + (tl * 2 + half) * 1024 + (ch * 32 + l32) * 16);
+                } else {
+                    const int tile = (r - 4) >> 1, lo = (r - 4) & 1;
+                    if (halo(C, kw, tile)) return;
+                    const unsigned char *p = (tile < 5 ? b_p + tile * 32 * 16 : bm_p) + lo * SP_STRIDE + kw * T * 16;
+                    if (lo) FBL[f][tile] = *reinterpret_cast<const half8 *>(p);
+                    else FBH[f][tile] = *reinterpret_cast<const half8 *>(p);
+                }
+            };
+            // MFMA i (0..32) of tap kw: term (lo*hi, hi*lo, hi*hi) x 11 accumulators
+            auto mma = [&](int C, int f, int kw, int i) {
+                const int term = i / 11, u = i - term * 11;
+                const int tile = u < 10 ? (u >> 1) : 5, j = u < 10 ? (u & 1) : 0;
+                if (halo(C, kw, tile)) return;
+                const half8 av = FA[f][2 * j + (term == 0 ? 1 : 0)];
+                const half8 bv = term == 1 ? FBL[f][tile] : FBH[f][tile];
+                acc[u] = mfma16(av, bv, acc[u]);
+            };
+            // One tap for column half C: its MFMAs on set F, the next tap's fragment reads into set F^1 (r_lo..15), one read
+            // after every second MFMA, pinned, and two DMA slots (see conv_f16x3_dma_kernel)
+#define DMA3_TAP_C(C, F, WOFF, TLN, KW, KWN, R_LO, NA, SLOT_A, SLOT_A2, NB, SLOT_B, SLOT_B2)              \
+    {                                                                                                    \
+        __builtin_amdgcn_sched_barrier(0);                                                               \
+        const DmaSlot sa_ = SLOT_A, sa2_ = SLOT_A2;                                                      \
+        _Pragma("unroll") for (int i = 0; i < 16; ++i) mma(C, F, KW, i);                                 \
+        _Pragma("unroll") for (int r = 0; r < 8; ++r) if (r >= (R_LO)) rd(C, (F) ^ 1, WOFF, TLN, KWN, r); \
+        _Pragma("unroll") for (int g = 0; g < 8; ++g) {                                                  \
+            __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);                                           \
+            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);                                           \
+        }                                                                                                \
+        __builtin_amdgcn_sched_barrier(0);                                                               \
+        if ((NA) >= 1) slot_issue(sa_);                                                                  \
+        if ((NA) >= 2) slot_issue(sa2_);                                                                 \
+        __builtin_amdgcn_sched_barrier(0);                                                               \
+        const DmaSlot sb_ = SLOT_B, sb2_ = SLOT_B2;                                                      \
+        _Pragma("unroll") for (int i = 16; i < 33; ++i) mma(C, F, KW, i);                                \
+        _Pragma("unroll") for (int r = 8; r < 16; ++r) if (r >= (R_LO)) rd(C, (F) ^ 1, WOFF, TLN, KWN, r); \
+        _Pragma("unroll") for (int g = 0; g < 8; ++g) {                                                  \
+            __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);                                           \
+            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);                                           \
+        }                                                                                                \
+        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                                               \
+        __builtin_amdgcn_sched_barrier(0);                                                               \
+        if ((NB) >= 1) slot_issue(sb_);                                                                  \
+        if ((NB) >= 2) slot_issue(sb2_);                                                                 \
+        __builtin_amdgcn_sched_barrier(0);                                                               \
+    }
+#define DMA3_TAP(...) DMA3_TAP_C(C, __VA_ARGS__)
+#define DMA3_ROW(K) slot_row(cbn, jn, (K) < RPW ? (K) : RPW - 1)
+#define DMA3_NA(J) ((J) < 6 + RPA ? 1 : 0)
+#define DMA3_SLOT_A(J) ((J) < 6 ? slot_w(s, 7, 6, W1_OFF, (J)) : DMA3_ROW((J) - 6))
+#define DMA3_NB(J) (((J) < 7 ? 1 : 0) + ((J) + 8 < RPW ? 1 : 0))
+#define DMA3_SLOT_B(J) slot_w(sn, 0, 7, W0_OFF, (J) < 7 ? (J) : 0)
+#define DMA3_SLOT_B2(J) DMA3_ROW((J) + 8)
+
+            // ---- phase A: taps 0..6 from W0 (tap 0's fragments: all of them, halo tiles included -- once per stage)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) rd(-1, 0, W0_OFF, 0, 0, r);
+#pragma unroll
+            for (int t = 0; t < 7; ++t) {
+                if (t < 6) DMA3_TAP(t & 1, W0_OFF, t + 1, t, t + 1, 0, DMA3_NA(2 * t), DMA3_SLOT_A(2 * t), DMA3_SLOT_A(2 * t), DMA3_NA(2 * t + 1), DMA3_SLOT_A(2 * t + 1), DMA3_SLOT_A(2 * t + 1))
+                else DMA3_TAP(t & 1, W0_OFF, 0, t, 7, 4, DMA3_NA(2 * t), DMA3_SLOT_A(2 * t), DMA3_SLOT_A(2 * t), DMA3_NA(2 * t + 1), DMA3_SLOT_A(2 * t + 1), DMA3_SLOT_A(2 * t + 1))     // tap 7's patch fragments only
+            }
+            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(RPA) : "memory");     // this wave's W1 pieces landed (the row pieces behind them may be in flight) ...
+            __syncthreads();                                               // ... and everyone's did
+            // ---- phase B: taps 7..12 from W1 (fragment set 1 holds tap 7's patch fragments)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) rd(-1, 1, W1_OFF, 0, 7, r);
+#pragma unroll
+            for (int t = 0; t < 6; ++t) {
+                if (t < 5) DMA3_TAP((t + 1) & 1, W1_OFF, t + 1, 7 + t, 8 + t, 0, DMA3_NB(2 * t), DMA3_SLOT_B(2 * t), DMA3_SLOT_B2(2 * t), DMA3_NB(2 * t + 1), DMA3_SLOT_B(2 * t + 1), DMA3_SLOT_B2(2 * t + 1))
+                else DMA3_TAP((t + 1) & 1, W1_OFF, 0, 7 + t, 0, 16, DMA3_NB(2 * t), DMA3_SLOT_B(2 * t), DMA3_SLOT_B2(2 * t), DMA3_NB(2 * t + 1), DMA3_SLOT_B(2 * t + 1), DMA3_SLOT_B2(2 * t + 1))
+            }
+            DMA_WAIT();
+            __syncthreads();
+            if (kh + 1 == NKH && cb + 1 < NCB) {          // row 1 of the next channel block into the slot row 4 left
+                row_burst(cb + 1, 1);
+                DMA_WAIT();
+                __syncthreads();
+            }
+#undef DMA3_TAP_C
+#undef DMA3_TAP
+#undef DMA3_ROW
+#undef DMA3_NA
+#undef DMA3_SLOT_A
+#undef DMA3_NB
+#undef DMA3_SLOT_B
+#undef DMA3_SLOT_B2
+        }
+    }
+    };
+    if (!DMA3_SKIP) k_loop(std::integral_constant<int, -1>{});
+    else if (c == 0) k_loop(std::integral_constant<int, 0>{});
+    else k_loop(std::integral_constant<int, 1>{});
+    conv_f16_epilogue<0>(acc, a, smem, b, h0, row, c, lane);
+}
+
+template <int T>
+static int launch_f16_dma3(const ConvF16Args &a, int B, hipStream_t st)
+{
+    constexpr size_t lds = 2 * (2 * 7 * 2048) + 3 * (size_t)(4 * (CV_PITCH + 12 * T) / 64) * 1024;      // W[2] + three row slots
+    static_assert(lds <= 160 * 1024, "LDS budget");
+    static_assert(lds >= 96 * 1024, "the pooling epilogue's exchange area");
+    static MxLdsLatch latch = {};                             // per device (common.h)
+    if (mx_set_dyn_lds(latch, (const void *)conv_f16x3_dma3_kernel<T>, lds) != MX_OK) return MX_ERR_LAUNCH;
+    hipLaunchKernelGGL((conv_f16x3_dma3_kernel<T>), dim3(a.H / 2, B), dim3(256), lds, st, a);
+    return mx_launch_status();
+}
+
 template <int T>
 static int launch_f16_dma16(const ConvF16Args &a, int B, hipStream_t st)
 {
@@ -1469,8 +1734,8 @@ static int dispatch_f16(int T, int outmode, const ConvF16Args &a, int B, hipStre
         if (T == 1) return launch_f16_dma16<1>(a, B, st);
         if (T == 2) return launch_f16_dma16<2>(a, B, st);
         if (T == 4) return launch_f16_dma16<4>(a, B, st);
-        if (T == 8) return launch_f16<8, 0>(a, B, st);
-        if (T == 16) return launch_f16<16, 0>(a, B, st);
+        if (T == 8) return launch_f16_dma3<8>(a, B, st);
+        if (T == 16) return launch_f16_dma3<16>(a, B, st);
     } else {
         if (T == 1) return launch_f16_dma<1>(a, B, st);
         if (T == 2) return launch_f16_dma<2>(a, B, st);
@@ -1532,7 +1797,7 @@ MX_EXPORT int mx_conv_prep_dgrad_f16(const float *G, const uint8_t *amax, int64_
     return mx_launch_status();
 }
 
-// forward conv (64 -> 64 channels, dilation in {1,2,4}) from prepared operands
+// forward conv (64 -> 64 channels, dilation in {1,2,4,8,16}) from prepared operands
 MX_EXPORT int mx_conv_block_fwd_f16(const void *x_hi, const void *x_lo, const void *w_hi, const void *w_lo,
                                     const float *bias, int64_t B, int64_t H, int64_t Wv, int32_t dilation, float *out,
                                     uint8_t *out_amax, const float *slope_out, float *stats_part, void *stream)
