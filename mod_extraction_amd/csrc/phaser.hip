@@ -242,6 +242,7 @@ __global__ __launch_bounds__(PS_P) void phaser_scan_kernel(const float *__restri
             for (int r = 0; r < 7; ++r) m[c * 7 + r] = S[c][r];      // column c = image of unit state c
 #pragma unroll
         for (int r = 0; r < 7; ++r) m[49 + r] = S[7][r];
+        if constexpr (STASH) m[PS_MV - 1] = 0.0f;                // the pad float goes into the stash with the map
     }
     __syncthreads();
 
@@ -265,6 +266,25 @@ __global__ __launch_bounds__(PS_P) void phaser_scan_kernel(const float *__restri
     __syncthreads();
     if constexpr (STASH) {                                       // the chunk maps, as they lie in LDS
         for (int i = p; i < PS_P * PS_MV; i += PS_P) st.maps()[i] = mv[i];
+        // Every word of the row's ps_stash_floats(sg) that the scan does not write is zeroed, so a stash row never carries what
+        // its allocation held: the group records beyond the clip, this chunk's checkpoint slots without a group, and the
+        // checkpoints beyond the clip's own packing (the row is laid out for sg groups, the clip packs n_groups <= sg).
+        for (int g = n_groups + p; g < sg; g += PS_P) {
+            st.G()[g] = 0.0f;
+            st.pre()[g] = 0.0f;
+            st.osc()[g] = 0.0f;
+            st.pass()[g] = 0;
+        }
+        const float4 zero4 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        const int spc = (gpc + PS_SUB - 1) / PS_SUB;
+        for (int sub = (max(g1 - g0, 0) + PS_SUB - 1) / PS_SUB; sub < spc; ++sub) {
+            float4 *ck = st.ckpt(p, gpc, sub);
+            ck[0] = zero4;
+            ck[1] = zero4;
+        }
+        float4 *ck_all = st.ckpt(0, gpc, 0);
+        const long long ck_used = 2ll * PS_P * spc, ck_row = 2ll * PS_P * ps_ckpts_per_chunk(sg);
+        for (long long i = ck_used + p; i < ck_row; i += PS_P) ck_all[i] = zero4;
     }
 
     // ---- C: the chunk from its true start state, JUCE's operation order, output window

@@ -447,6 +447,56 @@ def test_lengths_around_the_tiling(dev, total):
           again=(st, W, recompute))
 
 
+@pytest.mark.parametrize("total,W", [(5, 10), (1000, 1000), (2049, 2049), (3000, 9001)])
+def test_stash_row_is_written_whole(dev, total, W):
+    """mx_phaser_fwd_stash defines every word of a stash row (csrc/phaser_common.h: ps_stash_floats(sg)), whatever the buffer
+    held: the group records beyond the clip's groups, the pad float of every chunk map, the checkpoint slots of chunks without
+    a group and those beyond the clip's own packing are zeros.  Clips shorter than their row (per-clip lead-ins below the
+    row's) leave most of the row to this rule; (3000, 9001) has 750 of 2252 groups and 2 of 5 groups per chunk in use."""
+    from mod_extraction_amd import fx
+    B = 3
+    leads = [total // 3, 0, total // 2]
+    n = total - max(leads)
+    params = {k: v[[9, 30, 46]] for k, v in grid_params().items()}
+    params["centre_frequency_hz"] = np.asarray([440.0, 1300.0, 5000.0], np.float32)
+    ngw = (W + 3) // 4
+    x = torch.tensor(audio_np(B, W, 90 + total, 0.9), device=dev)
+    mod = torch.tensor(np.stack([lfo_np(SHAPES[i], ngw, 40.0 * (i + 1), 0.5 * i) for i in range(B)]), device=dev)
+    p, lead_t = dev_params(dev, params), torch.tensor(leads, device=dev, dtype=torch.int32)
+    sg, row = fx.phaser_stash_shape(W)
+    got = []
+    for fill in (float("nan"), 7.0):
+        y, st = fx.phaser_forward_stash(x, p, lead_t, SR, n, mod=mod, stash=torch.full((B, row), fill, device=dev))
+        got.append((y.cpu(), st.cpu()))
+    assert not torch.isnan(got[0][1]).any()
+    assert torch.equal(got[0][0], got[1][0]) and torch.equal(got[0][1], got[1][1])
+    st = got[0][1].numpy()
+    P, MV = 512, 57                                                            # PS_P, PS_MV of csrc/phaser_common.h
+    for b in range(B):
+        n_groups = (leads[b] + n + 3) // 4
+        for section in range(4):
+            assert (st[b, section * sg + n_groups:(section + 1) * sg].view(np.int32) == 0).all(), (b, section)
+        maps = st[b, 4 * sg:4 * sg + P * MV].reshape(P, MV)
+        assert (maps[:, MV - 1].view(np.int32) == 0).all()
+        gpc = -(-n_groups // P)
+        spc = -(-gpc // 2)
+        ck = st[b, 4 * sg + P * MV:]
+        assert ck.size == P * 8 * (-(-(-(-sg // P)) // 2))
+        used = ck[:P * spc * 8].reshape(P, spc, 8)
+        for chunk in range(P):
+            g0 = min(chunk * gpc, n_groups)
+            live = -(-(min(g0 + gpc, n_groups) - g0) // 2)
+            assert (used[chunk, live:].view(np.int32) == 0).all(), (b, chunk)
+        assert (ck[P * spc * 8:].view(np.int32) == 0).all(), b
+    # the adjoint reads the same bits from either row
+    dy = torch.randn(B, n, device=dev, generator=torch.Generator(device=dev).manual_seed(total))
+    outs = []
+    for _, st_h in got:
+        dx, dmod, g = fx.phaser_backward(dy, x, st_h.to(dev), p, lead_t, SR, n)
+        outs.append([dx.cpu(), dmod.cpu()] + [g[k].cpu() for k in sorted(g)])
+    assert all(torch.equal(a, b) for a, b in zip(*outs))
+
+
 def test_fit_by_analysis_by_synthesis(dev):
     """End to end.  4 clips x 0.5 s of three partials (220 / 330 / 440 Hz), a phaser driven by a 2 Hz LFO built from torch
     ops at group rate, mod = (1 + sin(2 pi 2 t + phase)) / 2, the phase a learnable parameter.  Targets: feedback 0.5, depth
