@@ -268,8 +268,9 @@ class _EffectAudioLossFn(torch.autograd.Function):
         from .effect_losses import effect_loss_grad, effect_loss_terms
         mod = mod_sig_hat.detach().float().contiguous()
         wet_hat, stashes = step._render_rows(dry, mod, consts, stash=True)
-        rendered = wet_hat                        # what the adjoints (and the gain match's backward) read
-        if step.match_gain is not None:           # every row in one launch pair, dry rows included: the losses see the match
+        rendered = wet_hat                        # what the adjoints (and the gain / FIR match's backward) read
+        if step.match_gain is not None or step.match_fir is not None:
+            # every row in one launch sequence, dry rows included: the losses see the match
             wet_hat = step._match_rows(rendered, wet)
         a, t = wet_hat.unsqueeze(1), wet.unsqueeze(1)
         weighted: Dict[str, T] = {}
@@ -277,6 +278,10 @@ class _EffectAudioLossFn(torch.autograd.Function):
         if step.match_gain is not None:           # d loss / d z -> d loss / d (the un-matched render), in place
             from .gain import match_gain_backward
             match_gain_backward(dy, rendered, wet, step._gain, step.match_gain, step.match_gain_eps, out=dy)
+        if step.match_fir is not None:            # likewise, into a buffer of its own: a sample reads its neighbours' dz
+            from .fir_match import match_fir_backward
+            dy = match_fir_backward(dy, rendered, wet, step._fir, step.match_fir_ridge, step.match_fir_eps,
+                                    step.match_fir_centre)
         # the adjoints write (they do not add) the rows of their family, and the reduction reads only those: no zeros
         gbuf = torch.empty((6, dry.size(0)), device=dry.device, dtype=torch.float64) if params else None
         dmod = step._adjoint_rows(dy, dry, mod, consts, stashes, gbuf=gbuf)
@@ -391,6 +396,17 @@ class LFOExtractionThroughEffect(BaseLightingModule):
       un-matched render.  A training step logs ``gain/mean``, ``gain/std`` and ``gain/clamped`` (the share of clamped rows),
       ``data_dict["gain"]`` is the (B,) vector; ``render`` has no ``wet`` and stays un-matched.  Without it the step's
       launches are unchanged.  What a free gain trades off against: DESIGN section 7.
+    * ``match_fir`` (optional, not together with ``match_gain``): K in 1 .. 32 -- one K-tap least-squares FIR per clip, fitted
+      from the re-render onto ``wet`` before any loss sees it (``fir_match.match_fir``, K21), with the centre
+      ``match_fir_centre`` (None: (K - 1) // 2), ``match_fir_ridge``, ``match_fir_eps`` and the guard ``match_fir_max_gain`` on
+      sum |h|.  It absorbs what a recording chain adds to a wet: a level (K = 1 is the "ls" gain), a tone curve, and a lag
+      of a fraction of a sample.  It sits exactly where ``match_gain`` sits: all rows in one launch sequence before the
+      losses; the losses, the returned ``wet_hat`` and the logged terms are those of the matched rows; d loss / d z passes
+      through ``fir_match.match_fir_backward`` (into a buffer of its own) before the adjoints, which read the un-matched
+      render; ``render`` stays un-matched.  A training step logs ``fir/dc_gain`` (mean of sum_k h), ``fir/l1`` (mean of
+      sum |h|) and ``fir/flagged`` (the share of rows a guard gave the identity filter); ``data_dict["fir"]`` is the (B, K)
+      taps.  Without it the step's launches are unchanged.  What the match is not, and the identifiability limit on
+      K - 1 - centre: DESIGN section 7, "Tone and sub-sample lag of recorded pairs".
     * ``loss_dict`` (optional, default none): an LFO-domain term (lightning.py:33-62) added to the loss when the batch carries
       ``mod_sig``; it is logged as ``{prefix}/lfo_{name}``.
     The LFO enters the effect at the extractor's own rate (n_frames points, resampled in-kernel exactly as the data path
@@ -435,11 +451,29 @@ class LFOExtractionThroughEffect(BaseLightingModule):
                  fx_head=None,
                  match_gain: Optional[str] = None,
                  match_gain_eps: float = 1e-8,
-                 match_gain_range: Optional[Sequence[float]] = (0.05, 20.0)) -> None:
+                 match_gain_range: Optional[Sequence[float]] = (0.05, 20.0),
+                 match_fir: Optional[int] = None,
+                 match_fir_centre: Optional[int] = None,
+                 match_fir_ridge: float = 1e-6,
+                 match_fir_eps: float = 1e-8,
+                 match_fir_max_gain: float = 20.0) -> None:
         super().__init__({} if loss_dict is None else loss_dict)
         self._set_pre_emph(pre_emph_filter_cfs, pre_emph_low_pass)
         from . import fx
+        from .fir_match import check_fir
         from .gain import check_mode
+        # validated without match_fir too, as the gain's arguments are (a centre is checked against the taps it belongs to)
+        _, fir_centre, _, _, _ = check_fir(1 if match_fir is None else match_fir, None if match_fir is None else match_fir_centre,
+                                           match_fir_ridge, match_fir_eps, match_fir_max_gain, "match_fir")
+        if match_fir is None and match_fir_centre is not None and (
+                isinstance(match_fir_centre, bool) or not isinstance(match_fir_centre, int) or match_fir_centre < 0):
+            raise ValueError(f"match_fir: centre must be an integer in 0 .. taps - 1 (or None), got {match_fir_centre!r}")
+        if match_fir is not None and match_gain is not None:
+            raise ValueError("match_fir and match_gain are mutually exclusive: one tap of the FIR match is the ls gain")
+        self.match_fir = match_fir
+        self.match_fir_centre = fir_centre if match_fir is not None else match_fir_centre
+        self.match_fir_ridge, self.match_fir_eps, self.match_fir_max_gain = match_fir_ridge, match_fir_eps, match_fir_max_gain
+        self._fir = None                        # the fir_match.FirMatch of the last matched batch
         if isinstance(match_gain_range, list):  # a config file's spelling of the pair
             match_gain_range = tuple(match_gain_range)
         # eps and the range are validated without match_gain too: a typo does not wait for the day it is switched on
@@ -506,10 +540,18 @@ class LFOExtractionThroughEffect(BaseLightingModule):
             self.step_metric_names = [f"fx/{n}" for n in fx_head.names] + [f"fx_std/{n}" for n in fx_head.names]
         if match_gain is not None:
             self.step_metric_names = self.step_metric_names + ["gain/mean", "gain/std", "gain/clamped"]
+        if match_fir is not None:
+            self.step_metric_names = self.step_metric_names + ["fir/dc_gain", "fir/l1", "fir/flagged"]
 
     def _match_rows(self, rendered: T, wet: T) -> T:
-        """The rows of ``rendered`` brought to the level of ``wet`` (``gain.match_gain``: two launches for all rows); the
-        ``GainMatch`` is kept in ``_gain`` for the backward, the log and ``data_dict``."""
+        """The rows of ``rendered`` brought to the level of ``wet`` (``gain.match_gain``: two launches for all rows) or to its
+        level, tone and sub-sample lag (``fir_match.match_fir``: three); the ``GainMatch`` / ``FirMatch`` is kept in ``_gain``
+        / ``_fir`` for the backward, the log and ``data_dict``."""
+        if self.match_fir is not None:
+            from .fir_match import match_fir
+            self._fir = match_fir(rendered, wet, self.match_fir, self.match_fir_centre, self.match_fir_ridge,
+                                  self.match_fir_eps, self.match_fir_max_gain)
+            return self._fir.z
         from .gain import match_gain
         self._gain = match_gain(rendered, wet, self.match_gain, self.match_gain_eps, self.match_gain_range)
         return self._gain.z
@@ -803,7 +845,7 @@ class LFOExtractionThroughEffect(BaseLightingModule):
             wet_hat = wet_hat.unsqueeze(1)
         else:
             wet_hat, loss = self.render(dry, mod_sig_hat, fx_params, latent), None
-            if self.match_gain is not None:                         # validation: the terms below are taken on the matched rows
+            if self.match_gain is not None or self.match_fir is not None:   # validation: the terms below are taken on the matched rows
                 wet_hat = self._match_rows(wet_hat, wet)
         if prefix is not None or loss is None:
             with torch.no_grad():
@@ -872,12 +914,19 @@ class LFOExtractionThroughEffect(BaseLightingModule):
             self.log("gain/mean", g.mean())
             self.log("gain/std", g.std(unbiased=False))
             self.log("gain/clamped", self._gain.flags.float().mean())
+        if is_training and self.match_fir is not None:              # three (B, K) / (B,) device reductions: no host sync
+            h = self._fir.taps
+            self.log("fir/dc_gain", h.sum(1).mean())
+            self.log("fir/l1", h.abs().sum(1).mean())
+            self.log("fir/flagged", (self._fir.flags != 0).float().mean())
         data_dict = {"dry": dry.detach(), "wet": wet.detach(), "wet_hat": wet_hat.detach(),
                      "mod_sig_hat": mod_sig_hat.detach()}
         if self.fx_head is not None:
             data_dict["fx_values"] = self._fx_values
         if self.match_gain is not None:
             data_dict["gain"] = self._gain.gain
+        if self.match_fir is not None:
+            data_dict["fir"] = self._fir.taps
         if mod_sig is not None:
             data_dict["mod_sig"] = mod_sig.detach()
         return loss, data_dict, fx_params
