@@ -269,19 +269,23 @@ class _EffectAudioLossFn(torch.autograd.Function):
         mod = mod_sig_hat.detach().float().contiguous()
         wet_hat, stashes = step._render_rows(dry, mod, consts, stash=True)
         rendered = wet_hat                        # what the adjoints (and the gain / FIR match's backward) read
-        if step.match_gain is not None or step.match_fir is not None:
-            # every row in one launch sequence, dry rows included: the losses see the match
-            wet_hat = step._match_rows(rendered, wet)
-        a, t = wet_hat.unsqueeze(1), wet.unsqueeze(1)
         weighted: Dict[str, T] = {}
-        dy = effect_loss_grad(a, t, step.audio_loss_dict, values=weighted, **step._grad_modules())
-        if step.match_gain is not None:           # d loss / d z -> d loss / d (the un-matched render), in place
-            from .gain import match_gain_backward
-            match_gain_backward(dy, rendered, wet, step._gain, step.match_gain, step.match_gain_eps, out=dy)
-        if step.match_fir is not None:            # likewise, into a buffer of its own: a sample reads its neighbours' dz
-            from .fir_match import match_fir_backward
-            dy = match_fir_backward(dy, rendered, wet, step._fir, step.match_fir_ridge, step.match_fir_eps,
-                                    step.match_fir_centre)
+        P = step._warmup(dry.size(1))
+        if P:                                     # the warm-up window: match and losses on columns [P:], dy zero on [:P]
+            dy, wet_hat, a, t = _EffectAudioLossFn._windowed(step, rendered, wet, P, weighted)
+        else:
+            if step.match_gain is not None or step.match_fir is not None:
+                # every row in one launch sequence, dry rows included: the losses see the match
+                wet_hat = step._match_rows(rendered, wet)
+            a, t = wet_hat.unsqueeze(1), wet.unsqueeze(1)
+            dy = effect_loss_grad(a, t, step.audio_loss_dict, values=weighted, **step._grad_modules())
+            if step.match_gain is not None:       # d loss / d z -> d loss / d (the un-matched render), in place
+                from .gain import match_gain_backward
+                match_gain_backward(dy, rendered, wet, step._gain, step.match_gain, step.match_gain_eps, out=dy)
+            if step.match_fir is not None:        # likewise, into a buffer of its own: a sample reads its neighbours' dz
+                from .fir_match import match_fir_backward
+                dy = match_fir_backward(dy, rendered, wet, step._fir, step.match_fir_ridge, step.match_fir_eps,
+                                        step.match_fir_centre)
         # the adjoints write (they do not add) the rows of their family, and the reduction reads only those: no zeros
         gbuf = torch.empty((6, dry.size(0)), device=dry.device, dtype=torch.float64) if params else None
         dmod = step._adjoint_rows(dy, dry, mod, consts, stashes, gbuf=gbuf)
@@ -302,6 +306,35 @@ class _EffectAudioLossFn(torch.autograd.Function):
             terms.update({k: v for k, v in effect_loss_terms(a, t).items() if k in w})
         ctx.mark_non_differentiable(wet_hat)
         return step.weighted_sum(terms, step.audio_loss_dict), wet_hat
+
+    @staticmethod
+    def _windowed(step, rendered, wet, P, weighted):
+        """The match and the losses with a warm-up of P samples (``step.warmup_ms``): (d loss / d (the un-matched render) (B, N),
+        wet_hat (B, N), and the (B, 1, N - P) pair the losses saw).  The match, the losses and the match's backward work on
+        columns [P:] of every row -- views whose rows stay N floats apart, read in place -- and the gradient is zero on [:P].
+        wet_hat holds the matched rows on [P:] (the match writes them there) and the un-matched render on [:P].  Without a
+        match the loss kernels' dense (B, N - P) gradient is copied once into the (B, N) buffer the adjoints read."""
+        from .effect_losses import effect_loss_grad
+        seen, target = rendered[:, P:], wet[:, P:]
+        wet_hat = rendered
+        if step.match_gain is not None or step.match_fir is not None:
+            wet_hat = torch.empty_like(rendered)
+            wet_hat[:, :P] = rendered[:, :P]
+            step._match_rows(seen, target, out=wet_hat[:, P:])
+        a, t = wet_hat[:, P:].unsqueeze(1), target.unsqueeze(1)
+        dz = effect_loss_grad(a, t, step.audio_loss_dict, values=weighted, **step._grad_modules())
+        dy = torch.empty_like(rendered)
+        dy[:, :P] = 0.0
+        if step.match_gain is not None:
+            from .gain import match_gain_backward
+            match_gain_backward(dz, seen, target, step._gain, step.match_gain, step.match_gain_eps, out=dy[:, P:])
+        elif step.match_fir is not None:
+            from .fir_match import match_fir_backward
+            match_fir_backward(dz, seen, target, step._fir, step.match_fir_ridge, step.match_fir_eps, step.match_fir_centre,
+                               out=dy[:, P:])
+        else:
+            dy[:, P:] = dz
+        return dy, wet_hat, a, t
 
     @staticmethod
     def backward(ctx, g, _g_wet_hat):
@@ -407,6 +440,17 @@ class LFOExtractionThroughEffect(BaseLightingModule):
       sum |h|) and ``fir/flagged`` (the share of rows a guard gave the identity filter); ``data_dict["fir"]`` is the (B, K)
       taps.  Without it the step's launches are unchanged.  What the match is not, and the identifiability limit on
       K - 1 - centre: DESIGN section 7, "Tone and sub-sample lag of recorded pairs".
+    * ``warmup_ms`` (optional): a loss warm-up window of P = ``fx.delay_samples(warmup_ms, sr)`` samples for chunks cut from
+      the inside of a recording, whose ``wet`` had the samples before the chunk in its delay line or filter state while the
+      re-render starts empty.  The extractor sees the whole clip and every row is rendered over all N samples as before;
+      everything that compares with ``wet`` -- the gain / FIR match (partials, solve, apply, and its backward), the loss
+      gradients, the logged terms, validation -- works on columns [P:] of every row (views, rows N apart; the FIR's "zeros
+      outside" means outside the view).  d loss / d wet_hat is zero on [:P] and the adjoints run on all N samples of the
+      un-matched render, so LFO frames inside the warm-up get gradient only through what they leave in the effect's state.
+      ``wet_hat`` stays (B, 1, N): [P:] the matched rows, [:P] the un-matched render; ``data_dict["warmup"]`` = P.  A step
+      whose losses would see P samples or fewer raises a ``ValueError``.  One P per module; ``render`` is unchanged.  None,
+      or a value that gives P = 0, is the step without it.  How large P must be: DESIGN section 7, "Warm-up of a chunk cut
+      from a file".
     * ``loss_dict`` (optional, default none): an LFO-domain term (lightning.py:33-62) added to the loss when the batch carries
       ``mod_sig``; it is logged as ``{prefix}/lfo_{name}``.
     The LFO enters the effect at the extractor's own rate (n_frames points, resampled in-kernel exactly as the data path
@@ -416,9 +460,10 @@ class LFOExtractionThroughEffect(BaseLightingModule):
     ``model_smooth_n_frames`` > 1 applies the moving average (with its transpose in the backward) and centre-crops dry and
     wet by the rule of ``TBPTTLFOEffectModeling._prepare_all_rows``.  One limit of that crop: the re-render starts from an
     EMPTY delay line at the first cropped sample, whereas the recorded wet had the samples before the crop in its line, so
-    the first ``max_delay_samples`` samples of ``wet_hat`` differ from ``wet`` even for the true LFO.  The default is
-    therefore no smoothing.  The tremolo has no state, so this caveat does not apply to it: the re-render of a cropped
-    clip does not depend on the samples before the crop.
+    the first ``max_delay_samples`` samples of ``wet_hat`` differ from ``wet`` even for the true LFO (with feedback: longer).
+    ``warmup_ms`` leaves those samples out of every comparison; without it the default is therefore no smoothing.  The
+    tremolo has no state, so this caveat does not apply to it: the re-render of a cropped clip does not depend on the
+    samples before the crop.
 
     The phaser's lead-in rule: the step re-renders from ``dry`` ALONE, with lead 0 and empty filter state
     (``mx_phaser_fwd_stash`` on the LFO expanded by ``mx_phaser_mod_expand``).  The batch's ``wet`` was rendered by JUCE's
@@ -426,7 +471,8 @@ class LFOExtractionThroughEffect(BaseLightingModule):
     data path that lead exists to randomise the LFO's phase.  So at the true label the loss is small but NOT exactly 0, for
     three reasons: the start transient of the six all-passes and the feedback path; a cut-off-update grid shifted by
     ``lead % 4`` samples against the recorded one; and a label that is the sine linearly interpolated from
-    ``n_samples // 100`` points.  The same kind of caveat as the flanger's crop above.
+    ``n_samples // 100`` points.  The same kind of caveat as the flanger's crop above; ``warmup_ms`` removes the first of the
+    three from the comparison (the start transient), not the other two.
 
     ``should_stretch`` is not wired in (the corner stretch has a backward, but not on this path)."""
     default_audio_loss_dict = {"mrstft": 1.0}
@@ -456,10 +502,16 @@ class LFOExtractionThroughEffect(BaseLightingModule):
                  match_fir_centre: Optional[int] = None,
                  match_fir_ridge: float = 1e-6,
                  match_fir_eps: float = 1e-8,
-                 match_fir_max_gain: float = 20.0) -> None:
+                 match_fir_max_gain: float = 20.0,
+                 warmup_ms: Optional[float] = None) -> None:
         super().__init__({} if loss_dict is None else loss_dict)
         self._set_pre_emph(pre_emph_filter_cfs, pre_emph_low_pass)
         from . import fx
+        if warmup_ms is not None and (isinstance(warmup_ms, bool) or not isinstance(warmup_ms, (int, float))
+                                      or not 0.0 <= warmup_ms < float("inf")):
+            raise ValueError(f"warmup_ms must be None or a finite number >= 0, got {warmup_ms!r}")
+        self.warmup_ms = warmup_ms
+        self.warmup_samples = 0 if warmup_ms is None else fx.delay_samples(warmup_ms, sr)    # P; 0 = the step without it
         from .fir_match import check_fir
         from .gain import check_mode
         # validated without match_fir too, as the gain's arguments are (a centre is checked against the taps it belongs to)
@@ -543,18 +595,28 @@ class LFOExtractionThroughEffect(BaseLightingModule):
         if match_fir is not None:
             self.step_metric_names = self.step_metric_names + ["fir/dc_gain", "fir/l1", "fir/flagged"]
 
-    def _match_rows(self, rendered: T, wet: T) -> T:
+    def _match_rows(self, rendered: T, wet: T, out: Optional[T] = None) -> T:
         """The rows of ``rendered`` brought to the level of ``wet`` (``gain.match_gain``: two launches for all rows) or to its
         level, tone and sub-sample lag (``fir_match.match_fir``: three); the ``GainMatch`` / ``FirMatch`` is kept in ``_gain``
-        / ``_fir`` for the backward, the log and ``data_dict``."""
+        / ``_fir`` for the backward, the log and ``data_dict``.  ``out``: where the matched rows go (the warm-up window: a view
+        of the step's wet_hat)."""
         if self.match_fir is not None:
             from .fir_match import match_fir
             self._fir = match_fir(rendered, wet, self.match_fir, self.match_fir_centre, self.match_fir_ridge,
-                                  self.match_fir_eps, self.match_fir_max_gain)
+                                  self.match_fir_eps, self.match_fir_max_gain, **({} if out is None else {"out": out}))
             return self._fir.z
         from .gain import match_gain
-        self._gain = match_gain(rendered, wet, self.match_gain, self.match_gain_eps, self.match_gain_range)
+        self._gain = match_gain(rendered, wet, self.match_gain, self.match_gain_eps, self.match_gain_range,
+                                **({} if out is None else {"out": out}))
         return self._gain.z
+
+    def _warmup(self, n: int) -> int:
+        """P, the samples every comparison with ``wet`` leaves out, for rows of ``n`` samples (after the smoothing crop), or the
+        ValueError when nothing would be left."""
+        if self.warmup_samples >= n:
+            raise ValueError(f"warmup_ms = {self.warmup_ms} is {self.warmup_samples} samples, and the losses see rows of {n}: "
+                             "nothing is left to compare")
+        return self.warmup_samples
 
     @property
     def _fxp(self):
@@ -832,6 +894,7 @@ class LFOExtractionThroughEffect(BaseLightingModule):
         otherwise nothing is stashed and no backward kernel runs.  ``prefix``: log every audio term under it."""
         from .effect_losses import effect_loss_terms
         dry_r, wet_r = self._rows(dry), self._rows(wet)
+        P = self._warmup(dry_r.size(1))                             # its ValueError, before any launch
         terms: Dict[str, T] = {}
         head = self.fx_head
         if head is not None and latent is None:
@@ -846,15 +909,21 @@ class LFOExtractionThroughEffect(BaseLightingModule):
         else:
             wet_hat, loss = self.render(dry, mod_sig_hat, fx_params, latent), None
             if self.match_gain is not None or self.match_fir is not None:   # validation: the terms below are taken on the matched rows
-                wet_hat = self._match_rows(wet_hat, wet)
+                if P:                                               # matched on the window, into [P:] of a (B, 1, N) buffer
+                    rendered, wet_hat = wet_hat, torch.empty_like(wet_hat)
+                    wet_hat[..., :P] = rendered[..., :P]
+                    self._match_rows(rendered[..., P:], wet[..., P:], out=wet_hat[..., P:])
+                else:
+                    wet_hat = self._match_rows(wet_hat, wet)
         if prefix is not None or loss is None:
             with torch.no_grad():
                 missing = [k for k in self.audio_loss_dict if k not in terms]
+                seen, target = (wet_hat[..., P:], wet[..., P:]) if P else (wet_hat, wet)    # what the losses compare
                 if any(k in ("l1", "mse", "esr", "dc") for k in missing):
-                    terms.update({k: v for k, v in effect_loss_terms(wet_hat, wet).items() if k in missing})
+                    terms.update({k: v for k, v in effect_loss_terms(seen, target).items() if k in missing})
                 for k in missing:
                     if k not in terms:
-                        terms[k] = self._loss_module(k)(wet_hat, wet)
+                        terms[k] = self._loss_module(k)(seen, target)
             if loss is None:
                 loss = self.weighted_sum(terms, self.audio_loss_dict)
             if prefix is not None:
@@ -927,6 +996,8 @@ class LFOExtractionThroughEffect(BaseLightingModule):
             data_dict["gain"] = self._gain.gain
         if self.match_fir is not None:
             data_dict["fir"] = self._fir.taps
+        if self.warmup_samples:
+            data_dict["warmup"] = self.warmup_samples
         if mod_sig is not None:
             data_dict["mod_sig"] = mod_sig.detach()
         return loss, data_dict, fx_params

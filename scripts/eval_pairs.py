@@ -1,0 +1,74 @@
+#!/usr/bin/env python3
+"""Score a trained effect-rendered step on whole recordings: one JSON line per dry / wet file pair.
+
+    python eval_pairs.py --config ../configs/train_lfo_pairs_flanger_fir.yml --ckpt run.ckpt --dry_dir DRY --wet_dir WET
+
+The config's ``model`` must be a ``lightning.LFOExtractionThroughEffect`` (without ``fx_head``); its ``data`` section supplies
+``n_samples``, ``sr`` and -- when ``align_max_lag_ms`` is there -- the alignment settings.  Files are paired as
+``datasets.RandomAudioChunkDryWetDataset`` pairs them (same name in both directories, same rate, channels and length within
+``end_buffer_n_samples``); with ``align_max_lag_ms`` its ``estimate_alignment`` table gives every pair's lag and polarity.
+Per pair ``file_eval.score_pair`` runs on channel 0 of the whole file: the extractor's LFO track, the rate and shape fitted
+to it, the re-render from the file's first sample, ONE gain or FIR for the file, and the step's audio losses.
+"""
+import argparse
+import json
+import os
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+from mod_extraction_amd import cli, datasets, file_eval, lightning, modulations  # noqa: E402
+
+
+def main() -> int:
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--config", "-c", required=True)
+    ap.add_argument("--ckpt", required=True, help="Lightning .ckpt or a bare .pt state dict (cli.load_weights)")
+    ap.add_argument("--dry_dir", required=True)
+    ap.add_argument("--wet_dir", required=True)
+    ap.add_argument("--hop", type=int, default=None, help="hop of the extractor's windows in samples (default n_samples // 2)")
+    ap.add_argument("--batch_size", type=int, default=32)
+    ap.add_argument("--device", default="cuda:0")
+    a = ap.parse_args()
+    cfg = cli.apply_links(cli.load_config(a.config))
+    dev = torch.device(a.device)
+    step = cli.instantiate(cfg["model"]).to(dev)
+    if not isinstance(step, lightning.LFOExtractionThroughEffect):
+        raise SystemExit(f"the config's model is a {type(step).__name__}: eval_pairs scores an LFOExtractionThroughEffect")
+    cli.load_weights(step, a.ckpt)
+    step.eval()
+    data = dict((cfg.get("data") or {}).get("init_args") or {})
+    n_samples, sr = int(data.get("n_samples", 88200)), float(data.get("sr", step.sr))
+    ds = datasets.RandomAudioChunkDryWetDataset(
+        a.dry_dir, a.wet_dir, n_samples, sr, check_dataset=False, end_buffer_n_samples=int(data.get("end_buffer_n_samples", 0)),
+        align_max_lag_ms=data.get("align_max_lag_ms"), align_n_probes=int(data.get("align_n_probes", 8)),
+        align_min_corr=float(data.get("align_min_corr", 0.5)))
+    table = ds.estimate_alignment(dev) if ds.align_max_lag is not None else {}
+    for dry_path in ds.dry_paths:
+        name = os.path.basename(dry_path)
+        dry, wet = datasets.wav_load(dry_path)[0][0], datasets.wav_load(ds.name_to_wet_path[name])[0][0]
+        n = min(dry.numel(), wet.numel())
+        row = {"file": name, "samples": n}
+        if n < n_samples:
+            row["skipped"] = f"shorter than one window of {n_samples} samples"
+            print(json.dumps(row), flush=True)
+            continue
+        al = table.get(name)
+        lag, polarity = (al.lag, al.polarity) if al is not None else (0, 1)
+        out = file_eval.score_pair(step, step.model, dry[:n].to(dev), wet[:n].to(dev), lag=lag, polarity=polarity, hop=a.hop,
+                                   n_samples=n_samples, batch_size=a.batch_size)
+        row.update(lag=lag, polarity=polarity, aligned=bool(al.ok) if al is not None else None,
+                   n_windows=out["n_windows"], fit_points=out["fit_points"], track_points=int(out["track"].numel()),
+                   rate_hz=float(out["rate_hz"]), shape=modulations.SHAPE_NAMES[int(out["shape"])], resid=float(out["resid"]))
+        row.update({k: float(out[k]) for k in step.audio_loss_dict})
+        if "fir" in out:
+            row["fir"] = [float(v) for v in out["fir"]]
+        if "gain" in out:
+            row["gain"] = float(out["gain"])
+        print(json.dumps(row), flush=True)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
