@@ -1,5 +1,4 @@
-"""ctypes binding of libmodex_hip.so (the C ABI declared in include/modex_hip.h and, for the six K21 entry points, in
-include/modex_hip_fir.h, for the K22 entry point in include/modex_hip_file.h; the argtypes are derived from those texts).
+"""ctypes binding of libmodex_hip.so (the C ABI declared in include/modex_hip.h; the argtypes are derived from its text).
 
 No fallback: if the shared library is missing, or a call returns a non-zero status, this raises.
 Device pointers are borrowed from torch tensors; launches go to torch's current HIP stream.
@@ -20,11 +19,6 @@ _ERR = {-1: "MX_ERR_ARG (bad argument)", -2: "MX_ERR_UNSUPPORTED (size not suppo
         -3: "MX_ERR_LAUNCH (HIP launch error)"}
 
 HEADER = os.path.join(_HERE, "..", "include", "modex_hip.h")      # where build.py finds it too
-# The second header: the K21 entry points.  It exists only because the declaration count of the first and the ABI number
-# were pinned when K21 was added; folding it back is the follow-up (parse_signatures(text1 + text2) already succeeds).
-HEADER_FIR = os.path.join(_HERE, "..", "include", "modex_hip_fir.h")
-# The third header, for the same reason: the K22 entry point (the first header's count and the second's six names are pinned).
-HEADER_FILE = os.path.join(_HERE, "..", "include", "modex_hip_file.h")
 
 # the parameter kinds of the C ABI: any pointer, and these six scalars (modex_hip.h states the rule)
 _SCALARS = {"int64_t": ctypes.c_int64, "int32_t": ctypes.c_int32, "uint64_t": ctypes.c_uint64, "uint32_t": ctypes.c_uint32,
@@ -74,9 +68,6 @@ def _header_text(path: Optional[str] = None) -> str:
 
 # name -> argtypes of every entry point, derived from include/modex_hip.h (the definitions are compiled against the same text)
 SIGNATURES = parse_signatures(_header_text())
-# likewise for include/modex_hip_fir.h; the ABI number does not cover these, so load() names a symbol that a stale build lacks
-SIGNATURES_FIR = parse_signatures(_header_text(HEADER_FIR))
-SIGNATURES_FILE = parse_signatures(_header_text(HEADER_FILE))       # include/modex_hip_file.h, under the same rule
 
 # measurement twins (same signatures): the dependent chain of the sample-recurrent kernels without global traffic
 PROBE_TWINS = ("mx_flanger_fwd", "mx_phaser_fwd", "mx_lstm_fwd", "mx_lstm_bwd_l1")
@@ -92,21 +83,15 @@ def load() -> ctypes.CDLL:
                 f"{SO_PATH} not found: build it with `python -m mod_extraction_amd.build` "
                 "(there is no CPU fallback)")
         lib = ctypes.CDLL(SO_PATH)
-        for name, argtypes in SIGNATURES.items():
-            fn = getattr(lib, name)          # AttributeError if the .so lacks a declared symbol
+        for name, argtypes in SIGNATURES.items():           # read as a module attribute here, at call time
+            fn = getattr(lib, name, None)
+            if fn is None:                  # the ABI number does not cover an added entry point: name what a stale build lacks
+                raise HipLibraryError(f"{SO_PATH} has no symbol {name} (declared in include/modex_hip.h): a stale build; "
+                                      "rebuild it with `python -m mod_extraction_amd.build`")
             fn.argtypes = argtypes
             fn.restype = ctypes.c_int
         if lib.mx_abi_version() != ABI_VERSION:
             raise HipLibraryError(f"ABI mismatch: library {lib.mx_abi_version()} != binding {ABI_VERSION}")
-        # both tables are read as module attributes here, at call time
-        for header, table in (("modex_hip_fir.h", SIGNATURES_FIR), ("modex_hip_file.h", SIGNATURES_FILE)):
-            for name, argtypes in table.items():
-                fn = getattr(lib, name, None)
-                if fn is None:
-                    raise HipLibraryError(f"{SO_PATH} has no symbol {name} (declared in include/{header}): a stale build; "
-                                          "rebuild it with `python -m mod_extraction_amd.build`")
-                fn.argtypes = argtypes
-                fn.restype = ctypes.c_int
         _lib = lib
     return _lib
 

@@ -18,7 +18,7 @@ SRC = os.path.join(HERE, "csrc")
 OUT_DIR = os.path.join(HERE, "_lib")
 OBJ_DIR = os.path.join(OUT_DIR, "obj")
 SO = os.path.join(OUT_DIR, "libmodex_hip.so")
-INCLUDE = os.path.join(HERE, "..", "include")       # the public headers (modex_hip.h, modex_hip_fir.h, modex_hip_file.h); csrc/common.h includes all three
+INCLUDE = os.path.join(HERE, "..", "include")       # the public header, modex_hip.h; csrc/common.h includes it
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
          "-fvisibility=hidden", "-Wall", "-Wno-unused-function", "-I", INCLUDE]
@@ -42,7 +42,7 @@ def sources():
 
 def build(force: bool = False, verbose: bool = True) -> str:
     os.makedirs(OBJ_DIR, exist_ok=True)
-    # every .h of csrc/ and of include/ (all three public headers): a change to any of them rebuilds every object
+    # every .h of csrc/ and of include/: a change to any of them rebuilds every object
     headers = [os.path.join(d, f) for d in (SRC, INCLUDE) for f in os.listdir(d) if f.endswith(".h")]
     hdr_time = max([os.path.getmtime(h) for h in headers] + [0.0])
     jobs = []

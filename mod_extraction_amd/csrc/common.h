@@ -7,8 +7,6 @@
 // The public header: MX_OK / MX_ERR_*, and the declaration of every entry point, so that an MX_EXPORT definition which
 // differs from its declaration is a compile error ("conflicting types") in whichever translation unit defines it.
 #include "modex_hip.h"
-#include "modex_hip_fir.h"      // the six K21 declarations: a header of their own until they are folded back into the first
-#include "modex_hip_file.h"     // likewise the K22 declaration
 
 #define MX_EXPORT extern "C" __attribute__((visibility("default")))
 

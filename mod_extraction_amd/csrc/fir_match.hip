@@ -1,5 +1,5 @@
 // fir_match.hip -- K21: one short least-squares FIR per clip that carries a rendered wet (y_hat = x) onto a recorded one (y),
-// forward and backward -- no counterpart in the reference (include/modex_hip_fir.h has the definition).
+// forward and backward -- no counterpart in the reference (include/modex_hip.h, K21, has the definition).
 //
 //     R[d] = sum_n x[n] x[n + d],  b[j] = sum_n x[n + c - j] y[n],  E = sum_n y[n]^2;   A = toeplitz(R) + (eps + ridge R[0]) I
 //     h = A^-1 b (fp64 Cholesky), rounded once;   z[n] = sum_k h[k] x[n + c - k]
@@ -24,9 +24,9 @@
 //     worth a (B, K, K) buffer), u by the same two solves, s by one lag per lane.
 // fm_apply_kernel, fm_bwd_apply_kernel   thread t forms samples t, t + 256, .. of the chunk in fp64 from LDS (consecutive
 //     lanes, consecutive banks), rounds once into an LDS row of results, and the workgroup stores that row as a scalar head up
-//     to the first 16-byte boundary of the output, float4s, and a scalar tail (gm_span's rule).  Coefficients are read from
+//     to the first 16-byte boundary of the output, float4s, and a scalar tail (rows_span's rule). Coefficients are read from
 //     LDS at one address a wave (a broadcast); one that is exactly 0 is skipped, so the identity filter copies.
-#include "common.h"
+#include "rows_common.h"
 
 #define FM_THREADS 256
 #define FM_CHUNK MX_FIR_CHUNK
@@ -208,23 +208,11 @@ __global__ __launch_bounds__(MX_WAVE) void fm_bwd_solve_kernel(
     }
 }
 
-// the part of a row one workgroup owns, split by the alignment of the output pointer (gain_match.hip's gm_span)
-struct FmSpan { int head, nvec, tail; };
-__device__ __forceinline__ FmSpan fm_span(const float *lead, int len)
-{
-    FmSpan s;
-    int head = (int)(((16u - (unsigned)((uintptr_t)lead & 15u)) & 15u) >> 2);   // floats before the first 16-byte boundary
-    s.head = head < len ? head : len;
-    s.nvec = (len - s.head) >> 2;
-    s.tail = len - s.head - 4 * s.nvec;
-    return s;
-}
-
 // o[0 : len] = res[0 : len] (LDS, 16-byte aligned): scalar head, float4s, scalar tail
 __device__ __forceinline__ void fm_store(float *o, const float *res, int len)
 {
     const int tid = (int)threadIdx.x;
-    const FmSpan sp = fm_span(o, len);
+    const RowsSpan sp = rows_span(o, len);
     if (tid < sp.head) o[tid] = res[tid];
     float4 *ov = reinterpret_cast<float4 *>(o + sp.head);
     for (int i = tid; i < sp.nvec; i += FM_THREADS) {
@@ -300,11 +288,6 @@ __global__ __launch_bounds__(FM_THREADS) void fm_bwd_apply_kernel(
 }
 
 // C ABI ---------------------------------------------------------------------------------------
-static int fm_check_rows(const void *p, int64_t stride, int64_t B, int64_t N)
-{
-    return (!p || B < 1 || N < 1 || stride < N) ? MX_ERR_ARG : MX_OK;
-}
-
 // K, then the centre, then the sizes
 static int fm_check_dims(int64_t B, int64_t N, int64_t K, int64_t centre, bool has_centre)
 {
@@ -316,27 +299,6 @@ static int fm_check_dims(int64_t B, int64_t N, int64_t K, int64_t centre, bool h
 static bool fm_bad_ridge_eps(double ridge, double eps)
 {
     return !(ridge >= 0.0) || !(ridge < 1e300) || !(eps > 0.0) || !(eps < 1e300);
-}
-
-struct FmRange { uintptr_t lo, hi; };
-static FmRange fm_rows(const void *p, int64_t stride, int64_t B, int64_t N)      // B rows of N floats, first to last byte
-{
-    return {(uintptr_t)p, (uintptr_t)p + 4 * (uintptr_t)((B - 1) * stride + N)};
-}
-static FmRange fm_flat(const void *p, int64_t count, int64_t elem)
-{
-    return {(uintptr_t)p, (uintptr_t)p + (uintptr_t)(count * elem)};
-}
-// does one of the n_out output ranges share a byte with another output or with one of the n_in input ranges?
-static bool fm_overlap(const FmRange *out, int n_out, const FmRange *in, int n_in)
-{
-    for (int i = 0; i < n_out; ++i) {
-        for (int j = i + 1; j < n_out; ++j)
-            if (out[i].lo < out[j].hi && out[j].lo < out[i].hi) return true;
-        for (int j = 0; j < n_in; ++j)
-            if (out[i].lo < in[j].hi && in[j].lo < out[i].hi) return true;
-    }
-    return false;
 }
 
 static int64_t fm_chunks(int64_t N)
@@ -352,11 +314,11 @@ static dim3 fm_grid(int64_t B, int64_t N)
 MX_EXPORT int mx_fir_match_partials(const float *y_hat, int64_t y_hat_stride, const float *y, int64_t y_stride, int64_t B,
                                     int64_t N, int64_t K, int64_t centre, double *partials, void *stream)
 {
-    if (!partials || fm_check_rows(y_hat, y_hat_stride, B, N) || fm_check_rows(y, y_stride, B, N)) return MX_ERR_ARG;
+    if (!partials || rows_check(y_hat, y_hat_stride, B, N) || rows_check(y, y_stride, B, N)) return MX_ERR_ARG;
     if (const int rc = fm_check_dims(B, N, K, centre, true)) return rc;
-    const FmRange out[1] = {fm_flat(partials, B * fm_chunks(N) * (2 * K + 1), 8)};
-    const FmRange in[2] = {fm_rows(y_hat, y_hat_stride, B, N), fm_rows(y, y_stride, B, N)};
-    if (fm_overlap(out, 1, in, 2)) return MX_ERR_ARG;
+    const RowsRange out[1] = {rows_flat(partials, B * fm_chunks(N) * (2 * K + 1), 8)};
+    const RowsRange in[2] = {rows_range(y_hat, y_hat_stride, B, N), rows_range(y, y_stride, B, N)};
+    if (rows_any_overlap(out, 1, in, 2)) return MX_ERR_ARG;
     hipLaunchKernelGGL(fm_partials_kernel<true>, fm_grid(B, N), dim3(FM_THREADS), 0, (hipStream_t)stream, y_hat,
                        (long long)y_hat_stride, y, (long long)y_stride, (int)N, (int)K, (int)centre, partials);
     return mx_launch_status();
@@ -369,9 +331,9 @@ MX_EXPORT int mx_fir_match_solve(const double *partials, int64_t B, int64_t n_ch
     if (const int rc = fm_check_dims(B, n_chunks, K, centre, true)) return rc;
     if (n_chunks > fm_chunks(FM_MAX_N)) return MX_ERR_UNSUPPORTED;
     if (fm_bad_ridge_eps(ridge, eps) || !(max_gain >= 1.0) || !(max_gain < 1e300)) return MX_ERR_ARG;
-    const FmRange out[3] = {fm_flat(taps, B * K, 4), fm_flat(sums, B * (2 * K + 1), 8), fm_flat(flags, B, 4)};
-    const FmRange in[1] = {fm_flat(partials, B * n_chunks * (2 * K + 1), 8)};
-    if (fm_overlap(out, 3, in, 1)) return MX_ERR_ARG;
+    const RowsRange out[3] = {rows_flat(taps, B * K, 4), rows_flat(sums, B * (2 * K + 1), 8), rows_flat(flags, B, 4)};
+    const RowsRange in[1] = {rows_flat(partials, B * n_chunks * (2 * K + 1), 8)};
+    if (rows_any_overlap(out, 3, in, 1)) return MX_ERR_ARG;
     hipLaunchKernelGGL(fm_solve_kernel, dim3((unsigned)B), dim3(MX_WAVE), 0, (hipStream_t)stream, partials, (int)n_chunks,
                        (int)K, (int)centre, ridge, eps, max_gain, taps, sums, (int *)flags);
     return mx_launch_status();
@@ -380,11 +342,11 @@ MX_EXPORT int mx_fir_match_solve(const double *partials, int64_t B, int64_t n_ch
 MX_EXPORT int mx_fir_match_apply(const float *x, int64_t x_stride, const float *taps, int64_t B, int64_t N, int64_t K,
                                  int64_t centre, float *z, int64_t z_stride, void *stream)
 {
-    if (!taps || fm_check_rows(x, x_stride, B, N) || fm_check_rows(z, z_stride, B, N)) return MX_ERR_ARG;
+    if (!taps || rows_check(x, x_stride, B, N) || rows_check(z, z_stride, B, N)) return MX_ERR_ARG;
     if (const int rc = fm_check_dims(B, N, K, centre, true)) return rc;
-    const FmRange out[1] = {fm_rows(z, z_stride, B, N)};
-    const FmRange in[2] = {fm_rows(x, x_stride, B, N), fm_flat(taps, B * K, 4)};
-    if (fm_overlap(out, 1, in, 2)) return MX_ERR_ARG;
+    const RowsRange out[1] = {rows_range(z, z_stride, B, N)};
+    const RowsRange in[2] = {rows_range(x, x_stride, B, N), rows_flat(taps, B * K, 4)};
+    if (rows_any_overlap(out, 1, in, 2)) return MX_ERR_ARG;
     hipLaunchKernelGGL(fm_apply_kernel, fm_grid(B, N), dim3(FM_THREADS), 0, (hipStream_t)stream, x, (long long)x_stride, taps,
                        (int)N, (int)K, (int)centre, z, (long long)z_stride);
     return mx_launch_status();
@@ -393,11 +355,11 @@ MX_EXPORT int mx_fir_match_apply(const float *x, int64_t x_stride, const float *
 MX_EXPORT int mx_fir_match_bwd_partials(const float *dz, int64_t dz_stride, const float *y_hat, int64_t y_hat_stride,
                                         int64_t B, int64_t N, int64_t K, int64_t centre, double *partials, void *stream)
 {
-    if (!partials || fm_check_rows(dz, dz_stride, B, N) || fm_check_rows(y_hat, y_hat_stride, B, N)) return MX_ERR_ARG;
+    if (!partials || rows_check(dz, dz_stride, B, N) || rows_check(y_hat, y_hat_stride, B, N)) return MX_ERR_ARG;
     if (const int rc = fm_check_dims(B, N, K, centre, true)) return rc;
-    const FmRange out[1] = {fm_flat(partials, B * fm_chunks(N) * K, 8)};
-    const FmRange in[2] = {fm_rows(dz, dz_stride, B, N), fm_rows(y_hat, y_hat_stride, B, N)};
-    if (fm_overlap(out, 1, in, 2)) return MX_ERR_ARG;
+    const RowsRange out[1] = {rows_flat(partials, B * fm_chunks(N) * K, 8)};
+    const RowsRange in[2] = {rows_range(dz, dz_stride, B, N), rows_range(y_hat, y_hat_stride, B, N)};
+    if (rows_any_overlap(out, 1, in, 2)) return MX_ERR_ARG;
     hipLaunchKernelGGL(fm_partials_kernel<false>, fm_grid(B, N), dim3(FM_THREADS), 0, (hipStream_t)stream, y_hat,
                        (long long)y_hat_stride, dz, (long long)dz_stride, (int)N, (int)K, (int)centre, partials);
     return mx_launch_status();
@@ -411,10 +373,10 @@ MX_EXPORT int mx_fir_match_bwd_solve(const double *partials, const double *sums,
     if (const int rc = fm_check_dims(B, n_chunks, K, 0, false)) return rc;
     if (n_chunks > fm_chunks(FM_MAX_N)) return MX_ERR_UNSUPPORTED;
     if (fm_bad_ridge_eps(ridge, eps)) return MX_ERR_ARG;
-    const FmRange out[2] = {fm_flat(u, B * K, 8), fm_flat(s, B * (2 * K - 1), 8)};
-    const FmRange in[4] = {fm_flat(partials, B * n_chunks * K, 8), fm_flat(sums, B * (2 * K + 1), 8), fm_flat(taps, B * K, 4),
-                           fm_flat(flags, B, 4)};
-    if (fm_overlap(out, 2, in, 4)) return MX_ERR_ARG;
+    const RowsRange out[2] = {rows_flat(u, B * K, 8), rows_flat(s, B * (2 * K - 1), 8)};
+    const RowsRange in[4] = {rows_flat(partials, B * n_chunks * K, 8), rows_flat(sums, B * (2 * K + 1), 8),
+                             rows_flat(taps, B * K, 4), rows_flat(flags, B, 4)};
+    if (rows_any_overlap(out, 2, in, 4)) return MX_ERR_ARG;
     hipLaunchKernelGGL(fm_bwd_solve_kernel, dim3((unsigned)B), dim3(MX_WAVE), 0, (hipStream_t)stream, partials, sums, taps,
                        (const int *)flags, (int)n_chunks, (int)K, ridge, eps, u, s);
     return mx_launch_status();
@@ -424,14 +386,15 @@ MX_EXPORT int mx_fir_match_bwd_apply(const float *dz, int64_t dz_stride, const f
                                      int64_t y_hat_stride, const float *taps, const double *u, const double *s, int64_t B,
                                      int64_t N, int64_t K, int64_t centre, float *dy_hat, int64_t dy_hat_stride, void *stream)
 {
-    if (!taps || !u || !s || fm_check_rows(dz, dz_stride, B, N) || fm_check_rows(y, y_stride, B, N)
-        || fm_check_rows(y_hat, y_hat_stride, B, N) || fm_check_rows(dy_hat, dy_hat_stride, B, N))
+    if (!taps || !u || !s || rows_check(dz, dz_stride, B, N) || rows_check(y, y_stride, B, N)
+        || rows_check(y_hat, y_hat_stride, B, N) || rows_check(dy_hat, dy_hat_stride, B, N))
         return MX_ERR_ARG;
     if (const int rc = fm_check_dims(B, N, K, centre, true)) return rc;
-    const FmRange out[1] = {fm_rows(dy_hat, dy_hat_stride, B, N)};
-    const FmRange in[6] = {fm_rows(dz, dz_stride, B, N), fm_rows(y, y_stride, B, N), fm_rows(y_hat, y_hat_stride, B, N),
-                           fm_flat(taps, B * K, 4), fm_flat(u, B * K, 8), fm_flat(s, B * (2 * K - 1), 8)};
-    if (fm_overlap(out, 1, in, 6)) return MX_ERR_ARG;
+    const RowsRange out[1] = {rows_range(dy_hat, dy_hat_stride, B, N)};
+    const RowsRange in[6] = {rows_range(dz, dz_stride, B, N), rows_range(y, y_stride, B, N),
+                             rows_range(y_hat, y_hat_stride, B, N), rows_flat(taps, B * K, 4), rows_flat(u, B * K, 8),
+                             rows_flat(s, B * (2 * K - 1), 8)};
+    if (rows_any_overlap(out, 1, in, 6)) return MX_ERR_ARG;
     hipLaunchKernelGGL(fm_bwd_apply_kernel, fm_grid(B, N), dim3(FM_THREADS), 0, (hipStream_t)stream, dz, (long long)dz_stride,
                        y, (long long)y_stride, y_hat, (long long)y_hat_stride, taps, u, s, (int)N, (int)K, (int)centre, dy_hat,
                        (long long)dy_hat_stride);

@@ -24,6 +24,7 @@
 //     Every output is one fp32 rounding of an fp64 sum in a fixed order: the same inputs give the same bits.
 // Both entries are latency- and streaming-bound: the latent is read once, d_latent is written once.
 #include "fx_params_common.h"
+#include "rows_common.h"
 
 #define FXH_MAX_C 1024
 #define FXH_WAVES (FXP_THREADS / MX_WAVE)
@@ -119,7 +120,7 @@ __global__ __launch_bounds__(FXP_THREADS) void fx_head_bwd_rows_kernel(
     // the clip's C W contiguous floats: element i belongs to channel i / W
     float *ob = d_latent + b * (size_t)C * (size_t)W;
     const int n = C * W;
-    int head = (int)(((16u - (unsigned)((uintptr_t)ob & 15u)) & 15u) >> 2);
+    int head = rows_head(ob);
     if (head > n) head = n;
     const int nv = (n - head) >> 2;
     for (int i = tid; i < head; i += FXP_THREADS) ob[i] = cv[i / W];

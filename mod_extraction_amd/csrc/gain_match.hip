@@ -22,8 +22,7 @@
 //     "ls": fma(g, dz, k (y - 2 g y_hat)),  "rms": fma(g, dz, -(k g) y_hat),  clamped: g dz -- rounded once.  A thread reads
 //     dz[i] before it writes dy_hat[i] and nobody else touches i, so dy_hat may be dz.
 // Memory bound: forward 2 reads + (1 read, 1 write) of B N floats, backward 2 + (3, 1).
-#include "common.h"
-#include "modex_hip.h"
+#include "rows_common.h"
 
 #define GM_THREADS 256
 #define GM_CHUNK MX_GAIN_CHUNK
@@ -31,20 +30,6 @@
 #define GM_MAX_B 65535
 
 static_assert(GM_CHUNK % 4 == 0, "every chunk of a row shares the row's head");
-
-struct __attribute__((packed, aligned(4))) GmFloat4U { float x, y, z, w; };    // four floats at any 4-byte boundary
-
-// the part of a row one workgroup owns, split by the alignment of the leading pointer
-struct GmSpan { int head, nvec, tail; };
-__device__ __forceinline__ GmSpan gm_span(const float *lead, int len)
-{
-    GmSpan s;
-    int head = (int)(((16u - (unsigned)((uintptr_t)lead & 15u)) & 15u) >> 2);   // floats before the first 16-byte boundary
-    s.head = head < len ? head : len;
-    s.nvec = (len - s.head) >> 2;
-    s.tail = len - s.head - 4 * s.nvec;
-    return s;
-}
 
 // three block sums at once; red: 12 doubles of LDS.  Fixed order: lanes by butterfly, then waves 0 + 1 + 2 + 3.
 __device__ __forceinline__ void gm_block_sum3(double &a, double &c, double &e, double *red)
@@ -76,7 +61,7 @@ __global__ __launch_bounds__(GM_THREADS) void gain_partials_kernel(
     const int len = min(GM_CHUNK, N - n0);                          // >= 1: the grid has ceil(N / GM_CHUNK) chunks
     const float *p = y_hat + b * (size_t)y_hat_stride + n0;
     const float *q = y + b * (size_t)y_stride + n0;
-    const GmSpan sp = gm_span(p, len);
+    const RowsSpan sp = rows_span(p, len);
     double a = 0.0, c = 0.0, e = 0.0;
     if (tid < sp.head) {
         const double u = (double)p[tid], v = (double)q[tid];
@@ -85,10 +70,10 @@ __global__ __launch_bounds__(GM_THREADS) void gain_partials_kernel(
         e = fma(v, v, e);
     }
     const float4 *pv = reinterpret_cast<const float4 *>(p + sp.head);
-    const GmFloat4U *qv = reinterpret_cast<const GmFloat4U *>(q + sp.head);
+    const RowsUFloat4 *qv = reinterpret_cast<const RowsUFloat4 *>(q + sp.head);
     for (int i = tid; i < sp.nvec; i += GM_THREADS) {
         const float4 u4 = pv[i];
-        const GmFloat4U v4 = qv[i];
+        const RowsUFloat4 v4 = qv[i];
         const double u[4] = {(double)u4.x, (double)u4.y, (double)u4.z, (double)u4.w};
         const double v[4] = {(double)v4.x, (double)v4.y, (double)v4.z, (double)v4.w};
 #pragma unroll
@@ -149,12 +134,12 @@ __global__ __launch_bounds__(GM_THREADS) void gain_apply_kernel(
     const int len = min(GM_CHUNK, N - n0);
     const float *p = y_hat + b * (size_t)y_hat_stride + n0;
     float *o = z + b * (size_t)z_stride + n0;
-    const GmSpan sp = gm_span(o, len);
+    const RowsSpan sp = rows_span(o, len);
     if (tid < sp.head) o[tid] = __fmul_rn(g, p[tid]);
-    const GmFloat4U *pv = reinterpret_cast<const GmFloat4U *>(p + sp.head);
+    const RowsUFloat4 *pv = reinterpret_cast<const RowsUFloat4 *>(p + sp.head);
     float4 *ov = reinterpret_cast<float4 *>(o + sp.head);
     for (int i = tid; i < sp.nvec; i += GM_THREADS) {
-        const GmFloat4U u = pv[i];
+        const RowsUFloat4 u = pv[i];
         ov[i] = make_float4(__fmul_rn(g, u.x), __fmul_rn(g, u.y), __fmul_rn(g, u.z), __fmul_rn(g, u.w));
     }
     if (tid < sp.tail) {
@@ -174,14 +159,14 @@ __global__ __launch_bounds__(GM_THREADS) void gain_bwd_partials_kernel(
     const int len = min(GM_CHUNK, N - n0);
     const float *p = dz + b * (size_t)dz_stride + n0;
     const float *q = y_hat + b * (size_t)y_hat_stride + n0;
-    const GmSpan sp = gm_span(p, len);
+    const RowsSpan sp = rows_span(p, len);
     double s = 0.0;
     if (tid < sp.head) s = fma((double)p[tid], (double)q[tid], s);
     const float4 *pv = reinterpret_cast<const float4 *>(p + sp.head);
-    const GmFloat4U *qv = reinterpret_cast<const GmFloat4U *>(q + sp.head);
+    const RowsUFloat4 *qv = reinterpret_cast<const RowsUFloat4 *>(q + sp.head);
     for (int i = tid; i < sp.nvec; i += GM_THREADS) {
         const float4 u = pv[i];
-        const GmFloat4U v = qv[i];
+        const RowsUFloat4 v = qv[i];
         s = fma((double)u.x, (double)v.x, s);
         s = fma((double)u.y, (double)v.y, s);
         s = fma((double)u.z, (double)v.z, s);
@@ -225,14 +210,14 @@ __global__ __launch_bounds__(GM_THREADS) void gain_bwd_apply_kernel(
     const float *p = y_hat + b * (size_t)y_hat_stride + n0;
     const float *q = y + b * (size_t)y_stride + n0;
     float *o = dy_hat + b * (size_t)dy_hat_stride + n0;
-    const GmSpan sp = gm_span(o, len);
+    const RowsSpan sp = rows_span(o, len);
     if (tid < sp.head) o[tid] = gm_bwd_one(mode, g, k, kg, d[tid], p[tid], q[tid]);
-    const GmFloat4U *dv = reinterpret_cast<const GmFloat4U *>(d + sp.head);
-    const GmFloat4U *pv = reinterpret_cast<const GmFloat4U *>(p + sp.head);
-    const GmFloat4U *qv = reinterpret_cast<const GmFloat4U *>(q + sp.head);
+    const RowsUFloat4 *dv = reinterpret_cast<const RowsUFloat4 *>(d + sp.head);
+    const RowsUFloat4 *pv = reinterpret_cast<const RowsUFloat4 *>(p + sp.head);
+    const RowsUFloat4 *qv = reinterpret_cast<const RowsUFloat4 *>(q + sp.head);
     float4 *ov = reinterpret_cast<float4 *>(o + sp.head);
     for (int i = tid; i < sp.nvec; i += GM_THREADS) {
-        const GmFloat4U u = dv[i], v = pv[i], w = qv[i];
+        const RowsUFloat4 u = dv[i], v = pv[i], w = qv[i];
         ov[i] = make_float4(gm_bwd_one(mode, g, k, kg, u.x, v.x, w.x), gm_bwd_one(mode, g, k, kg, u.y, v.y, w.y),
                             gm_bwd_one(mode, g, k, kg, u.z, v.z, w.z), gm_bwd_one(mode, g, k, kg, u.w, v.w, w.w));
     }
@@ -243,22 +228,9 @@ __global__ __launch_bounds__(GM_THREADS) void gain_bwd_apply_kernel(
 }
 
 // C ABI ---------------------------------------------------------------------------------------
-static int gm_check_rows(const void *p, int64_t stride, int64_t B, int64_t N)
-{
-    return (!p || B < 1 || N < 1 || stride < N) ? MX_ERR_ARG : MX_OK;
-}
-
 static int gm_check_size(int64_t B, int64_t N)
 {
     return (N > GM_MAX_N || B > GM_MAX_B) ? MX_ERR_UNSUPPORTED : MX_OK;
-}
-
-// do B rows of N floats at a (stride sa) and at b (stride sb) share a byte?  (the spans from first to last element)
-static bool gm_overlap(const float *a, int64_t sa, const float *b, int64_t sb, int64_t B, int64_t N)
-{
-    const uintptr_t a0 = (uintptr_t)a, a1 = a0 + 4 * (uintptr_t)((B - 1) * sa + N);
-    const uintptr_t b0 = (uintptr_t)b, b1 = b0 + 4 * (uintptr_t)((B - 1) * sb + N);
-    return a0 < b1 && b0 < a1;
 }
 
 static dim3 gm_grid(int64_t B, int64_t N)
@@ -269,7 +241,7 @@ static dim3 gm_grid(int64_t B, int64_t N)
 MX_EXPORT int mx_gain_match_partials(const float *y_hat, int64_t y_hat_stride, const float *y, int64_t y_stride, int64_t B,
                                      int64_t N, double *partials, void *stream)
 {
-    if (!partials || gm_check_rows(y_hat, y_hat_stride, B, N) || gm_check_rows(y, y_stride, B, N)) return MX_ERR_ARG;
+    if (!partials || rows_check(y_hat, y_hat_stride, B, N) || rows_check(y, y_stride, B, N)) return MX_ERR_ARG;
     if (gm_check_size(B, N)) return MX_ERR_UNSUPPORTED;
     hipLaunchKernelGGL(gain_partials_kernel, gm_grid(B, N), dim3(GM_THREADS), 0, (hipStream_t)stream, y_hat,
                        (long long)y_hat_stride, y, (long long)y_stride, (int)N, partials);
@@ -285,12 +257,12 @@ MX_EXPORT int mx_gain_match_apply(const float *y_hat, int64_t y_hat_stride, cons
                                   int32_t mode, double eps, int32_t clamp, double lo, double hi, float *z, int64_t z_stride,
                                   float *gain, double *sums, int32_t *flags, void *stream)
 {
-    if (!partials || !gain || !sums || !flags || gm_check_rows(y_hat, y_hat_stride, B, N) || gm_check_rows(z, z_stride, B, N))
+    if (!partials || !gain || !sums || !flags || rows_check(y_hat, y_hat_stride, B, N) || rows_check(z, z_stride, B, N))
         return MX_ERR_ARG;
     if (gm_bad_mode_eps(mode, eps)) return MX_ERR_ARG;
     if (clamp && !(0.0 < lo && lo <= 1.0 && 1.0 <= hi && hi < 1e300)) return MX_ERR_ARG;
     if (gm_check_size(B, N)) return MX_ERR_UNSUPPORTED;
-    if (gm_overlap(z, z_stride, y_hat, y_hat_stride, B, N)) return MX_ERR_ARG;
+    if (rows_overlap(rows_range(z, z_stride, B, N), rows_range(y_hat, y_hat_stride, B, N))) return MX_ERR_ARG;
     hipLaunchKernelGGL(gain_apply_kernel, gm_grid(B, N), dim3(GM_THREADS), 0, (hipStream_t)stream, y_hat,
                        (long long)y_hat_stride, partials, (int)N, (int)mode, eps, (int)clamp, lo, hi, z, (long long)z_stride,
                        gain, sums, (int *)flags);
@@ -300,7 +272,7 @@ MX_EXPORT int mx_gain_match_apply(const float *y_hat, int64_t y_hat_stride, cons
 MX_EXPORT int mx_gain_match_bwd_partials(const float *dz, int64_t dz_stride, const float *y_hat, int64_t y_hat_stride,
                                          int64_t B, int64_t N, double *partials, void *stream)
 {
-    if (!partials || gm_check_rows(dz, dz_stride, B, N) || gm_check_rows(y_hat, y_hat_stride, B, N)) return MX_ERR_ARG;
+    if (!partials || rows_check(dz, dz_stride, B, N) || rows_check(y_hat, y_hat_stride, B, N)) return MX_ERR_ARG;
     if (gm_check_size(B, N)) return MX_ERR_UNSUPPORTED;
     hipLaunchKernelGGL(gain_bwd_partials_kernel, gm_grid(B, N), dim3(GM_THREADS), 0, (hipStream_t)stream, dz,
                        (long long)dz_stride, y_hat, (long long)y_hat_stride, (int)N, partials);
@@ -312,14 +284,15 @@ MX_EXPORT int mx_gain_match_bwd_apply(const float *dz, int64_t dz_stride, const 
                                       const int32_t *flags, const double *partials, int64_t B, int64_t N, int32_t mode,
                                       double eps, float *dy_hat, int64_t dy_hat_stride, void *stream)
 {
-    if (!gain || !sums || !flags || !partials || gm_check_rows(dz, dz_stride, B, N) || gm_check_rows(y_hat, y_hat_stride, B, N)
-        || gm_check_rows(y, y_stride, B, N) || gm_check_rows(dy_hat, dy_hat_stride, B, N))
+    if (!gain || !sums || !flags || !partials || rows_check(dz, dz_stride, B, N) || rows_check(y_hat, y_hat_stride, B, N)
+        || rows_check(y, y_stride, B, N) || rows_check(dy_hat, dy_hat_stride, B, N))
         return MX_ERR_ARG;
     if (gm_bad_mode_eps(mode, eps)) return MX_ERR_ARG;
     if (gm_check_size(B, N)) return MX_ERR_UNSUPPORTED;
     const bool in_place = dy_hat == dz && dy_hat_stride == dz_stride;
-    if ((!in_place && gm_overlap(dy_hat, dy_hat_stride, dz, dz_stride, B, N))
-        || gm_overlap(dy_hat, dy_hat_stride, y_hat, y_hat_stride, B, N) || gm_overlap(dy_hat, dy_hat_stride, y, y_stride, B, N))
+    const RowsRange out = rows_range(dy_hat, dy_hat_stride, B, N);
+    if ((!in_place && rows_overlap(out, rows_range(dz, dz_stride, B, N)))
+        || rows_overlap(out, rows_range(y_hat, y_hat_stride, B, N)) || rows_overlap(out, rows_range(y, y_stride, B, N)))
         return MX_ERR_ARG;
     hipLaunchKernelGGL(gain_bwd_apply_kernel, gm_grid(B, N), dim3(GM_THREADS), 0, (hipStream_t)stream, dz,
                        (long long)dz_stride, y_hat, (long long)y_hat_stride, y, (long long)y_stride, gain, sums,

@@ -1,5 +1,5 @@
 // lfo_stitch.hip -- K22: one LFO track along a whole recording from the LFOs of overlapping windows -- no counterpart in
-// the reference (include/modex_hip_file.h has the definition).
+// the reference (include/modex_hip.h, K22, has the definition).
 //
 //     p_j = j (L - 1) / (n_t - 1);   over the windows with s_w <= p_j <= s_w + N - 1, ascending w:
 //     track[j] = sum_w a_w v_w / sum_w a_w,   v_w = window w interpolated linearly at p_j,   a_w = sin^2(pi u) + 1e-3
@@ -10,7 +10,7 @@
 // L2-resident list), and the walk from it ends at the first s_w > p_j.  An index into a window is clamped to its row
 // whatever the starts hold, so no list can make the kernel read outside `windows`.  No atomics, no workspace, no LDS.
 // A 60 s recording is some 10^4 points and a few hundred windows: launch latency; there is nothing here to tune.
-#include "common.h"
+#include "rows_common.h"
 
 #define LS_THREADS 256
 #define LS_MAX_L (1ll << 31)
@@ -55,23 +55,15 @@ __global__ __launch_bounds__(LS_THREADS) void lfo_stitch_kernel(
 }
 
 // C ABI ---------------------------------------------------------------------------------------
-static bool ls_overlap(const void *a, uint64_t a_bytes, const void *b, uint64_t b_bytes)
-{
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return a0 < b0 + b_bytes && b0 < a0 + a_bytes;
-}
-
 MX_EXPORT int mx_lfo_stitch(const float *windows, const int64_t *starts, int64_t W, int64_t n_f, int64_t N, int64_t L,
                             int64_t n_t, float *track, int32_t *cover, void *stream)
 {
     if (!windows || !starts || !track || !cover) return MX_ERR_ARG;
     if (W < 1 || n_f < 2 || N < 2 || L < N || n_t < 2) return MX_ERR_ARG;
     if (W > MX_STITCH_MAX_WINDOWS || L > LS_MAX_L || n_f > LS_MAX_POINTS || n_t > LS_MAX_POINTS) return MX_ERR_UNSUPPORTED;
-    const uint64_t win_bytes = 4ull * (uint64_t)W * (uint64_t)n_f, st_bytes = 8ull * (uint64_t)W, out_bytes = 4ull * (uint64_t)n_t;
-    if (ls_overlap(track, out_bytes, windows, win_bytes) || ls_overlap(track, out_bytes, starts, st_bytes)
-        || ls_overlap(cover, out_bytes, windows, win_bytes) || ls_overlap(cover, out_bytes, starts, st_bytes)
-        || ls_overlap(track, out_bytes, cover, out_bytes))
-        return MX_ERR_ARG;
+    const RowsRange out[2] = {rows_flat(track, n_t, 4), rows_flat(cover, n_t, 4)};
+    const RowsRange in[2] = {rows_flat(windows, W * n_f, 4), rows_flat(starts, W, 8)};
+    if (rows_any_overlap(out, 2, in, 2)) return MX_ERR_ARG;
     const unsigned grid = (unsigned)((n_t + LS_THREADS - 1) / LS_THREADS);
     hipLaunchKernelGGL(lfo_stitch_kernel, dim3(grid), dim3(LS_THREADS), 0, (hipStream_t)stream, windows,
                        (const long long *)starts, (int)W, (int)n_f, (long long)N, (long long)L, (int)n_t, track, (int *)cover);

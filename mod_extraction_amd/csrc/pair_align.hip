@@ -20,8 +20,7 @@
 //     16-byte boundary of the out row, chunk q >= 1 four floats stored as one float4; the source is lag_b floats off that
 //     alignment, so it is read through a 4-byte-aligned vector type.  Chunks at the row's tail or across the source's ends
 //     go element by element with the bounds check.
-#include "common.h"
-#include "modex_hip.h"
+#include "rows_common.h"
 
 #define XC_THREADS 256
 #define XC_WAVES (XC_THREADS / MX_WAVE)
@@ -152,8 +151,6 @@ __global__ __launch_bounds__(256) void pair_peak_kernel(
     frac_out[b] = (float)frac;
 }
 
-struct __attribute__((packed, aligned(4))) Float4U { float x, y, z, w; };     // four floats at any 4-byte boundary
-
 __global__ __launch_bounds__(256) void pair_shift_kernel(
     const float *__restrict__ wet, long long wet_stride, int N, const int *__restrict__ lag, const float *__restrict__ corr,
     float *__restrict__ out, long long out_stride)
@@ -163,7 +160,7 @@ __global__ __launch_bounds__(256) void pair_shift_kernel(
     float *o = out + b * (size_t)out_stride;
     const long long sh = lag[b];
     const float s = (corr != nullptr && corr[b] < 0.0f) ? -1.0f : 1.0f;
-    int head = (int)(((16u - (unsigned)((uintptr_t)o & 15u)) & 15u) >> 2);    // floats before the first 16-byte boundary
+    int head = rows_head(o);
     head = head < N ? head : N;
     const long long q = (long long)blockIdx.x * 256 + threadIdx.x;
     const long long start = q == 0 ? 0 : head + 4 * (q - 1);
@@ -171,7 +168,7 @@ __global__ __launch_bounds__(256) void pair_shift_kernel(
     end = end < N ? end : N;
     if (start >= end) return;
     if (q > 0 && end - start == 4 && start + sh >= 0 && end + sh <= N) {
-        const Float4U v = *reinterpret_cast<const Float4U *>(w + (start + sh));
+        const RowsUFloat4 v = *reinterpret_cast<const RowsUFloat4 *>(w + (start + sh));
         *reinterpret_cast<float4 *>(o + start) = make_float4(s * v.x, s * v.y, s * v.z, s * v.w);
         return;
     }
@@ -215,11 +212,9 @@ MX_EXPORT int mx_pair_peak(const float *dry, int64_t dry_stride, const float *we
 MX_EXPORT int mx_pair_shift(const float *wet, int64_t wet_stride, int64_t B, int64_t N, const int32_t *lag, const float *corr,
                             float *out, int64_t out_stride, void *stream)
 {
-    if (!wet || !lag || !out || B <= 0 || N <= 0 || wet_stride < N || out_stride < N) return MX_ERR_ARG;
+    if (!lag || rows_check(wet, wet_stride, B, N) || rows_check(out, out_stride, B, N)) return MX_ERR_ARG;
     if (N > PA_MAX_N || B > PA_MAX_B) return MX_ERR_UNSUPPORTED;
-    const float *wet_end = wet + (B - 1) * wet_stride + N;
-    const float *out_end = out + (B - 1) * out_stride + N;
-    if (out < wet_end && wet < out_end) return MX_ERR_ARG;     // out may not alias wet
+    if (rows_overlap(rows_range(out, out_stride, B, N), rows_range(wet, wet_stride, B, N))) return MX_ERR_ARG;   // no aliasing
     const long long chunks = 1 + (N + 3) / 4;                   // the head, then float4s: covers every head length 0..3
     hipLaunchKernelGGL(pair_shift_kernel, dim3((unsigned)((chunks + 255) / 256), (unsigned)B), dim3(256), 0,
                        (hipStream_t)stream, wet, (long long)wet_stride, (int)N, (const int *)lag, corr, out,

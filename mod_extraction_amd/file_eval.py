@@ -2,7 +2,7 @@
 the reference.
 
     window_starts      where the model's N-sample windows sit on a file of L samples
-    stitch_lfo         K22 (csrc/lfo_stitch.hip; include/modex_hip_file.h has the definition): the windows' LFOs -> one track
+    stitch_lfo         K22 (csrc/lfo_stitch.hip; include/modex_hip.h has the definition): the windows' LFOs -> one track
     extract_lfo_track  the model over every window of a file, stitched
     render_file        ``LFOExtractionThroughEffect.render`` on the file as ONE row: the delay line starts where the recording
                        does, so there is no warm-up to mask ("Warm-up of a chunk cut from a file")
@@ -66,7 +66,7 @@ def stitch_lfo(lfo_windows: T, starts: Union[Sequence[int], T], L: int, N: int, 
                out: Optional[T] = None):
     """(track (n_t,) fp32, cover (n_t,) int32) from ``lfo_windows`` (W, n_f) fp32 on the device, window w covering the samples
     ``starts[w] .. starts[w] + N - 1`` of a file of L samples, in one ``mx_lfo_stitch`` launch: every track point is the
-    sin^2-tapered mean of the windows that cover it, each interpolated linearly at the point (include/modex_hip_file.h).
+    sin^2-tapered mean of the windows that cover it, each interpolated linearly at the point (include/modex_hip.h, K22).
     ``starts``: ascending ints, or an int64 device tensor.  ``n_t`` defaults to ``default_track_points``.  ``out``: an fp32
     (n_t,) device tensor with unit stride that receives the track."""
     fn = "stitch_lfo"

@@ -1,5 +1,5 @@
 """K21: one short least-squares FIR per clip that carries a rendered wet onto a recorded one, forward and backward on the
-device (csrc/fir_match.hip; include/modex_hip_fir.h has the definition) -- no counterpart in the reference.
+device (csrc/fir_match.hip; include/modex_hip.h has the definition) -- no counterpart in the reference.
 
     x = y_hat, both rows zero outside [0, N);  K taps, a centre c
     R[d] = sum_n x[n] x[n + d],  b[j] = sum_n x[n + c - j] y[n],  E = sum_n y[n]^2      (fp64 sums of exact products)

@@ -1,4 +1,4 @@
-"""The per-clip FIR match (K21, include/modex_hip_fir.h) restated in numpy fp64, one row at a time and one stage at a time.
+"""The per-clip FIR match (K21, include/modex_hip.h) restated in numpy fp64, one row at a time and one stage at a time.
 
     x = y_hat, y: N samples, zero outside [0, N);  K taps, a centre c
     sums      R[d] = sum_n x[n] x[n + d],  b[j] = sum_n x[n + c - j] y[n],  E = sum_n y[n]^2

@@ -9,7 +9,7 @@ import re
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-N_ENTRY_POINTS = 117                        # the one pin of the number of declarations; a new entry point raises it here
+N_ENTRY_POINTS = 124                      # the one pin of the number of declarations; a new entry point raises it here
 
 
 def header_symbols():
@@ -115,6 +115,36 @@ def test_missing_header_is_an_error(monkeypatch, tmp_path):
         _hip._header_text()
 
 
+def test_a_stale_library_is_named(monkeypatch, so_path):
+    """A library that lacks a declared symbol (the ABI number cannot tell an added entry point): ``load()``, which reads the
+    table as a module attribute at call time, names the symbol and the header and says how to rebuild."""
+    from mod_extraction_amd import _hip
+    monkeypatch.setattr(_hip, "_lib", None)
+    monkeypatch.setattr(_hip, "SIGNATURES", dict(_hip.SIGNATURES, mx_entry_of_tomorrow=[ctypes.c_void_p]))
+    with pytest.raises(_hip.HipLibraryError,
+                       match=r"mx_entry_of_tomorrow.*include/modex_hip\.h.*rebuild.*python -m mod_extraction_amd\.build"):
+        _hip.load()
+    monkeypatch.undo()
+    assert _hip.load() is not None
+
+
+def test_the_build_sees_the_header(monkeypatch, so_path):
+    """build.py runs nothing when everything is up to date, and compiles every source again and relinks when
+    include/modex_hip.h is newer than the objects."""
+    from mod_extraction_amd import build
+    ran = []
+    monkeypatch.setattr(build.subprocess, "check_call", lambda cmd: ran.append(cmd))
+    build.build(verbose=False)                                                # so_path built for real: up to date
+    assert ran == []
+    real = os.path.getmtime
+    hdr = os.path.join(build.INCLUDE, "modex_hip.h")
+    monkeypatch.setattr(build.os.path, "getmtime", lambda p: 4e9 if os.path.samefile(p, hdr) else real(p))
+    build.build(verbose=False)
+    compiled = {os.path.basename(c[c.index("-c") + 1]) for c in ran if "-c" in c}
+    assert compiled == set(build.sources()) and {"fir_match.hip", "lfo_stitch.hip"} <= compiled
+    assert any("-shared" in c for c in ran)
+
+
 def test_product_has_no_cpu_fallback():
     import torch
     from mod_extraction_amd import _hip, fx
@@ -160,4 +190,4 @@ def test_entry_points_reject_bad_arguments_before_touching_the_device(so_path):
         rc = getattr(lib, name)(*[zeros[t] for t in argtypes])
         assert rc in (-1, -2), (name, rc)                     # MX_ERR_ARG or MX_ERR_UNSUPPORTED
         checked += 1
-    assert checked == N_ENTRY_POINTS - 1 == 116
+    assert checked == N_ENTRY_POINTS - 1 == 123

@@ -1,5 +1,5 @@
-"""CPU: the surface of the file-level tools (``mod_extraction_amd.file_eval``, K22) -- ``window_starts``, the third header
-include/modex_hip_file.h against ``_hip.SIGNATURES_FILE``, the limits of ``mx_lfo_stitch`` (checked before any launch, so
+"""CPU: the surface of the file-level tools (``mod_extraction_amd.file_eval``, K22) -- ``window_starts``, the declaration of
+``mx_lfo_stitch`` in include/modex_hip.h against ``_hip.SIGNATURES``, the limits of ``mx_lfo_stitch`` (checked before any launch, so
 without a device) and the wrappers' ``ValueError``s.  No device work."""
 import ctypes
 import os
@@ -48,59 +48,30 @@ def test_window_starts_errors():
         window_starts(200.0, 64)
 
 
-def test_third_header_table_and_symbol():
-    """One name, declared in include/modex_hip_file.h and read here with a regex of this test's own; it is exported; the
-    argument count and the bound argtypes are those of ``_hip.SIGNATURES_FILE``; the other two tables are untouched and the
-    three texts together parse to 124 names -- the fold-back check."""
+def test_header_table_and_symbol():
+    """The one ``mx_lfo_stitch`` name, declared in include/modex_hip.h -- the one header: ``include/`` holds no other, and
+    csrc/common.h includes no other -- and read here with a regex of this test's own; it is exported; the argument count and
+    the bound argtypes are those of ``_hip.SIGNATURES``, which is what the parser makes of that text (ABI 21)."""
     from mod_extraction_amd import _hip, build, file_eval
     lib = ctypes.CDLL(build.build(verbose=False))
-    raw = open(os.path.join(ROOT, "include", "modex_hip_file.h")).read()
+    assert [f for f in os.listdir(os.path.join(ROOT, "include")) if f.endswith(".h")] == ["modex_hip.h"]
+    raw = open(os.path.join(ROOT, "include", "modex_hip.h")).read()
     text = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
-    found = re.findall(r"\bint\s+(mx_\w+)\s*\(([^;]*?)\)\s*;", text, flags=re.S)
-    assert [n for n, _ in found] == ["mx_lfo_stitch"] == list(_hip.SIGNATURES_FILE)
+    found = [(n, a) for n, a in re.findall(r"\bint\s+(mx_\w+)\s*\(([^;]*?)\)\s*;", text, flags=re.S) if "stitch" in n]
+    assert [n for n, _ in found] == ["mx_lfo_stitch"] == [n for n in _hip.SIGNATURES if "stitch" in n]
     params = [" ".join(a.split()) for a in found[0][1].split(",")]
-    assert len(params) == 10 == len(_hip.SIGNATURES_FILE["mx_lfo_stitch"])
+    assert len(params) == 10 == len(_hip.SIGNATURES["mx_lfo_stitch"])
     P, I64 = ctypes.c_void_p, ctypes.c_int64
-    assert _hip.SIGNATURES_FILE["mx_lfo_stitch"] == [P, P, I64, I64, I64, I64, I64, P, P, P]
-    assert [("*" in a) for a in params] == [t is P for t in _hip.SIGNATURES_FILE["mx_lfo_stitch"]]
-    assert not set(_hip.SIGNATURES_FILE) & (set(_hip.SIGNATURES) | set(_hip.SIGNATURES_FIR))
-    assert len(_hip.SIGNATURES) == 117 and len(_hip.SIGNATURES_FIR) == 6 and _hip.ABI_VERSION == 21
-    first, second = (open(os.path.join(ROOT, "include", n)).read() for n in ("modex_hip.h", "modex_hip_fir.h"))
-    every = _hip.parse_signatures(first + second + raw)
-    assert len(every) == 124 and every == dict(_hip.SIGNATURES, **_hip.SIGNATURES_FIR, **_hip.SIGNATURES_FILE)
+    assert _hip.SIGNATURES["mx_lfo_stitch"] == [P, P, I64, I64, I64, I64, I64, P, P, P]
+    assert [("*" in a) for a in params] == [t is P for t in _hip.SIGNATURES["mx_lfo_stitch"]]
+    assert _hip.SIGNATURES == _hip.parse_signatures(raw) and _hip.ABI_VERSION == 21
     assert int(re.search(r"^#define MX_STITCH_MAX_WINDOWS \(1 << (\d+)\)$", raw, flags=re.M).group(1)) == 20
     assert file_eval.MAX_WINDOWS == 1 << 20
     common = open(os.path.join(ROOT, "mod_extraction_amd", "csrc", "common.h")).read()
-    assert '#include "modex_hip_file.h"' in common
+    assert re.findall(r'#include\s+"(modex_hip\w*\.h)"', common) == ["modex_hip.h"]
     assert hasattr(lib, "mx_lfo_stitch")
     fn = _hip.load().mx_lfo_stitch
-    assert fn.argtypes == _hip.SIGNATURES_FILE["mx_lfo_stitch"] and fn.restype is ctypes.c_int
-
-
-def test_a_stale_library_is_named(monkeypatch):
-    """``load()`` reads the third table as a module attribute at call time, names a symbol the library lacks and says to rebuild."""
-    from mod_extraction_amd import _hip
-    monkeypatch.setattr(_hip, "_lib", None)
-    monkeypatch.setattr(_hip, "SIGNATURES_FILE", dict(_hip.SIGNATURES_FILE, mx_lfo_stitch_of_tomorrow=[ctypes.c_void_p]))
-    with pytest.raises(_hip.HipLibraryError, match="mx_lfo_stitch_of_tomorrow.*modex_hip_file.h.*rebuild"):
-        _hip.load()
-    monkeypatch.undo()
-    assert _hip.load() is not None
-
-
-def test_the_build_sees_the_third_header(monkeypatch):
-    from mod_extraction_amd import build
-    build.build(verbose=False)
-    ran = []
-    monkeypatch.setattr(build.subprocess, "check_call", lambda cmd: ran.append(cmd))
-    build.build(verbose=False)
-    assert ran == []
-    real = os.path.getmtime
-    hdr = os.path.join(build.INCLUDE, "modex_hip_file.h")
-    monkeypatch.setattr(build.os.path, "getmtime", lambda p: 4e9 if os.path.samefile(p, hdr) else real(p))
-    build.build(verbose=False)
-    compiled = {os.path.basename(c[c.index("-c") + 1]) for c in ran if "-c" in c}
-    assert compiled == set(build.sources()) and "lfo_stitch.hip" in compiled and any("-shared" in c for c in ran)
+    assert fn.argtypes == _hip.SIGNATURES["mx_lfo_stitch"] and fn.restype is ctypes.c_int
 
 
 def p(v):

@@ -1,4 +1,4 @@
-"""CPU: the surface of the FIR match (K21) -- the second header include/modex_hip_fir.h against ``_hip.SIGNATURES_FIR``, the
+"""CPU: the surface of the FIR match (K21) -- its six declarations in include/modex_hip.h against ``_hip.SIGNATURES``, the
 limits of the six entry points (checked before any launch, so without a device), the ``ValueError``s of the wrappers in
 ``mod_extraction_amd.fir_match`` and of the step's constructor, and the shipped config.  No device work."""
 import ctypes
@@ -15,68 +15,35 @@ NAMES = {"mx_fir_match_partials": 10, "mx_fir_match_solve": 12, "mx_fir_match_ap
 ARG, UNSUPPORTED = -1, -2
 
 
-def header_text(name):
-    return open(os.path.join(ROOT, "include", name)).read()
-
-
-def test_second_header_table_and_symbols():
-    """Exactly the six names, declared in include/modex_hip_fir.h and read here with a regex of this test's own; each is
-    exported; argument counts and the bound argtypes are those of ``_hip.SIGNATURES_FIR``; the first header's table is
-    untouched (117 entries, ABI 21), the two name sets are disjoint, and the two texts together parse to 123 names -- the
-    fold-back check."""
+def test_header_table_and_symbols():
+    """Exactly the six ``mx_fir_`` names, declared in include/modex_hip.h -- the one header: ``include/`` holds no other, and
+    csrc/common.h includes no other -- and read here with a regex of this test's own; each is exported; argument counts and
+    the bound argtypes are those of ``_hip.SIGNATURES``, which is what the parser makes of that text (ABI 21)."""
     from mod_extraction_amd import _hip, build, fir_match
     lib = ctypes.CDLL(build.build(verbose=False))
-    raw = header_text("modex_hip_fir.h")
+    assert [f for f in os.listdir(os.path.join(ROOT, "include")) if f.endswith(".h")] == ["modex_hip.h"]
+    raw = open(os.path.join(ROOT, "include", "modex_hip.h")).read()
     text = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
-    counts = {n: len(a.split(",")) for n, a in re.findall(r"\bint\s+(mx_\w+)\s*\(([^;]*?)\)\s*;", text, flags=re.S)}
-    assert counts == NAMES and list(counts) == list(_hip.SIGNATURES_FIR)
-    assert {k: len(v) for k, v in _hip.SIGNATURES_FIR.items()} == NAMES
+    counts = {n: len(a.split(",")) for n, a in re.findall(r"\bint\s+(mx_\w+)\s*\(([^;]*?)\)\s*;", text, flags=re.S)
+              if n.startswith("mx_fir_")}
+    assert counts == NAMES and list(counts) == [n for n in _hip.SIGNATURES if n.startswith("mx_fir_")]
+    assert {k: len(_hip.SIGNATURES[k]) for k in NAMES} == NAMES
     assert all(n.startswith("mx_fir_") and not n.startswith(("mx_gain_match_", "mx_pair_")) for n in NAMES)
-    assert not set(_hip.SIGNATURES_FIR) & set(_hip.SIGNATURES) and len(_hip.SIGNATURES) == 117 and _hip.ABI_VERSION == 21
-    assert _hip.SIGNATURES == _hip.parse_signatures(header_text("modex_hip.h"))
-    both = _hip.parse_signatures(header_text("modex_hip.h") + raw)
-    assert len(both) == 123 and both == dict(_hip.SIGNATURES, **_hip.SIGNATURES_FIR)
+    assert _hip.SIGNATURES == _hip.parse_signatures(raw) and _hip.ABI_VERSION == 21
     P, I64, I32, F64 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_double
-    assert _hip.SIGNATURES_FIR["mx_fir_match_solve"] == [P, I64, I64, I64, I64, F64, F64, F64, P, P, P, P]
-    assert _hip.SIGNATURES_FIR["mx_fir_match_bwd_apply"] == [P, I64, P, I64, P, I64, P, P, P, I64, I64, I64, I64, P, I64, P]
+    assert _hip.SIGNATURES["mx_fir_match_solve"] == [P, I64, I64, I64, I64, F64, F64, F64, P, P, P, P]
+    assert _hip.SIGNATURES["mx_fir_match_bwd_apply"] == [P, I64, P, I64, P, I64, P, P, P, I64, I64, I64, I64, P, I64, P]
     assert int(re.search(r"^#define MX_FIR_CHUNK (\d+)$", raw, flags=re.M).group(1)) == fir_match.CHUNK
     assert int(re.search(r"^#define MX_FIR_MAX_TAPS (\d+)$", raw, flags=re.M).group(1)) == fir_match.MAX_TAPS == 32
     common = open(os.path.join(ROOT, "mod_extraction_amd", "csrc", "common.h")).read()
-    assert '#include "modex_hip.h"' in common and '#include "modex_hip_fir.h"' in common
+    assert re.findall(r'#include\s+"(modex_hip\w*\.h)"', common) == ["modex_hip.h"]
     zeros = {P: None, I64: 0, I32: 0, F64: 0.0}
     loaded = _hip.load()
     for name in NAMES:
         assert hasattr(lib, name)
         fn = getattr(loaded, name)
-        assert fn.argtypes == _hip.SIGNATURES_FIR[name] and fn.restype is ctypes.c_int   # load() binds the second table too
+        assert fn.argtypes == _hip.SIGNATURES[name] and fn.restype is ctypes.c_int        # load() binds the one table
         assert fn(*[zeros[t] for t in fn.argtypes]) in (ARG, UNSUPPORTED)
-
-
-def test_a_stale_library_is_named(monkeypatch):
-    """A library without one of the six symbols (the ABI number cannot tell): ``load()`` names the symbol and says to rebuild."""
-    from mod_extraction_amd import _hip
-    monkeypatch.setattr(_hip, "_lib", None)
-    monkeypatch.setattr(_hip, "SIGNATURES_FIR", dict(_hip.SIGNATURES_FIR, mx_fir_match_of_tomorrow=[ctypes.c_void_p]))
-    with pytest.raises(_hip.HipLibraryError, match="mx_fir_match_of_tomorrow.*rebuild"):
-        _hip.load()
-    monkeypatch.undo()
-    assert _hip.load() is not None
-
-
-def test_the_build_sees_the_second_header(monkeypatch):
-    """build.py compiles every source again when include/modex_hip_fir.h is newer than the objects."""
-    from mod_extraction_amd import build
-    build.build(verbose=False)                                                # for real: everything is up to date after it
-    ran = []
-    monkeypatch.setattr(build.subprocess, "check_call", lambda cmd: ran.append(cmd))
-    build.build(verbose=False)
-    assert ran == []
-    real = os.path.getmtime
-    fir = os.path.join(build.INCLUDE, "modex_hip_fir.h")
-    monkeypatch.setattr(build.os.path, "getmtime", lambda p: 4e9 if os.path.samefile(p, fir) else real(p))
-    build.build(verbose=False)
-    compiled = {os.path.basename(c[c.index("-c") + 1]) for c in ran if "-c" in c}
-    assert compiled == set(build.sources()) and "fir_match.hip" in compiled and any("-shared" in c for c in ran)
 
 
 def p(v):
