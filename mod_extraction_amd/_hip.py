@@ -19,6 +19,8 @@ _ERR = {-1: "MX_ERR_ARG (bad argument)", -2: "MX_ERR_UNSUPPORTED (size not suppo
         -3: "MX_ERR_LAUNCH (HIP launch error)"}
 
 HEADER = os.path.join(_HERE, "..", "include", "modex_hip.h")      # where build.py finds it too
+# K23's entry points are declared beside their kernels until they are folded into modex_hip.h with an ABI number
+HEADER_TRACK = os.path.join(_HERE, "csrc", "track_fit_abi.h")
 
 # the parameter kinds of the C ABI: any pointer, and these six scalars (modex_hip.h states the rule)
 _SCALARS = {"int64_t": ctypes.c_int64, "int32_t": ctypes.c_int32, "uint64_t": ctypes.c_uint64, "uint32_t": ctypes.c_uint32,
@@ -68,6 +70,9 @@ def _header_text(path: Optional[str] = None) -> str:
 
 # name -> argtypes of every entry point, derived from include/modex_hip.h (the definitions are compiled against the same text)
 SIGNATURES = parse_signatures(_header_text())
+# the second table: the entry points of csrc/track_fit_abi.h (mx_track_fit*), bound by load() like the first
+SIGNATURES_TRACK = parse_signatures(_header_text(HEADER_TRACK))
+TRACK_FIT_ROW_TILE = int(re.search(r"#define\s+MX_TRACK_FIT_ROW_TILE\s+(\d+)", _header_text(HEADER_TRACK)).group(1))
 
 # measurement twins (same signatures): the dependent chain of the sample-recurrent kernels without global traffic
 PROBE_TWINS = ("mx_flanger_fwd", "mx_phaser_fwd", "mx_lstm_fwd", "mx_lstm_bwd_l1")
@@ -83,13 +88,15 @@ def load() -> ctypes.CDLL:
                 f"{SO_PATH} not found: build it with `python -m mod_extraction_amd.build` "
                 "(there is no CPU fallback)")
         lib = ctypes.CDLL(SO_PATH)
-        for name, argtypes in SIGNATURES.items():           # read as a module attribute here, at call time
-            fn = getattr(lib, name, None)
-            if fn is None:                  # the ABI number does not cover an added entry point: name what a stale build lacks
-                raise HipLibraryError(f"{SO_PATH} has no symbol {name} (declared in include/modex_hip.h): a stale build; "
-                                      "rebuild it with `python -m mod_extraction_amd.build`")
-            fn.argtypes = argtypes
-            fn.restype = ctypes.c_int
+        # both tables are read as module attributes here, at call time
+        for table, header in ((SIGNATURES, "include/modex_hip.h"), (SIGNATURES_TRACK, "csrc/track_fit_abi.h")):
+            for name, argtypes in table.items():
+                fn = getattr(lib, name, None)
+                if fn is None:              # the ABI number does not cover an added entry point: name what a stale build lacks
+                    raise HipLibraryError(f"{SO_PATH} has no symbol {name} (declared in {header}): a stale build; "
+                                          "rebuild it with `python -m mod_extraction_amd.build`")
+                fn.argtypes = argtypes
+                fn.restype = ctypes.c_int
         if lib.mx_abi_version() != ABI_VERSION:
             raise HipLibraryError(f"ABI mismatch: library {lib.mx_abi_version()} != binding {ABI_VERSION}")
         _lib = lib

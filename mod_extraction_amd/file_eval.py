@@ -17,10 +17,9 @@ import torch
 from torch import Tensor as T
 
 from . import _hip
+from .modulations import FIT_MAX_POINTS, FIT_MAX_RATES     # K18's limits: fit_track keeps its launch inside them
 
 MAX_WINDOWS = 1 << 20                           # MX_STITCH_MAX_WINDOWS
-FIT_MAX_POINTS = 4096                           # FIT_MAX_N of csrc/lfo_fit.hip: the longest row mx_lfo_fit takes
-FIT_MAX_RATES = 512                             # FIT_MAX_K there: the most rates of its grid
 
 
 class LfoTrack(NamedTuple):
@@ -202,13 +201,18 @@ def render_file(step, dry: T, track: T, fx_params=None) -> T:
     return step.render(d.view(1, 1, L), mod.contiguous(), fx_params).reshape(L)
 
 
-def fit_track(track: T, point_rate: float, rate_hz=(0.25, 8.0)):
-    """(LFOFit, points used): ``modulations.fit_lfo`` on a track of any length.  ``mx_lfo_fit`` takes rows of at most
-    ``FIT_MAX_POINTS`` points and a grid of at most ``FIT_MAX_RATES`` rates (both LDS budgets of csrc/lfo_fit.hip): a longer
-    track is fitted on its first ``FIT_MAX_POINTS`` points, and ``rate_div`` (default 4) is lowered until the grid fits."""
+def fit_track(track: T, point_rate: float, rate_hz=(0.25, 8.0), rate_div: Optional[int] = None):
+    """(LFOFit, points fitted): ``modulations.fit_lfo`` on the WHOLE track, whatever its length.  With ``rate_div=None`` a
+    track of at most ``FIT_MAX_POINTS`` points is one ``mx_lfo_fit`` launch (K18), ``rate_div`` (default 4) lowered until its
+    grid has at most ``FIT_MAX_RATES`` rates; a longer track is fitted at ``rate_div`` 4 by ``mx_track_fit`` (K23).  An explicit
+    ``rate_div`` is passed on as it is, and ``modulations.fit_plan`` picks the route."""
     from .modulations import fit_lfo, fit_rate_window
     f_min, f_max = fit_rate_window(rate_hz, float(point_rate))
-    n = min(track.numel(), FIT_MAX_POINTS)
+    n = track.numel()
+    if rate_div is not None:
+        return fit_lfo(track, point_rate, (f_min, f_max), rate_div=rate_div), n
+    if n > FIT_MAX_POINTS:
+        return fit_lfo(track, point_rate, (f_min, f_max), rate_div=4), n
     for rate_div in (4, 3, 2, 1):
         if int((f_max - f_min) / (float(point_rate) / (rate_div * n))) + 1 <= FIT_MAX_RATES:
             return fit_lfo(track[:n], point_rate, (f_min, f_max), rate_div=rate_div), n
@@ -220,7 +224,7 @@ def score_pair(step, model, dry: T, wet: T, lag: int = 0, polarity: int = 1, hop
     """One dry / wet recording against ``step`` (an ``LFOExtractionThroughEffect``) and its extractor ``model``:
     1. ``alignment.shift_rows`` brings ``wet`` onto ``dry`` by ``lag`` samples and ``polarity`` (+1 / -1) -- K19's convention;
     2. ``extract_lfo_track`` over windows of ``n_samples`` (``dry`` is shown too iff ``step.use_dry``);
-    3. ``fit_track``: rate, shape and residual of the track (``fit_points`` says how many points were fitted);
+    3. ``fit_track``: rate, shape and residual of the whole track (``fit_points`` is its number of points);
     4. ``render_file`` from the track;
     5. the match ``step`` is configured for (``match_fir`` / ``match_gain``) with the WHOLE FILE as one row: one FIR or one
        gain per file;

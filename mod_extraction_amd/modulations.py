@@ -4,6 +4,7 @@
 kernel; ``make_mod_signals`` is the batched form the training loop uses (one launch for the whole
 batch, optional crop offset and on-the-fly resampling).
 """
+import ctypes
 import math
 from typing import List, NamedTuple, Optional, Sequence, Tuple, Union
 
@@ -398,13 +399,53 @@ def fit_rate_window(rate_hz, sr: float) -> Tuple[float, float]:
     return f_min, f_max
 
 
+FIT_MIN_POINTS = 16                             # FIT_MIN_N of csrc/lfo_fit_common.h
+FIT_MAX_POINTS = 4096                           # FIT_MAX_N of csrc/lfo_fit.hip: the longest row mx_lfo_fit takes
+FIT_MAX_RATES = 512                             # FIT_MAX_K there: the most rates of its grid
+TRACK_FIT_MAX_POINTS = 1 << 20                  # MX_TRACK_FIT_MAX_N of csrc/track_fit_abi.h
+TRACK_FIT_MAX_RATES = 1 << 20                   # MX_TRACK_FIT_MAX_K there
+TRACK_FIT_ROW_TILE = _hip.TRACK_FIT_ROW_TILE    # MX_TRACK_FIT_ROW_TILE there: the points of a row mx_track_fit stages at a time
+
+
+def _fl32(v: float) -> float:
+    """``v`` rounded to fp32, as a float: what the C ABI receives for a ``float`` parameter."""
+    return ctypes.c_float(v).value
+
+
+def fit_plan(n: int, sr: float, rate_hz=(0.25, 8.0), rate_div: int = 4) -> Tuple[str, int]:
+    """(route, K) of a fit of n-point rows: ``"lfo_fit"`` (K18, one workgroup a row: n <= 4096 and K <= 512) or
+    ``"track_fit"`` (K23, a grid of candidate tiles: n <= 2^20, K <= 2^20), and the number of rates
+    K = floor((f_max - f_min) / df) + 1, df = 1 / (rate_div (n / sr)): fp64 on the fp32 roundings of the window and of sr,
+    the formula of both libraries' entry points.  Pure host arithmetic.  A row below 16 points, or a ``rate_div`` outside
+    1 .. 16, has no grid: up to 4096 points it goes to ``mx_lfo_fit`` with K = 0, which refuses it as it always has; a longer
+    one is a ValueError, as are n > 2^20 and K > 2^20."""
+    f_min, f_max = fit_rate_window(rate_hz, float(sr))
+    n, rate_div = int(n), int(rate_div)
+    if n > TRACK_FIT_MAX_POINTS:
+        raise ValueError(f"fit_lfo: rows of {n} points; the fit takes at most {TRACK_FIT_MAX_POINTS}")
+    if n < FIT_MIN_POINTS or not 1 <= rate_div <= 16:
+        if n <= FIT_MAX_POINTS:
+            return "lfo_fit", 0
+        raise ValueError(f"fit_lfo: rate_div must be in 1 .. 16, got {rate_div}")
+    df = 1.0 / (rate_div * (n / _fl32(float(sr))))
+    K = int(math.floor((_fl32(f_max) - _fl32(f_min)) / df)) + 1
+    if n <= FIT_MAX_POINTS and K <= FIT_MAX_RATES:
+        return "lfo_fit", K
+    if K > TRACK_FIT_MAX_RATES:
+        raise ValueError(f"fit_lfo: the rate window {rate_hz!r} needs {K} rates on {n} points at rate_div = {rate_div}; the "
+                         f"fit takes at most {TRACK_FIT_MAX_RATES}")
+    return "track_fit", K
+
+
 def fit_lfo(mod_sig: T, sr: float, rate_hz=(0.25, 8.0), shapes: Sequence[str] = LFO_SHAPES, rate_div: int = 4,
             n_phases: int = 32, n_rounds: int = 4, per_shape: bool = False) -> LFOFit:
     """Rate, phase and shape of every row of ``mod_sig`` ((B, n) or (n,), fp32, on the device; ``sr`` the rate of its
-    points, 172.5 for 345 points of a 2 s clip) in one ``mx_lfo_fit`` launch: a grid search over the rate window ``rate_hz``
-    (spacing ``sr / (rate_div n)``) and ``n_phases`` centre phases, ``n_rounds`` rounds of 5 x 5 refinement, per allowed shape,
-    with a non-negative amplitude and a free offset (include/modex_hip.h, K18, has the definition).  Rows a row stride apart
-    (inner stride 1) are read in place."""
+    points, 172.5 for 345 points of a 2 s clip): a grid search over the rate window ``rate_hz`` (spacing ``sr / (rate_div n)``)
+    and ``n_phases`` centre phases, ``n_rounds`` rounds of 5 x 5 refinement, per allowed shape, with a non-negative amplitude
+    and a free offset (include/modex_hip.h, K18, has the definition).  Rows a row stride apart (inner stride 1) are read in
+    place.  ``fit_plan`` picks the route: rows of at most 4096 points on a grid of at most 512 rates are one ``mx_lfo_fit``
+    launch; longer rows or finer grids (to 2^20 points, 2^20 rates) go to ``mx_track_fit`` (K23, csrc/track_fit_abi.h), the
+    same function on a grid of workgroups, with a workspace from ``torch.empty``."""
     mask = fit_shape_mask(shapes)
     f_min, f_max = fit_rate_window(rate_hz, float(sr))
     if not isinstance(mod_sig, torch.Tensor) or mod_sig.ndim not in (1, 2) or mod_sig.dtype != torch.float32:
@@ -416,14 +457,24 @@ def fit_lfo(mod_sig: T, sr: float, rate_hz=(0.25, 8.0), shapes: Sequence[str] = 
     B, n = m.shape
     if B == 0:
         raise ValueError("fit_lfo: mod_sig has no rows")
+    route, _ = fit_plan(n, sr, (f_min, f_max), rate_div)
+    if route == "track_fit" and not (4 <= int(n_phases) <= 128 and 0 <= int(n_rounds) <= 8):
+        raise ValueError(f"fit_lfo: need 4 <= n_phases <= 128 and 0 <= n_rounds <= 8, got {n_phases!r} and {n_rounds!r}")
     if m.stride(1) != 1 or (B > 1 and m.stride(0) < n):
         m = m.contiguous()
     stride = max(m.stride(0), n) if B > 1 else n
     dev = m.device
+    grid = (float(sr), f_min, f_max, mask, int(rate_div), int(n_phases), int(n_rounds))
+    ws_args = ()
+    if route == "track_fit":
+        sizes = (ctypes.c_int64 * 2)()                                  # K and the workspace's bytes, from the library
+        _hip.call("mx_track_fit_plan", B, n, *grid, ctypes.addressof(sizes), ctypes.addressof(sizes) + 8)
+        ws = torch.empty((sizes[1] + 7) // 8, device=dev, dtype=torch.float64)
+        ws_args = (ws.data_ptr(), ws.numel() * 8)
     out = [torch.empty(B, device=dev, dtype=torch.int32)] + [torch.empty(B, device=dev, dtype=torch.float32) for _ in range(5)]
     table = torch.empty((B, 7), device=dev, dtype=torch.float32) if per_shape else None
-    _hip.call("mx_lfo_fit", m.data_ptr(), stride, B, n, float(sr), f_min, f_max, mask, int(rate_div), int(n_phases),
-              int(n_rounds), *[_hip.ptr(o) for o in out], _hip.ptr(table), _hip.stream())
+    _hip.call("mx_lfo_fit" if route == "lfo_fit" else "mx_track_fit", m.data_ptr(), stride, B, n, *grid,
+              *[_hip.ptr(o) for o in out], _hip.ptr(table), *ws_args, _hip.stream())
     return LFOFit(*out, table)
 
 
