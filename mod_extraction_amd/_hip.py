@@ -21,6 +21,8 @@ _ERR = {-1: "MX_ERR_ARG (bad argument)", -2: "MX_ERR_UNSUPPORTED (size not suppo
 HEADER = os.path.join(_HERE, "..", "include", "modex_hip.h")      # where build.py finds it too
 # K23's entry points are declared beside their kernels until they are folded into modex_hip.h with an ABI number
 HEADER_TRACK = os.path.join(_HERE, "csrc", "track_fit_abi.h")
+# K24's likewise
+HEADER_RESAMPLE = os.path.join(_HERE, "csrc", "resample_abi.h")
 
 # the parameter kinds of the C ABI: any pointer, and these six scalars (modex_hip.h states the rule)
 _SCALARS = {"int64_t": ctypes.c_int64, "int32_t": ctypes.c_int32, "uint64_t": ctypes.c_uint64, "uint32_t": ctypes.c_uint32,
@@ -73,6 +75,9 @@ SIGNATURES = parse_signatures(_header_text())
 # the second table: the entry points of csrc/track_fit_abi.h (mx_track_fit*), bound by load() like the first
 SIGNATURES_TRACK = parse_signatures(_header_text(HEADER_TRACK))
 TRACK_FIT_ROW_TILE = int(re.search(r"#define\s+MX_TRACK_FIT_ROW_TILE\s+(\d+)", _header_text(HEADER_TRACK)).group(1))
+# the third table: the entry points of csrc/resample_abi.h (mx_resample_*)
+SIGNATURES_RESAMPLE = parse_signatures(_header_text(HEADER_RESAMPLE))
+RESAMPLE_OUT_TILE = int(re.search(r"#define\s+MX_RESAMPLE_OUT_TILE\s+(\d+)", _header_text(HEADER_RESAMPLE)).group(1))
 
 # measurement twins (same signatures): the dependent chain of the sample-recurrent kernels without global traffic
 PROBE_TWINS = ("mx_flanger_fwd", "mx_phaser_fwd", "mx_lstm_fwd", "mx_lstm_bwd_l1")
@@ -88,8 +93,9 @@ def load() -> ctypes.CDLL:
                 f"{SO_PATH} not found: build it with `python -m mod_extraction_amd.build` "
                 "(there is no CPU fallback)")
         lib = ctypes.CDLL(SO_PATH)
-        # both tables are read as module attributes here, at call time
-        for table, header in ((SIGNATURES, "include/modex_hip.h"), (SIGNATURES_TRACK, "csrc/track_fit_abi.h")):
+        # the tables are read as module attributes here, at call time
+        for table, header in ((SIGNATURES, "include/modex_hip.h"), (SIGNATURES_TRACK, "csrc/track_fit_abi.h"),
+                              (SIGNATURES_RESAMPLE, "csrc/resample_abi.h")):
             for name, argtypes in table.items():
                 fn = getattr(lib, name, None)
                 if fn is None:              # the ABI number does not cover an added entry point: name what a stale build lacks

@@ -446,10 +446,27 @@ class _SyntheticDataModule:
     _DS_KEYS = ("ext", "silence_fraction_allowed", "silence_threshold_energy", "n_retries", "check_dataset",
                 "end_buffer_n_samples", "should_peak_norm", "peak_norm_db")
 
+    def _audio_dir(self, key: str) -> Optional[str]:
+        """The directory the init_args name under ``key`` (``train_dir``, ``dry_val_dir``, ...).  With ``resample_cache_dir``
+        set, ``resample.convert_tree`` first brings every file of it to ``sr`` under ``<cache>/<key without _dir>`` on the
+        device ``setup`` was given, and that tree is returned: the datasets drop files at another rate, and the seeded start
+        offsets of their items count samples at ``sr``.  Every rank converts; the conversion is deterministic and files
+        appear by rename.  Without the key: the directory as it was given, no other work."""
+        d = self.ignored_args.get(key)
+        cache = self.ignored_args.get("resample_cache_dir")
+        if not cache or not d or not os.path.isdir(d):
+            return d
+        if int(self.sr) != self.sr:
+            raise ValueError(f"resample_cache_dir needs an integer sr, got {self.sr!r}")
+        from . import resample
+        dst = os.path.join(cache, key[:-len("_dir")])
+        resample.convert_tree(d, dst, int(self.sr), ext=self.ignored_args.get("ext", "wav"), device=self._setup_device)
+        return dst
+
     def _chunk_source(self, which: str) -> Optional[Any]:
         """datasets.FileChunkSource over `<which>_dir` (train_dir / val_dir of the reference's init_args) if that
         directory exists, else None (synthetic clips)."""
-        d = self.ignored_args.get(f"{which}_dir") or self.ignored_args.get(f"dry_{which}_dir")
+        d = self._audio_dir(f"{which}_dir") or self._audio_dir(f"dry_{which}_dir")
         if not d or not os.path.isdir(d):
             return None
         from . import datasets
@@ -459,6 +476,7 @@ class _SyntheticDataModule:
         return datasets.FileChunkSource(ds)
 
     def setup(self, device: torch.device, rank: int = 0, seed: int = 43) -> None:
+        self._setup_device = device
         fl = self.fx_config.get("flanger")
         common = dict(flanger_fx=fl, chorus_fx=fl if "chorus" in self.kinds and fl else None,
                       phaser_fx=self.fx_config.get("pedalboard_phaser"), tremolo_fx=self.fx_config.get("tremolo"),
@@ -572,7 +590,7 @@ class RandomAudioChunkDryWetDataModule(_SyntheticDataModule):
     _ALIGN_KEYS = ("align_max_lag_ms", "align_n_probes", "align_min_corr")
 
     def _pair_dataset(self, which: str):
-        dry_d, wet_d = self.ignored_args.get(f"dry_{which}_dir"), self.ignored_args.get(f"wet_{which}_dir")
+        dry_d, wet_d = self._audio_dir(f"dry_{which}_dir"), self._audio_dir(f"wet_{which}_dir")
         if not dry_d or not wet_d or not os.path.isdir(dry_d) or not os.path.isdir(wet_d):
             return None
         from . import datasets
@@ -596,8 +614,8 @@ class RandomAudioChunkDryWetDataModule(_SyntheticDataModule):
                  max(lags), sum(al.polarity < 0 for al in good))
 
     def setup(self, device: torch.device, rank: int = 0, seed: int = 43) -> None:
+        self._setup_device = self._device = device
         self._pairs = {w: self._pair_dataset(w) for w in ("train", "val")}
-        self._device = device
         for which, ds in self._pairs.items():
             if ds is not None and ds.align_max_lag is not None:
                 self._align(which, ds, device)

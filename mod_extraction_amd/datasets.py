@@ -109,14 +109,21 @@ class RandomAudioChunkDataset:
         self.max_n_consecutive_silent_samples = int(silence_fraction_allowed * n_samples)
         self._frames: Dict[str, int] = {}
         kept, total = [], 0
+        other_rates: Dict[int, int] = {}                    # rate -> files dropped for their rate alone
         for path in list_files(input_dir, ext):
             frames, file_sr, _ = wav_info(path)
             if frames < n_samples or file_sr != sr:          # too short / wrong rate: dropped (datasets.py:125-131)
+                if file_sr != sr and frames * sr >= n_samples * file_sr:
+                    other_rates[file_sr] = other_rates.get(file_sr, 0) + 1
                 continue
             self._frames[path] = frames
             total += frames
             kept.append(path)
         log.info("%d usable files, %.0f s of audio", len(kept), total / sr)
+        if other_rates:
+            log.warning("%d files under %s dropped because they are not at %s Hz (%s): convert them with the data module's "
+                        "resample_cache_dir key or scripts/resample_dir.py", sum(other_rates.values()), input_dir, sr,
+                        ", ".join(f"{n} at {r} Hz" for r, n in sorted(other_rates.items())))
         assert len(kept) > 0
         self.input_paths = kept
         if check_dataset:

@@ -7,6 +7,8 @@ The config's ``model`` must be a ``lightning.LFOExtractionThroughEffect`` (witho
 ``n_samples``, ``sr`` and -- when ``align_max_lag_ms`` is there -- the alignment settings.  Files are paired as
 ``datasets.RandomAudioChunkDryWetDataset`` pairs them (same name in both directories, same rate, channels and length within
 ``end_buffer_n_samples``); with ``align_max_lag_ms`` its ``estimate_alignment`` table gives every pair's lag and polarity.
+Recordings at another rate than the config's ``sr``: ``--resample_cache_dir DIR`` converts both directories on the device into
+``DIR/dry`` and ``DIR/wet`` first (``resample.convert_tree``) and scores those; without it such files are dropped.
 Per pair ``file_eval.score_pair`` runs on channel 0 of the whole file: the extractor's LFO track, the rate and shape fitted
 to it, the re-render from the file's first sample, ONE gain or FIR for the file, and the step's audio losses.
 """
@@ -18,7 +20,7 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
-from mod_extraction_amd import cli, datasets, file_eval, lightning, modulations  # noqa: E402
+from mod_extraction_amd import cli, datasets, file_eval, lightning, modulations, resample  # noqa: E402
 
 
 def main() -> int:
@@ -30,6 +32,8 @@ def main() -> int:
     ap.add_argument("--hop", type=int, default=None, help="hop of the extractor's windows in samples (default n_samples // 2)")
     ap.add_argument("--batch_size", type=int, default=32)
     ap.add_argument("--device", default="cuda:0")
+    ap.add_argument("--resample_cache_dir", default=None,
+                    help="bring both directories to the config's sr on the device, into DIR/dry and DIR/wet, and score those")
     a = ap.parse_args()
     cfg = cli.apply_links(cli.load_config(a.config))
     dev = torch.device(a.device)
@@ -40,8 +44,15 @@ def main() -> int:
     step.eval()
     data = dict((cfg.get("data") or {}).get("init_args") or {})
     n_samples, sr = int(data.get("n_samples", 88200)), float(data.get("sr", step.sr))
+    dry_dir, wet_dir = a.dry_dir, a.wet_dir
+    if a.resample_cache_dir:
+        if int(sr) != sr:
+            raise SystemExit(f"--resample_cache_dir needs an integer sr, the config has {sr}")
+        dry_dir, wet_dir = (os.path.join(a.resample_cache_dir, w) for w in ("dry", "wet"))
+        resample.convert_tree(a.dry_dir, dry_dir, int(sr), device=dev)
+        resample.convert_tree(a.wet_dir, wet_dir, int(sr), device=dev)
     ds = datasets.RandomAudioChunkDryWetDataset(
-        a.dry_dir, a.wet_dir, n_samples, sr, check_dataset=False, end_buffer_n_samples=int(data.get("end_buffer_n_samples", 0)),
+        dry_dir, wet_dir, n_samples, sr, check_dataset=False, end_buffer_n_samples=int(data.get("end_buffer_n_samples", 0)),
         align_max_lag_ms=data.get("align_max_lag_ms"), align_n_probes=int(data.get("align_n_probes", 8)),
         align_min_corr=float(data.get("align_min_corr", 0.5)))
     table = ds.estimate_alignment(dev) if ds.align_max_lag is not None else {}
