@@ -23,6 +23,8 @@ HEADER = os.path.join(_HERE, "..", "include", "modex_hip.h")      # where build.
 HEADER_TRACK = os.path.join(_HERE, "csrc", "track_fit_abi.h")
 # K24's likewise
 HEADER_RESAMPLE = os.path.join(_HERE, "csrc", "resample_abi.h")
+# K25's likewise
+HEADER_RATE = os.path.join(_HERE, "csrc", "rate_track_abi.h")
 
 # the parameter kinds of the C ABI: any pointer, and these six scalars (modex_hip.h states the rule)
 _SCALARS = {"int64_t": ctypes.c_int64, "int32_t": ctypes.c_int32, "uint64_t": ctypes.c_uint64, "uint32_t": ctypes.c_uint32,
@@ -78,6 +80,10 @@ TRACK_FIT_ROW_TILE = int(re.search(r"#define\s+MX_TRACK_FIT_ROW_TILE\s+(\d+)", _
 # the third table: the entry points of csrc/resample_abi.h (mx_resample_*)
 SIGNATURES_RESAMPLE = parse_signatures(_header_text(HEADER_RESAMPLE))
 RESAMPLE_OUT_TILE = int(re.search(r"#define\s+MX_RESAMPLE_OUT_TILE\s+(\d+)", _header_text(HEADER_RESAMPLE)).group(1))
+# the fourth table: the entry points of csrc/rate_track_abi.h (mx_rate_track_*), and the limits that header defines
+SIGNATURES_RATE = parse_signatures(_header_text(HEADER_RATE))
+RATE_TRACK_LIMITS = {k: int(v) for k, v in re.findall(r"#define\s+MX_RATE_TRACK_(\w+)\s+(\d+)\s*$", _header_text(HEADER_RATE),
+                                                      flags=re.M)}
 
 # measurement twins (same signatures): the dependent chain of the sample-recurrent kernels without global traffic
 PROBE_TWINS = ("mx_flanger_fwd", "mx_phaser_fwd", "mx_lstm_fwd", "mx_lstm_bwd_l1")
@@ -95,7 +101,7 @@ def load() -> ctypes.CDLL:
         lib = ctypes.CDLL(SO_PATH)
         # the tables are read as module attributes here, at call time
         for table, header in ((SIGNATURES, "include/modex_hip.h"), (SIGNATURES_TRACK, "csrc/track_fit_abi.h"),
-                              (SIGNATURES_RESAMPLE, "csrc/resample_abi.h")):
+                              (SIGNATURES_RESAMPLE, "csrc/resample_abi.h"), (SIGNATURES_RATE, "csrc/rate_track_abi.h")):
             for name, argtypes in table.items():
                 fn = getattr(lib, name, None)
                 if fn is None:              # the ABI number does not cover an added entry point: name what a stale build lacks

@@ -1,6 +1,8 @@
 // lfo_fit_common.h -- what the two LFO fits share (lfo_fit.hip, K18: one workgroup per row; track_fit.hip, K23: a grid of
 // candidate tiles): the candidate's fp32 (rate, phase), the decoding of a candidate index, the objective, the order of the
 // argmin, and one search stage of a 1024-thread workgroup over a centred fp64 row.  lfo_fit.hip has the definition of the fit.
+// rate_track.hip (K25) evaluates the same candidates per slice of a track and runs the same refinement rounds, which K23 and
+// K25 share as fit_refine_rounds.
 #pragma once
 #include "lfo_common.h"
 
@@ -117,4 +119,21 @@ __device__ __forceinline__ FitBest fit_stage(const double *yc, int n, float sr, 
     for (int w = 1; w < FIT_WAVES; ++w)
         if (fit_less(red[w].R, red[w].c, best.R, best.c)) best = red[w];
     return best;
+}
+
+// rounds 1..L of shape SH from the coarse (R0, f0, phi0), as fit_shape of lfo_fit.hip runs them
+template <int SH>
+__device__ void fit_refine_rounds(const double *yc, int n, float sr, double Syy, double f_min, double f_max, double df, int J, int L,
+                                   FitBest *red, double &R0, double &f0, double &phi0)
+{
+    const double dphi = FIT_TWO_PI / (double)J;
+    for (int l = 1; l <= L; ++l) {
+        const double scale = 1.0 / (double)(1 << l);
+        const double fbase = f0, pbase = phi0;
+        const FitBest r = fit_stage<SH>(yc, n, sr, Syy, 5, 2, 25, fbase, df * scale, pbase, dphi * scale, f_min, f_max, red);
+        if (r.R < R0) {
+            R0 = r.R;
+            fit_decode(r.c, 5, 2, fbase, df * scale, pbase, dphi * scale, f_min, f_max, f0, phi0);
+        }
+    }
 }

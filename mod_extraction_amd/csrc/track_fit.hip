@@ -135,23 +135,6 @@ __global__ __launch_bounds__(TRACK_TILE_THREADS) void track_coarse_kernel(
     if (threadIdx.x == 0) part[(b * FIT_N_SHAPES + (size_t)sh) * gridDim.x + blockIdx.x] = r;
 }
 
-// rounds 1..L of shape SH from the coarse (R0, f0, phi0), as fit_shape of lfo_fit.hip runs them
-template <int SH>
-__device__ void track_refine_shape(const double *yc, int n, float sr, double Syy, double f_min, double f_max, double df, int J, int L,
-                                   FitBest *red, double &R0, double &f0, double &phi0)
-{
-    const double dphi = FIT_TWO_PI / (double)J;
-    for (int l = 1; l <= L; ++l) {
-        const double scale = 1.0 / (double)(1 << l);
-        const double fbase = f0, pbase = phi0;
-        const FitBest r = fit_stage<SH>(yc, n, sr, Syy, 5, 2, 25, fbase, df * scale, pbase, dphi * scale, f_min, f_max, red);
-        if (r.R < R0) {
-            R0 = r.R;
-            fit_decode(r.c, 5, 2, fbase, df * scale, pbase, dphi * scale, f_min, f_max, f0, phi0);
-        }
-    }
-}
-
 __global__ __launch_bounds__(FIT_THREADS) void track_refine_kernel(
     const double *__restrict__ stats, const double *__restrict__ yc_all, const FitBest *__restrict__ part, long long ntiles,
     long long b0, int n, float sr, double f_min, double f_max, double df, int J, int L, int mask, double *__restrict__ res)
@@ -193,13 +176,13 @@ __global__ __launch_bounds__(FIT_THREADS) void track_refine_kernel(
         fit_decode(best.c, J, 0, f_min, df, 0.0, FIT_TWO_PI / (double)J, f_min, f_max, f0, phi0);
     }
     switch (sh) {
-    case LFO_COS: track_refine_shape<LFO_COS>(yc, n, sr, Syy, f_min, f_max, df, J, L, red, R0, f0, phi0); break;
-    case LFO_RECT_COS: track_refine_shape<LFO_RECT_COS>(yc, n, sr, Syy, f_min, f_max, df, J, L, red, R0, f0, phi0); break;
-    case LFO_INV_RECT_COS: track_refine_shape<LFO_INV_RECT_COS>(yc, n, sr, Syy, f_min, f_max, df, J, L, red, R0, f0, phi0); break;
-    case LFO_TRI: track_refine_shape<LFO_TRI>(yc, n, sr, Syy, f_min, f_max, df, J, L, red, R0, f0, phi0); break;
-    case LFO_SAW: track_refine_shape<LFO_SAW>(yc, n, sr, Syy, f_min, f_max, df, J, L, red, R0, f0, phi0); break;
-    case LFO_RSAW: track_refine_shape<LFO_RSAW>(yc, n, sr, Syy, f_min, f_max, df, J, L, red, R0, f0, phi0); break;
-    default: track_refine_shape<LFO_SQR>(yc, n, sr, Syy, f_min, f_max, df, J, L, red, R0, f0, phi0); break;
+    case LFO_COS: fit_refine_rounds<LFO_COS>(yc, n, sr, Syy, f_min, f_max, df, J, L, red, R0, f0, phi0); break;
+    case LFO_RECT_COS: fit_refine_rounds<LFO_RECT_COS>(yc, n, sr, Syy, f_min, f_max, df, J, L, red, R0, f0, phi0); break;
+    case LFO_INV_RECT_COS: fit_refine_rounds<LFO_INV_RECT_COS>(yc, n, sr, Syy, f_min, f_max, df, J, L, red, R0, f0, phi0); break;
+    case LFO_TRI: fit_refine_rounds<LFO_TRI>(yc, n, sr, Syy, f_min, f_max, df, J, L, red, R0, f0, phi0); break;
+    case LFO_SAW: fit_refine_rounds<LFO_SAW>(yc, n, sr, Syy, f_min, f_max, df, J, L, red, R0, f0, phi0); break;
+    case LFO_RSAW: fit_refine_rounds<LFO_RSAW>(yc, n, sr, Syy, f_min, f_max, df, J, L, red, R0, f0, phi0); break;
+    default: fit_refine_rounds<LFO_SQR>(yc, n, sr, Syy, f_min, f_max, df, J, L, red, R0, f0, phi0); break;
     }
     if (tid == 0) {
         double *o = res + (b * FIT_N_SHAPES + (size_t)sh) * 3;

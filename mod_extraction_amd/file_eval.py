@@ -220,7 +220,8 @@ def fit_track(track: T, point_rate: float, rate_hz=(0.25, 8.0), rate_div: Option
 
 
 def score_pair(step, model, dry: T, wet: T, lag: int = 0, polarity: int = 1, hop: Optional[int] = None,
-               fit_rate_hz=(0.25, 8.0), n_samples: int = 88200, batch_size: int = 32, fx_params=None) -> Dict[str, object]:
+               fit_rate_hz=(0.25, 8.0), n_samples: int = 88200, batch_size: int = 32, fx_params=None,
+               rate_track: Optional[dict] = None) -> Dict[str, object]:
     """One dry / wet recording against ``step`` (an ``LFOExtractionThroughEffect``) and its extractor ``model``:
     1. ``alignment.shift_rows`` brings ``wet`` onto ``dry`` by ``lag`` samples and ``polarity`` (+1 / -1) -- K19's convention;
     2. ``extract_lfo_track`` over windows of ``n_samples`` (``dry`` is shown too iff ``step.use_dry``);
@@ -232,7 +233,13 @@ def score_pair(step, model, dry: T, wet: T, lag: int = 0, polarity: int = 1, hop
        dropped: every loss kernel runs at the shapes it is tested at).
     Returns device scalars and tensors: the terms by name, ``rate_hz``, ``shape`` (id of ``modulations.SHAPE_NAMES``),
     ``resid``, ``gain`` () or ``fir`` (K,) when matched, ``track`` (n_t,), ``wet_hat`` (L,), and the Python ints ``n_windows``
-    and ``fit_points``."""
+    and ``fit_points``.
+    ``rate_track``: None, or a dict of ``rate_track.fit_rate_track`` keywords -- ``slice_points`` / ``hop_points``, or ``slice_s``
+    / ``hop_s`` in seconds, converted with the track's point rate; ``rate_hz`` defaults to ``fit_rate_hz``.  The track's rate
+    contour (K25) is then fitted too, the clean LFO it describes (``synth_from_rate_track``) is rendered through step 4 and
+    scored by steps 5 and 6 with a match of its own, and the result gains ``rate_track`` (the ``RateTrack``), ``rate_min_hz``,
+    ``rate_max_hz``, ``rate_resid`` (the mean slice residual), ``fit_wet_hat`` (L,) and ``fit/<name>`` for every term: whether a
+    parametric LFO is enough to reproduce the recording.  With None nothing is added and nothing more is launched."""
     from .alignment import shift_rows
     from .effect_losses import effect_loss_terms
     fn = "score_pair"
@@ -249,27 +256,53 @@ def score_pair(step, model, dry: T, wet: T, lag: int = 0, polarity: int = 1, hop
                    torch.full((1,), float(polarity), dtype=torch.float32, device=dev)).view(L)
     lt = extract_lfo_track(model, w, d if step.use_dry else None, N, hop, batch_size)
     n_t = lt.track.numel()
-    fit, fit_points = fit_track(lt.track, float(step.sr) * (n_t - 1) / (L - 1), fit_rate_hz)
+    point_rate = float(step.sr) * (n_t - 1) / (L - 1)
+    fit, fit_points = fit_track(lt.track, point_rate, fit_rate_hz)
     wet_hat = render_file(step, d, lt.track, fx_params)
-    out: Dict[str, object] = {}
-    with torch.no_grad():
-        if step.match_fir is not None:
-            from .fir_match import match_fir
-            m = match_fir(wet_hat.view(1, L), w.view(1, L), step.match_fir, step.match_fir_centre, step.match_fir_ridge,
-                          step.match_fir_eps, step.match_fir_max_gain)
-            wet_hat, out["fir"] = m.z.view(L), m.taps[0]
-        elif step.match_gain is not None:
-            from .gain import match_gain
-            m = match_gain(wet_hat.view(1, L), w.view(1, L), step.match_gain, step.match_gain_eps, step.match_gain_range)
-            wet_hat, out["gain"] = m.z.view(L), m.gain[0]
-        rows = L // N
-        a, t = wet_hat[:rows * N].view(rows, 1, N), w[:rows * N].view(rows, 1, N)
-        names = list(step.audio_loss_dict)
-        if any(k in ("l1", "mse", "esr", "dc") for k in names):
-            out.update({k: v for k, v in effect_loss_terms(a, t).items() if k in names})
-        for k in names:
-            if k not in out:
-                out[k] = step._loss_module(k)(a, t)
-    out.update(rate_hz=fit.rate_hz[0], shape=fit.shape[0], resid=fit.resid[0], track=lt.track, wet_hat=wet_hat,
+
+    def matched_terms(wet_hat: T) -> Dict[str, object]:
+        """steps 5 and 6 on one render: the terms, ``gain`` or ``fir`` when matched, and the matched ``wet_hat``"""
+        out: Dict[str, object] = {}
+        with torch.no_grad():
+            if step.match_fir is not None:
+                from .fir_match import match_fir
+                m = match_fir(wet_hat.view(1, L), w.view(1, L), step.match_fir, step.match_fir_centre, step.match_fir_ridge,
+                              step.match_fir_eps, step.match_fir_max_gain)
+                wet_hat, out["fir"] = m.z.view(L), m.taps[0]
+            elif step.match_gain is not None:
+                from .gain import match_gain
+                m = match_gain(wet_hat.view(1, L), w.view(1, L), step.match_gain, step.match_gain_eps, step.match_gain_range)
+                wet_hat, out["gain"] = m.z.view(L), m.gain[0]
+            rows = L // N
+            a, t = wet_hat[:rows * N].view(rows, 1, N), w[:rows * N].view(rows, 1, N)
+            names = list(step.audio_loss_dict)
+            if any(k in ("l1", "mse", "esr", "dc") for k in names):
+                out.update({k: v for k, v in effect_loss_terms(a, t).items() if k in names})
+            for k in names:
+                if k not in out:
+                    out[k] = step._loss_module(k)(a, t)
+        out["wet_hat"] = wet_hat
+        return out
+
+    out = matched_terms(wet_hat)
+    out.update(rate_hz=fit.rate_hz[0], shape=fit.shape[0], resid=fit.resid[0], track=lt.track, wet_hat=out.pop("wet_hat"),
                n_windows=len(lt.starts), fit_points=fit_points)
+    if rate_track is not None:
+        from .rate_track import fit_rate_track, synth_from_rate_track
+        if not isinstance(rate_track, dict):
+            raise ValueError(f"{fn}: rate_track must be None or a dict of fit_rate_track keywords, got {rate_track!r}")
+        kw = dict(rate_track)
+        for sec, pts in (("slice_s", "slice_points"), ("hop_s", "hop_points")):
+            if sec in kw:
+                if pts in kw:
+                    raise ValueError(f"{fn}: rate_track has both {sec} and {pts}")
+                kw[pts] = max(1, int(round(float(kw.pop(sec)) * point_rate)))
+        if "slice_points" not in kw:
+            raise ValueError(f"{fn}: rate_track needs slice_points or slice_s")
+        kw.setdefault("rate_hz", fit_rate_hz)
+        rt = fit_rate_track(lt.track, point_rate, **kw)
+        scored = matched_terms(render_file(step, d, synth_from_rate_track(rt), fx_params))
+        out.update({f"fit/{k}": scored[k] for k in step.audio_loss_dict})
+        out.update(rate_track=rt, rate_min_hz=rt.rate_hz[0].min(), rate_max_hz=rt.rate_hz[0].max(),
+                   rate_resid=rt.resid[0].mean(), fit_wet_hat=scored["wet_hat"])
     return out

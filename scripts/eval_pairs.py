@@ -11,6 +11,9 @@ Recordings at another rate than the config's ``sr``: ``--resample_cache_dir DIR`
 ``DIR/dry`` and ``DIR/wet`` first (``resample.convert_tree``) and scores those; without it such files are dropped.
 Per pair ``file_eval.score_pair`` runs on channel 0 of the whole file: the extractor's LFO track, the rate and shape fitted
 to it, the re-render from the file's first sample, ONE gain or FIR for the file, and the step's audio losses.
+``--rate_track SLICE_S[:HOP_S]`` also fits the track's rate contour (``rate_track.fit_rate_track`` on slices of SLICE_S seconds,
+HOP_S apart, default half a slice) and adds ``rate_min_hz``, ``rate_max_hz``, ``rate_resid``, the per-slice ``rate_times_s`` and
+``rate_track_hz``, and ``fit/<loss>``: the losses of a re-render from the clean LFO that contour describes.
 """
 import argparse
 import json
@@ -21,6 +24,7 @@ import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 from mod_extraction_amd import cli, datasets, file_eval, lightning, modulations, resample  # noqa: E402
+from mod_extraction_amd import rate_track as rate_track_mod  # noqa: E402
 
 
 def main() -> int:
@@ -34,7 +38,17 @@ def main() -> int:
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--resample_cache_dir", default=None,
                     help="bring both directories to the config's sr on the device, into DIR/dry and DIR/wet, and score those")
+    ap.add_argument("--rate_track", default=None, metavar="SLICE_S[:HOP_S]",
+                    help="also fit a rate contour on slices of SLICE_S seconds (HOP_S apart, default half a slice)")
     a = ap.parse_args()
+    rate_track = None
+    if a.rate_track is not None:
+        try:
+            parts = [float(v) for v in a.rate_track.split(":")]
+            assert len(parts) in (1, 2) and all(v > 0.0 for v in parts)
+        except (ValueError, AssertionError):
+            raise SystemExit(f"--rate_track takes SLICE_S or SLICE_S:HOP_S in seconds, got {a.rate_track!r}") from None
+        rate_track = dict(zip(("slice_s", "hop_s"), parts))
     cfg = cli.apply_links(cli.load_config(a.config))
     dev = torch.device(a.device)
     step = cli.instantiate(cfg["model"]).to(dev)
@@ -68,7 +82,7 @@ def main() -> int:
         al = table.get(name)
         lag, polarity = (al.lag, al.polarity) if al is not None else (0, 1)
         out = file_eval.score_pair(step, step.model, dry[:n].to(dev), wet[:n].to(dev), lag=lag, polarity=polarity, hop=a.hop,
-                                   n_samples=n_samples, batch_size=a.batch_size)
+                                   n_samples=n_samples, batch_size=a.batch_size, rate_track=rate_track)
         row.update(lag=lag, polarity=polarity, aligned=bool(al.ok) if al is not None else None,
                    n_windows=out["n_windows"], fit_points=out["fit_points"], track_points=int(out["track"].numel()),
                    rate_hz=float(out["rate_hz"]), shape=modulations.SHAPE_NAMES[int(out["shape"])], resid=float(out["resid"]))
@@ -77,6 +91,13 @@ def main() -> int:
             row["fir"] = [float(v) for v in out["fir"]]
         if "gain" in out:
             row["gain"] = float(out["gain"])
+        if rate_track is not None:
+            rt = out["rate_track"]
+            row.update({k: float(out[k]) for k in ("rate_min_hz", "rate_max_hz", "rate_resid")})
+            row.update({f"fit/{k}": float(out[f"fit/{k}"]) for k in step.audio_loss_dict})
+            row["rate_shape"] = modulations.SHAPE_NAMES[int(rt.shape[0])]
+            row["rate_times_s"] = [float(v) for v in rate_track_mod.rate_at(rt)[0]]
+            row["rate_track_hz"] = [float(v) for v in rt.rate_hz[0]]
         print(json.dumps(row), flush=True)
     return 0
 
