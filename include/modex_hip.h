@@ -470,7 +470,8 @@ int mx_head_bwd(const float *p6, const float *slope, const float *wout, const fl
 
 /* ---- K8: LFO loss -- mod_extraction/lightning.py:33-62 + losses.py:70-102 (l1, fdl1, sdl1, mse,
  * 'mean' reductions).  y_hat, y (B,n), n <= 2048; part (B,4) workspace; losses (5,) = l1, fdl1,
- * sdl1, mse, weighted total (weights <= 0 are logged but not added); grad (B,n) or NULL. */
+ * sdl1, mse, weighted total (weights <= 0 are logged but not added); grad (B,n) or NULL = d total / d y_hat
+ * (so a term with a weight <= 0 is absent from it too). */
 int mx_lfo_loss(const float *y_hat, const float *y, int64_t B, int64_t n, float w_l1, float w_fdl1,
                 float w_sdl1, float w_mse, float *part, float *losses, float *grad, void *stream);
 

@@ -168,7 +168,8 @@ MX_EXPORT int mx_head_bwd(const float *p6, const float *slope, const float *wout
 
 // ---- LFO loss (forward terms + gradient) -------------------------------------------------------
 // y_hat, y: (B, n).  part (B, 4): per-clip sums of |e|, |d1 e|, |d2 e|, e^2 (un-normalised).
-// grad (B, n) optional: d(sum_k w_k loss_k)/d y_hat with 'mean' reductions over B*n, B*(n-2), B*(n-4).
+// grad (B, n) optional: d total / d y_hat = d(sum over w_k > 0 of w_k loss_k)/d y_hat with 'mean' reductions over B*n,
+// B*(n-2), B*(n-4).
 __global__ __launch_bounds__(256) void lfo_loss_kernel(const float *__restrict__ y_hat,
                                                        const float *__restrict__ y, int n, int B, float w_l1,
                                                        float w_fd, float w_sd, float w_mse,
@@ -213,10 +214,11 @@ __global__ __launch_bounds__(256) void lfo_loss_kernel(const float *__restrict__
         if (tid < 4) part[(size_t)b * 4 + tid] = (float)(r4[0][tid] + r4[1][tid] + r4[2][tid] + r4[3][tid]);
     }
     if (grad) {
-        const float c_l1 = w_l1 / ((float)B * (float)n);
-        const float c_fd = n > 2 ? w_fd / ((float)B * (float)(n - 2)) : 0.0f;
-        const float c_sd = n > 4 ? w_sd / ((float)B * (float)(n - 4)) : 0.0f;
-        const float c_mse = 2.0f * w_mse / ((float)B * (float)n);
+        // the gradient is that of the TOTAL: a weight <= 0 leaves its term out of both (lightning.py:48 `if weighting > 0:`)
+        const float c_l1 = w_l1 > 0.0f ? w_l1 / ((float)B * (float)n) : 0.0f;
+        const float c_fd = n > 2 && w_fd > 0.0f ? w_fd / ((float)B * (float)(n - 2)) : 0.0f;
+        const float c_sd = n > 4 && w_sd > 0.0f ? w_sd / ((float)B * (float)(n - 4)) : 0.0f;
+        const float c_mse = w_mse > 0.0f ? 2.0f * w_mse / ((float)B * (float)n) : 0.0f;
         for (int k = tid; k < n; k += 256) {
             const float e = a[k] - t[k];
             float g = c_l1 * (e > 0.0f ? 1.0f : (e < 0.0f ? -1.0f : 0.0f)) + c_mse * e;
