@@ -25,6 +25,8 @@ HEADER_TRACK = os.path.join(_HERE, "csrc", "track_fit_abi.h")
 HEADER_RESAMPLE = os.path.join(_HERE, "csrc", "resample_abi.h")
 # K25's likewise
 HEADER_RATE = os.path.join(_HERE, "csrc", "rate_track_abi.h")
+# K26's likewise
+HEADER_WARP = os.path.join(_HERE, "csrc", "warp_abi.h")
 
 # the parameter kinds of the C ABI: any pointer, and these six scalars (modex_hip.h states the rule)
 _SCALARS = {"int64_t": ctypes.c_int64, "int32_t": ctypes.c_int32, "uint64_t": ctypes.c_uint64, "uint32_t": ctypes.c_uint32,
@@ -84,6 +86,11 @@ RESAMPLE_OUT_TILE = int(re.search(r"#define\s+MX_RESAMPLE_OUT_TILE\s+(\d+)", _he
 SIGNATURES_RATE = parse_signatures(_header_text(HEADER_RATE))
 RATE_TRACK_LIMITS = {k: int(v) for k, v in re.findall(r"#define\s+MX_RATE_TRACK_(\w+)\s+(\d+)\s*$", _header_text(HEADER_RATE),
                                                       flags=re.M)}
+# the fifth table: the entry points of csrc/warp_abi.h (mx_warp_*), and that header's limits
+SIGNATURES_WARP = parse_signatures(_header_text(HEADER_WARP))
+WARP_OUT_TILE = int(re.search(r"#define\s+MX_WARP_OUT_TILE\s+(\d+)", _header_text(HEADER_WARP)).group(1))
+WARP_MAX_DRIFT = float(re.search(r"#define\s+MX_WARP_MAX_DRIFT\s+(\S+)", _header_text(HEADER_WARP)).group(1))
+WARP_MAX_OFFSET = float(re.search(r"#define\s+MX_WARP_MAX_OFFSET\s+(\S+)", _header_text(HEADER_WARP)).group(1))
 
 # measurement twins (same signatures): the dependent chain of the sample-recurrent kernels without global traffic
 PROBE_TWINS = ("mx_flanger_fwd", "mx_phaser_fwd", "mx_lstm_fwd", "mx_lstm_bwd_l1")
@@ -101,7 +108,8 @@ def load() -> ctypes.CDLL:
         lib = ctypes.CDLL(SO_PATH)
         # the tables are read as module attributes here, at call time
         for table, header in ((SIGNATURES, "include/modex_hip.h"), (SIGNATURES_TRACK, "csrc/track_fit_abi.h"),
-                              (SIGNATURES_RESAMPLE, "csrc/resample_abi.h"), (SIGNATURES_RATE, "csrc/rate_track_abi.h")):
+                              (SIGNATURES_RESAMPLE, "csrc/resample_abi.h"), (SIGNATURES_RATE, "csrc/rate_track_abi.h"),
+                              (SIGNATURES_WARP, "csrc/warp_abi.h")):
             for name, argtypes in table.items():
                 fn = getattr(lib, name, None)
                 if fn is None:              # the ABI number does not cover an added entry point: name what a stale build lacks

@@ -594,9 +594,42 @@ class RandomAudioChunkDryWetDataModule(_SyntheticDataModule):
         if not dry_d or not wet_d or not os.path.isdir(dry_d) or not os.path.isdir(wet_d):
             return None
         from . import datasets
+        wet_d = self._undrifted(which, dry_d, wet_d)
         kw = {k: self.ignored_args[k] for k in self._DS_KEYS + self._ALIGN_KEYS if k in self.ignored_args}
         n_ex = self.train_num_examples_per_epoch if which == "train" else self.val_num_examples_per_epoch
         return datasets.RandomAudioChunkDryWetDataset(dry_d, wet_d, self.n_samples, self.sr, num_examples_per_epoch=n_ex, **kw)
+
+    def _undrifted(self, which: str, dry_d: str, wet_d: str) -> str:
+        """With ``align_drift_cache_dir`` (K26): ``alignment.warp_tree`` puts every wet file of ``wet_d`` on its dry file's time
+        base under ``<cache>/wet_<which>`` -- after the ``resample_cache_dir`` conversion, on the device ``setup`` was given --
+        and that tree is returned; the dataset is then built on it unchanged, so its own K19 estimate still runs (and finds
+        lag 0, polarity +1 on every trusted pair), and pairs whose raw frame counts differed are no longer dropped: a warped
+        wet has its dry's length.  The key needs ``align_max_lag_ms`` (the reach of the estimate, as for K19) and takes
+        ``align_drift_probe_ms`` (default 8192 samples) and ``align_drift_n_probes`` (default 16).  Every rank converts; the
+        conversion is deterministic and files appear by rename.  Without the key: ``wet_d`` as it is, no other work."""
+        cache = self.ignored_args.get("align_drift_cache_dir")
+        if not cache:
+            return wet_d
+        ms = self.ignored_args.get("align_max_lag_ms")
+        if ms is None or int(self.sr) != self.sr:
+            raise ValueError(f"align_drift_cache_dir needs align_max_lag_ms and an integer sr, got {ms!r} and {self.sr!r}")
+        from . import alignment
+        probe_ms = self.ignored_args.get("align_drift_probe_ms")
+        probe = 8192 if probe_ms is None else int(round(float(probe_ms) * 1e-3 * self.sr))
+        dst = os.path.join(cache, f"wet_{which}")
+        table = alignment.warp_tree(dry_d, wet_d, dst, int(self.sr), int(round(float(ms) * 1e-3 * self.sr)),
+                                    ext=self.ignored_args.get("ext", "wav"), device=self._setup_device, probe_points=probe,
+                                    n_probes=int(self.ignored_args.get("align_drift_n_probes", 16)),
+                                    min_corr=float(self.ignored_args.get("align_min_corr", 0.5)))
+        self._pair_drift[which] = table
+        log.info("%s pairs, drift: %s", which, alignment.summarise_drift(table))
+        return dst
+
+    @property
+    def pair_drift(self) -> Dict[str, Any]:
+        """``{"train": table, "val": table}``: each pair set's ``{relative path: alignment.PairDrift}`` of
+        ``align_drift_cache_dir``, None where there is no such set or the key is not given."""
+        return {w: getattr(self, "_pair_drift", {}).get(w) for w in ("train", "val")}
 
     @property
     def pair_alignment(self) -> Dict[str, Any]:
@@ -615,6 +648,7 @@ class RandomAudioChunkDryWetDataModule(_SyntheticDataModule):
 
     def setup(self, device: torch.device, rank: int = 0, seed: int = 43) -> None:
         self._setup_device = self._device = device
+        self._pair_drift: Dict[str, Any] = {}
         self._pairs = {w: self._pair_dataset(w) for w in ("train", "val")}
         for which, ds in self._pairs.items():
             if ds is not None and ds.align_max_lag is not None:

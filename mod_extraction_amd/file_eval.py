@@ -221,7 +221,7 @@ def fit_track(track: T, point_rate: float, rate_hz=(0.25, 8.0), rate_div: Option
 
 def score_pair(step, model, dry: T, wet: T, lag: int = 0, polarity: int = 1, hop: Optional[int] = None,
                fit_rate_hz=(0.25, 8.0), n_samples: int = 88200, batch_size: int = 32, fx_params=None,
-               rate_track: Optional[dict] = None) -> Dict[str, object]:
+               rate_track: Optional[dict] = None, drift=None) -> Dict[str, object]:
     """One dry / wet recording against ``step`` (an ``LFOExtractionThroughEffect``) and its extractor ``model``:
     1. ``alignment.shift_rows`` brings ``wet`` onto ``dry`` by ``lag`` samples and ``polarity`` (+1 / -1) -- K19's convention;
     2. ``extract_lfo_track`` over windows of ``n_samples`` (``dry`` is shown too iff ``step.use_dry``);
@@ -239,21 +239,43 @@ def score_pair(step, model, dry: T, wet: T, lag: int = 0, polarity: int = 1, hop
     contour (K25) is then fitted too, the clean LFO it describes (``synth_from_rate_track``) is rendered through step 4 and
     scored by steps 5 and 6 with a match of its own, and the result gains ``rate_track`` (the ``RateTrack``), ``rate_min_hz``,
     ``rate_max_hz``, ``rate_resid`` (the mean slice residual), ``fit_wet_hat`` (L,) and ``fit/<name>`` for every term: whether a
-    parametric LFO is enough to reproduce the recording.  With None nothing is added and nothing more is launched."""
-    from .alignment import shift_rows
+    parametric LFO is enough to reproduce the recording.  With None nothing is added and nothing more is launched.
+    ``drift``: None, an ``alignment.PairDrift`` or an ``(offset, drift)`` pair of floats (K26) -- step 1 is then
+    ``alignment.warp_rows`` along that line onto ``dry``'s length instead of ``shift_rows``, so ``wet`` may have any length; a
+    ``PairDrift`` brings its own polarity (``polarity`` stays +1), an untrusted one (``ok`` False) is refused, and ``lag != 0``
+    beside ``drift`` is a ValueError.  The result gains the floats ``drift_ppm`` and ``lag_offset``.  With None step 1 is the
+    ``shift_rows`` launch as before and nothing is added."""
+    from .alignment import PairDrift, shift_rows, warp_rows
     from .effect_losses import effect_loss_terms
     fn = "score_pair"
     d, w = _file_row(dry, "dry", fn), _file_row(wet, "wet", fn)
     L, N = d.numel(), _int(n_samples, "n_samples", fn)
-    if w.numel() != L or w.device != d.device:
+    if (drift is None and w.numel() != L) or w.device != d.device:
         raise ValueError(f"{fn}: dry and wet must have the same length on the same device, got {L} and {w.numel()}")
     if polarity not in (1, -1):
         raise ValueError(f"{fn}: polarity must be +1 or -1, got {polarity!r}")
+    line = None
+    if drift is not None:
+        if _int(lag, "lag", fn) != 0:
+            raise ValueError(f"{fn}: lag = {lag} beside drift: the line's offset is the lag")
+        if isinstance(drift, PairDrift):
+            if not drift.ok or polarity != 1:
+                raise ValueError(f"{fn}: a PairDrift must be trusted (ok) and brings its own polarity; got {drift!r}, polarity = {polarity}")
+            line, polarity = (float(drift.offset), float(drift.drift)), drift.polarity
+        else:
+            try:
+                line = (float(drift[0]), float(drift[1]))
+                assert len(drift) == 2
+            except (TypeError, ValueError, IndexError, AssertionError):
+                raise ValueError(f"{fn}: drift must be None, a PairDrift or (offset, drift), got {drift!r}") from None
     if getattr(step, "fx_head", None) is not None:
         raise ValueError(f"{fn}: file-level scoring of a step with fx_head is out of scope")
     dev = d.device
-    w = shift_rows(w.view(1, L), torch.full((1,), _int(lag, "lag", fn), dtype=torch.int32, device=dev),
-                   torch.full((1,), float(polarity), dtype=torch.float32, device=dev)).view(L)
+    if line is None:
+        w = shift_rows(w.view(1, L), torch.full((1,), _int(lag, "lag", fn), dtype=torch.int32, device=dev),
+                       torch.full((1,), float(polarity), dtype=torch.float32, device=dev)).view(L)
+    else:
+        w = warp_rows(w, line[0], line[1], n_out=L, polarity=polarity)
     lt = extract_lfo_track(model, w, d if step.use_dry else None, N, hop, batch_size)
     n_t = lt.track.numel()
     point_rate = float(step.sr) * (n_t - 1) / (L - 1)
@@ -287,6 +309,8 @@ def score_pair(step, model, dry: T, wet: T, lag: int = 0, polarity: int = 1, hop
     out = matched_terms(wet_hat)
     out.update(rate_hz=fit.rate_hz[0], shape=fit.shape[0], resid=fit.resid[0], track=lt.track, wet_hat=out.pop("wet_hat"),
                n_windows=len(lt.starts), fit_points=fit_points)
+    if line is not None:
+        out.update(drift_ppm=1e6 * line[1], lag_offset=line[0])
     if rate_track is not None:
         from .rate_track import fit_rate_track, synth_from_rate_track
         if not isinstance(rate_track, dict):

@@ -14,6 +14,11 @@ to it, the re-render from the file's first sample, ONE gain or FIR for the file,
 ``--rate_track SLICE_S[:HOP_S]`` also fits the track's rate contour (``rate_track.fit_rate_track`` on slices of SLICE_S seconds,
 HOP_S apart, default half a slice) and adds ``rate_min_hz``, ``rate_max_hz``, ``rate_resid``, the per-slice ``rate_times_s`` and
 ``rate_track_hz``, and ``fit/<loss>``: the losses of a re-render from the clean LFO that contour describes.
+``--drift``: for pairs whose two files ran on two clocks.  Per pair ``alignment.estimate_file_drift`` measures the line of lags
+on the two whole files (they are on the device already; the config's ``align_max_lag_ms`` is its reach) and, where it is
+trusted, ``score_pair`` warps the wet along it onto the dry's length instead of shifting it; the line gains ``drift_ppm``,
+``lag_offset``, ``drift_resid`` and ``drift_ok``.  An untrusted pair is scored by its constant lag as without the flag.  Pairs
+whose lengths differ by more than ``end_buffer_n_samples`` are still dropped by the pairing.
 """
 import argparse
 import json
@@ -23,7 +28,7 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
-from mod_extraction_amd import cli, datasets, file_eval, lightning, modulations, resample  # noqa: E402
+from mod_extraction_amd import alignment, cli, datasets, file_eval, lightning, modulations, resample  # noqa: E402
 from mod_extraction_amd import rate_track as rate_track_mod  # noqa: E402
 
 
@@ -40,6 +45,10 @@ def main() -> int:
                     help="bring both directories to the config's sr on the device, into DIR/dry and DIR/wet, and score those")
     ap.add_argument("--rate_track", default=None, metavar="SLICE_S[:HOP_S]",
                     help="also fit a rate contour on slices of SLICE_S seconds (HOP_S apart, default half a slice)")
+    ap.add_argument("--drift", action="store_true",
+                    help="estimate every pair's line of lags (two clocks) on the files and warp the wet along it")
+    ap.add_argument("--drift_probe_points", type=int, default=8192)
+    ap.add_argument("--drift_n_probes", type=int, default=16)
     a = ap.parse_args()
     rate_track = None
     if a.rate_track is not None:
@@ -69,6 +78,8 @@ def main() -> int:
         dry_dir, wet_dir, n_samples, sr, check_dataset=False, end_buffer_n_samples=int(data.get("end_buffer_n_samples", 0)),
         align_max_lag_ms=data.get("align_max_lag_ms"), align_n_probes=int(data.get("align_n_probes", 8)),
         align_min_corr=float(data.get("align_min_corr", 0.5)))
+    if a.drift and ds.align_max_lag is None:
+        raise SystemExit("--drift needs the config's align_max_lag_ms: it is the reach of the estimate")
     table = ds.estimate_alignment(dev) if ds.align_max_lag is not None else {}
     for dry_path in ds.dry_paths:
         name = os.path.basename(dry_path)
@@ -81,8 +92,19 @@ def main() -> int:
             continue
         al = table.get(name)
         lag, polarity = (al.lag, al.polarity) if al is not None else (0, 1)
-        out = file_eval.score_pair(step, step.model, dry[:n].to(dev), wet[:n].to(dev), lag=lag, polarity=polarity, hop=a.hop,
-                                   n_samples=n_samples, batch_size=a.batch_size, rate_track=rate_track)
+        est = None
+        if a.drift:
+            dry_d, wet_d = dry.to(dev), wet.to(dev)
+            est = alignment.estimate_file_drift(dry_d, wet_d, ds.align_max_lag, a.drift_probe_points, a.drift_n_probes,
+                                                min_corr=ds.align_min_corr)
+            row.update(drift_ppm=1e6 * est.drift, lag_offset=est.offset, drift_resid=est.resid, drift_ok=est.ok)
+        if est is not None and est.ok:
+            out = file_eval.score_pair(step, step.model, dry_d, wet_d, hop=a.hop, n_samples=n_samples, batch_size=a.batch_size,
+                                       rate_track=rate_track, drift=est)
+            lag, polarity = 0, est.polarity
+        else:
+            out = file_eval.score_pair(step, step.model, dry[:n].to(dev), wet[:n].to(dev), lag=lag, polarity=polarity, hop=a.hop,
+                                       n_samples=n_samples, batch_size=a.batch_size, rate_track=rate_track)
         row.update(lag=lag, polarity=polarity, aligned=bool(al.ok) if al is not None else None,
                    n_windows=out["n_windows"], fit_points=out["fit_points"], track_points=int(out["track"].numel()),
                    rate_hz=float(out["rate_hz"]), shape=modulations.SHAPE_NAMES[int(out["shape"])], resid=float(out["resid"]))
