@@ -27,6 +27,8 @@ HEADER_RESAMPLE = os.path.join(_HERE, "csrc", "resample_abi.h")
 HEADER_RATE = os.path.join(_HERE, "csrc", "rate_track_abi.h")
 # K26's likewise
 HEADER_WARP = os.path.join(_HERE, "csrc", "warp_abi.h")
+# K27's likewise
+HEADER_SHAPER = os.path.join(_HERE, "csrc", "shaper_match_abi.h")
 
 # the parameter kinds of the C ABI: any pointer, and these six scalars (modex_hip.h states the rule)
 _SCALARS = {"int64_t": ctypes.c_int64, "int32_t": ctypes.c_int32, "uint64_t": ctypes.c_uint64, "uint32_t": ctypes.c_uint32,
@@ -91,6 +93,10 @@ SIGNATURES_WARP = parse_signatures(_header_text(HEADER_WARP))
 WARP_OUT_TILE = int(re.search(r"#define\s+MX_WARP_OUT_TILE\s+(\d+)", _header_text(HEADER_WARP)).group(1))
 WARP_MAX_DRIFT = float(re.search(r"#define\s+MX_WARP_MAX_DRIFT\s+(\S+)", _header_text(HEADER_WARP)).group(1))
 WARP_MAX_OFFSET = float(re.search(r"#define\s+MX_WARP_MAX_OFFSET\s+(\S+)", _header_text(HEADER_WARP)).group(1))
+# the sixth table: the entry points of csrc/shaper_match_abi.h (mx_shaper_match_*), and that header's limits
+SIGNATURES_SHAPER = parse_signatures(_header_text(HEADER_SHAPER))
+SHAPER_CHUNK = int(re.search(r"#define\s+MX_SHAPER_CHUNK\s+(\d+)", _header_text(HEADER_SHAPER)).group(1))
+SHAPER_MAX_ORDER = int(re.search(r"#define\s+MX_SHAPER_MAX_ORDER\s+(\d+)", _header_text(HEADER_SHAPER)).group(1))
 
 # measurement twins (same signatures): the dependent chain of the sample-recurrent kernels without global traffic
 PROBE_TWINS = ("mx_flanger_fwd", "mx_phaser_fwd", "mx_lstm_fwd", "mx_lstm_bwd_l1")
@@ -109,7 +115,7 @@ def load() -> ctypes.CDLL:
         # the tables are read as module attributes here, at call time
         for table, header in ((SIGNATURES, "include/modex_hip.h"), (SIGNATURES_TRACK, "csrc/track_fit_abi.h"),
                               (SIGNATURES_RESAMPLE, "csrc/resample_abi.h"), (SIGNATURES_RATE, "csrc/rate_track_abi.h"),
-                              (SIGNATURES_WARP, "csrc/warp_abi.h")):
+                              (SIGNATURES_WARP, "csrc/warp_abi.h"), (SIGNATURES_SHAPER, "csrc/shaper_match_abi.h")):
             for name, argtypes in table.items():
                 fn = getattr(lib, name, None)
                 if fn is None:              # the ABI number does not cover an added entry point: name what a stale build lacks

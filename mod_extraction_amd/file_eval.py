@@ -228,7 +228,7 @@ def score_pair(step, model, dry: T, wet: T, lag: int = 0, polarity: int = 1, hop
     3. ``fit_track``: rate, shape and residual of the whole track (``fit_points`` is its number of points);
     4. ``render_file`` from the track;
     5. the match ``step`` is configured for (``match_fir`` / ``match_gain``) with the WHOLE FILE as one row: one FIR or one
-       gain per file;
+       gain per file; then, with ``match_shaper``, ONE curve per file on that row (``shaper`` (K,) in the result);
     6. the terms of ``step.audio_loss_dict`` on the matched render, cut into consecutive rows of ``n_samples`` (the tail is
        dropped: every loss kernel runs at the shapes it is tested at).
     Returns device scalars and tensors: the terms by name, ``rate_hz``, ``shape`` (id of ``modulations.SHAPE_NAMES``),
@@ -295,6 +295,11 @@ def score_pair(step, model, dry: T, wet: T, lag: int = 0, polarity: int = 1, hop
                 from .gain import match_gain
                 m = match_gain(wet_hat.view(1, L), w.view(1, L), step.match_gain, step.match_gain_eps, step.match_gain_range)
                 wet_hat, out["gain"] = m.z.view(L), m.gain[0]
+            if getattr(step, "match_shaper", None) is not None:     # ONE curve per file, on the linearly matched row (K27)
+                from .shaper import match_shaper
+                m = match_shaper(wet_hat.view(1, L), w.view(1, L), step.match_shaper, step.match_shaper_even,
+                                 step.match_shaper_ridge, step.match_shaper_max_gain)
+                wet_hat, out["shaper"] = m.z.view(L), m.coeffs[0]
             rows = L // N
             a, t = wet_hat[:rows * N].view(rows, 1, N), w[:rows * N].view(rows, 1, N)
             names = list(step.audio_loss_dict)

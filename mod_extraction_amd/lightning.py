@@ -274,11 +274,16 @@ class _EffectAudioLossFn(torch.autograd.Function):
         if P:                                     # the warm-up window: match and losses on columns [P:], dy zero on [:P]
             dy, wet_hat, a, t = _EffectAudioLossFn._windowed(step, rendered, wet, P, weighted)
         else:
-            if step.match_gain is not None or step.match_fir is not None:
+            if step._matched:
                 # every row in one launch sequence, dry rows included: the losses see the match
                 wet_hat = step._match_rows(rendered, wet)
             a, t = wet_hat.unsqueeze(1), wet.unsqueeze(1)
             dy = effect_loss_grad(a, t, step.audio_loss_dict, values=weighted, **step._grad_modules())
+            if step.match_shaper is not None:     # d loss / d (shaped rows) -> d loss / d (the linearly matched rows), in place
+                from .shaper import match_shaper_backward
+                match_shaper_backward(dy, step._shaper_in, wet, step._shaper, step.match_shaper_even, step.match_shaper_ridge,
+                                      out=dy)
+                step._shaper_in = None            # a batch-sized buffer: not kept between steps
             if step.match_gain is not None:       # d loss / d z -> d loss / d (the un-matched render), in place
                 from .gain import match_gain_backward
                 match_gain_backward(dy, rendered, wet, step._gain, step.match_gain, step.match_gain_eps, out=dy)
@@ -317,7 +322,7 @@ class _EffectAudioLossFn(torch.autograd.Function):
         from .effect_losses import effect_loss_grad
         seen, target = rendered[:, P:], wet[:, P:]
         wet_hat = rendered
-        if step.match_gain is not None or step.match_fir is not None:
+        if step._matched:
             wet_hat = torch.empty_like(rendered)
             wet_hat[:, :P] = rendered[:, :P]
             step._match_rows(seen, target, out=wet_hat[:, P:])
@@ -325,6 +330,14 @@ class _EffectAudioLossFn(torch.autograd.Function):
         dz = effect_loss_grad(a, t, step.audio_loss_dict, values=weighted, **step._grad_modules())
         dy = torch.empty_like(rendered)
         dy[:, :P] = 0.0
+        if step.match_shaper is not None:         # first the curve's backward: in place on the dense dz when a linear match
+            from .shaper import match_shaper_backward       # follows, else straight into the window of dy
+            linear = step.match_gain is not None or step.match_fir is not None
+            match_shaper_backward(dz, step._shaper_in, target, step._shaper, step.match_shaper_even, step.match_shaper_ridge,
+                                  out=dz if linear else dy[:, P:])
+            step._shaper_in = None                # a batch-sized buffer: not kept between steps
+            if not linear:
+                return dy, wet_hat, a, t
         if step.match_gain is not None:
             from .gain import match_gain_backward
             match_gain_backward(dz, seen, target, step._gain, step.match_gain, step.match_gain_eps, out=dy[:, P:])
@@ -451,6 +464,18 @@ class LFOExtractionThroughEffect(BaseLightingModule):
       whose losses would see P samples or fewer raises a ``ValueError``.  One P per module; ``render`` is unchanged.  None,
       or a value that gives P = 0, is the step without it.  How large P must be: DESIGN section 7, "Warm-up of a chunk cut
       from a file".
+    * ``match_shaper`` (optional, alone or together with ``match_gain`` or ``match_fir``): the order P in 1 .. 7 of one
+      memoryless polynomial curve per clip, fitted from the (linearly matched) re-render onto ``wet`` before any loss sees
+      it (``shaper.match_shaper``, K27), with ``match_shaper_even`` (the even powers too, for asymmetric curves),
+      ``match_shaper_ridge`` and the guard ``match_shaper_max_gain`` on sum |c|.  It absorbs what a compander, an op-amp
+      stage or a re-amp box does to the peaks of a recorded wet.  The linear match runs first and the curve is fitted on its
+      rows, aligned and at the level of ``wet``; the losses, the returned ``wet_hat``, the logged terms and validation see
+      the shaped rows; d loss / d z passes through ``shaper.match_shaper_backward`` (in place; it reads the linear match's
+      rows and ``wet``), then through the linear match's backward, then into the adjoints, which read the un-matched render;
+      under ``warmup_ms`` all of it works on columns [P:].  A training step logs ``shaper/linear`` (mean c_1),
+      ``shaper/curve`` (mean of sum_{k >= 2} |c_k|) and ``shaper/flagged``; ``data_dict["shaper"]`` is the (B, K)
+      coefficients; ``render`` stays un-matched.  Without it the step's launches are unchanged.  What the match is not:
+      DESIGN section 7, "Saturation of recorded pairs".
     * ``loss_dict`` (optional, default none): an LFO-domain term (lightning.py:33-62) added to the loss when the batch carries
       ``mod_sig``; it is logged as ``{prefix}/lfo_{name}``.
     The LFO enters the effect at the extractor's own rate (n_frames points, resampled in-kernel exactly as the data path
@@ -503,7 +528,11 @@ class LFOExtractionThroughEffect(BaseLightingModule):
                  match_fir_ridge: float = 1e-6,
                  match_fir_eps: float = 1e-8,
                  match_fir_max_gain: float = 20.0,
-                 warmup_ms: Optional[float] = None) -> None:
+                 warmup_ms: Optional[float] = None,
+                 match_shaper: Optional[int] = None,
+                 match_shaper_even: bool = False,
+                 match_shaper_ridge: float = 1e-9,
+                 match_shaper_max_gain: float = 20.0) -> None:
         super().__init__({} if loss_dict is None else loss_dict)
         self._set_pre_emph(pre_emph_filter_cfs, pre_emph_low_pass)
         from . import fx
@@ -532,6 +561,16 @@ class LFOExtractionThroughEffect(BaseLightingModule):
         check_mode("ls" if match_gain is None else match_gain, match_gain_eps, match_gain_range, "match_gain")
         self.match_gain, self.match_gain_eps, self.match_gain_range = match_gain, match_gain_eps, match_gain_range
         self._gain = None                       # the gain.GainMatch of the last matched batch
+        from .shaper import check_shaper
+        # validated without match_shaper too, as the gain's and the FIR's arguments are
+        check_shaper(5 if match_shaper is None else match_shaper, match_shaper_even, match_shaper_ridge, match_shaper_max_gain,
+                     "match_shaper")
+        self.match_shaper, self.match_shaper_even = match_shaper, match_shaper_even
+        self.match_shaper_ridge, self.match_shaper_max_gain = match_shaper_ridge, match_shaper_max_gain
+        self._shaper = None                     # the shaper.ShaperMatch of the last matched batch
+        self._shaper_in = None                  # the rows it was fitted on (the linear match's z, or the render itself), from
+                                                # _match_rows until the curve's backward has read them
+        self._matched = match_gain is not None or match_fir is not None or match_shaper is not None
         from .effect_losses import GRAD_NAMES
         if should_stretch:
             raise NotImplementedError("should_stretch is not supported when training through the rendered effect")
@@ -594,20 +633,35 @@ class LFOExtractionThroughEffect(BaseLightingModule):
             self.step_metric_names = self.step_metric_names + ["gain/mean", "gain/std", "gain/clamped"]
         if match_fir is not None:
             self.step_metric_names = self.step_metric_names + ["fir/dc_gain", "fir/l1", "fir/flagged"]
+        if match_shaper is not None:
+            self.step_metric_names = self.step_metric_names + ["shaper/linear", "shaper/curve", "shaper/flagged"]
 
     def _match_rows(self, rendered: T, wet: T, out: Optional[T] = None) -> T:
         """The rows of ``rendered`` brought to the level of ``wet`` (``gain.match_gain``: two launches for all rows) or to its
         level, tone and sub-sample lag (``fir_match.match_fir``: three); the ``GainMatch`` / ``FirMatch`` is kept in ``_gain``
         / ``_fir`` for the backward, the log and ``data_dict``.  ``out``: where the matched rows go (the warm-up window: a view
-        of the step's wet_hat)."""
+        of the step's wet_hat).  With ``match_shaper`` the linear match (if any) runs first, into a buffer of its own, and the
+        curve (``shaper.match_shaper``, K27: three calls) is fitted on its rows -- aligned and at the level of ``wet``; the
+        ``ShaperMatch`` is kept in ``_shaper`` and the rows it read in ``_shaper_in``."""
+        kw = {} if out is None else {"out": out}
+        if self.match_shaper is None:
+            return self._match_linear(rendered, wet, kw)
+        from .shaper import match_shaper
+        linear = self.match_gain is not None or self.match_fir is not None
+        self._shaper_in = self._match_linear(rendered, wet, {}) if linear else rendered
+        self._shaper = match_shaper(self._shaper_in, wet, self.match_shaper, self.match_shaper_even, self.match_shaper_ridge,
+                                    self.match_shaper_max_gain, **kw)
+        return self._shaper.z
+
+    def _match_linear(self, rendered: T, wet: T, kw) -> T:
+        """The gain or the FIR match of ``_match_rows``; ``kw``: its ``out``, if any."""
         if self.match_fir is not None:
             from .fir_match import match_fir
             self._fir = match_fir(rendered, wet, self.match_fir, self.match_fir_centre, self.match_fir_ridge,
-                                  self.match_fir_eps, self.match_fir_max_gain, **({} if out is None else {"out": out}))
+                                  self.match_fir_eps, self.match_fir_max_gain, **kw)
             return self._fir.z
         from .gain import match_gain
-        self._gain = match_gain(rendered, wet, self.match_gain, self.match_gain_eps, self.match_gain_range,
-                                **({} if out is None else {"out": out}))
+        self._gain = match_gain(rendered, wet, self.match_gain, self.match_gain_eps, self.match_gain_range, **kw)
         return self._gain.z
 
     def _warmup(self, n: int) -> int:
@@ -908,13 +962,14 @@ class LFOExtractionThroughEffect(BaseLightingModule):
             wet_hat = wet_hat.unsqueeze(1)
         else:
             wet_hat, loss = self.render(dry, mod_sig_hat, fx_params, latent), None
-            if self.match_gain is not None or self.match_fir is not None:   # validation: the terms below are taken on the matched rows
+            if self._matched:                                       # validation: the terms below are taken on the matched rows
                 if P:                                               # matched on the window, into [P:] of a (B, 1, N) buffer
                     rendered, wet_hat = wet_hat, torch.empty_like(wet_hat)
                     wet_hat[..., :P] = rendered[..., :P]
                     self._match_rows(rendered[..., P:], wet[..., P:], out=wet_hat[..., P:])
                 else:
                     wet_hat = self._match_rows(wet_hat, wet)
+                self._shaper_in = None                              # read by a backward only
         if prefix is not None or loss is None:
             with torch.no_grad():
                 missing = [k for k in self.audio_loss_dict if k not in terms]
@@ -988,6 +1043,11 @@ class LFOExtractionThroughEffect(BaseLightingModule):
             self.log("fir/dc_gain", h.sum(1).mean())
             self.log("fir/l1", h.abs().sum(1).mean())
             self.log("fir/flagged", (self._fir.flags != 0).float().mean())
+        if is_training and self.match_shaper is not None:           # three (B, K) / (B,) device reductions: no host sync
+            c = self._shaper.coeffs
+            self.log("shaper/linear", c[:, 0].mean())
+            self.log("shaper/curve", c[:, 1:].abs().sum(1).mean())
+            self.log("shaper/flagged", (self._shaper.flags != 0).float().mean())
         data_dict = {"dry": dry.detach(), "wet": wet.detach(), "wet_hat": wet_hat.detach(),
                      "mod_sig_hat": mod_sig_hat.detach()}
         if self.fx_head is not None:
@@ -996,6 +1056,8 @@ class LFOExtractionThroughEffect(BaseLightingModule):
             data_dict["gain"] = self._gain.gain
         if self.match_fir is not None:
             data_dict["fir"] = self._fir.taps
+        if self.match_shaper is not None:
+            data_dict["shaper"] = self._shaper.coeffs
         if self.warmup_samples:
             data_dict["warmup"] = self.warmup_samples
         if mod_sig is not None:

@@ -10,7 +10,8 @@ The config's ``model`` must be a ``lightning.LFOExtractionThroughEffect`` (witho
 Recordings at another rate than the config's ``sr``: ``--resample_cache_dir DIR`` converts both directories on the device into
 ``DIR/dry`` and ``DIR/wet`` first (``resample.convert_tree``) and scores those; without it such files are dropped.
 Per pair ``file_eval.score_pair`` runs on channel 0 of the whole file: the extractor's LFO track, the rate and shape fitted
-to it, the re-render from the file's first sample, ONE gain or FIR for the file, and the step's audio losses.
+to it, the re-render from the file's first sample, ONE gain or FIR for the file (and, with the step's
+``match_shaper``, ONE curve: ``shaper``, its coefficients), and the step's audio losses.
 ``--rate_track SLICE_S[:HOP_S]`` also fits the track's rate contour (``rate_track.fit_rate_track`` on slices of SLICE_S seconds,
 HOP_S apart, default half a slice) and adds ``rate_min_hz``, ``rate_max_hz``, ``rate_resid``, the per-slice ``rate_times_s`` and
 ``rate_track_hz``, and ``fit/<loss>``: the losses of a re-render from the clean LFO that contour describes.
@@ -113,6 +114,8 @@ def main() -> int:
             row["fir"] = [float(v) for v in out["fir"]]
         if "gain" in out:
             row["gain"] = float(out["gain"])
+        if "shaper" in out:
+            row["shaper"] = [float(v) for v in out["shaper"]]
         if rate_track is not None:
             rt = out["rate_track"]
             row.update({k: float(out[k]) for k in ("rate_min_hz", "rate_max_hz", "rate_resid")})
